@@ -2,7 +2,11 @@
 """bench.py - img/s of the CT-WGAN adversarial iteration (N_CRITIC critic steps + 1 generator step)
 of CT_gan_cifar_resnet.py on MI355X, synthetic 32x32x3 data, fp32 (the reference's dtype).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the record line; --dump-outputs DIR also writes what the last timed
+step computed (loss terms, trained weights) as DIR/<name>.npy.  Everything else the record can carry - roofline, CPU baseline,
+host-fed loop, the all-fp32-MFMA and autograd-critic A/Bs, the GP unit, at N > 1 the collective timing and the A/B legs - runs
+only with --full.
 N > 1: either launched under torch.distributed.run (one rank per GPU, RCCL; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from
 the environment), or - when WORLD_SIZE is not set - this process becomes a LAUNCHER: before anything touches the GPU it
 starts N rank processes of itself (127.0.0.1 rendezvous on a free port), relays rank 0's JSON line and exits with the
@@ -74,6 +78,11 @@ def main():
                          'staging kernel (the span TF/CT_gan_cifar_resnet.py:394-412 times includes the feed) - reported as config.host_feed')
     ap.add_argument('--spawn-check', action='store_true',
                     help='ranks only join the process group, all-reduce their rank numbers and report (no GPU work): the launcher test')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beside the headline: roofline, CPU baseline, host-fed loop, fp32-MFMA-only and '
+                         'autograd-critic A/Bs, GP unit; N > 1: collective timing and the A/B legs (the --no-* / --feed options still apply)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss terms, trained weights) to DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
     if 'WORLD_SIZE' not in os.environ and (args.launcher == 'always' or (args.launcher == 'auto' and args.gpus > 1)):
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -83,6 +92,10 @@ def main():
         args.no_roofline = args.no_cpu_baseline = args.no_ab_legs = True
         args.feed = 'device'
         args.ar_in_graph, args.no_graph = LEGS[args.leg]['ar_in_graph'], LEGS[args.leg]['no_graph']
+    if not args.full:
+        # a plain run: the headline loop only (the collective timing of N > 1 is gated on args.full below)
+        args.no_roofline = args.no_cpu_baseline = args.no_ab_legs = True
+        args.feed = 'device'
     # N > 1: the RECORD leg runs the eager side-stream collective (ddp.FlatAllReduce between per-step graphs: the path the 2-rank gloo tests
     # cover) unless --ar-in-graph asks for the captured one; the captured RCCL collectives and the split flush are A/B legs, run as fresh
     # rank groups after the record is out (run_ab_legs): a hang or a watchdog abort there cannot cost the record
@@ -172,6 +185,8 @@ def main():
     p50 = per_step[len(per_step) // 2]
     last = {k: float(out[k].item()) for k in ('cost', 'wgan', 'ct', 'gp', 'acgan') if out.get(k) is not None}
     last_cost = last['cost']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, getattr(eng, 'g_out', None), trainer)
     ms_per_step = 1e3 * dt / args.steps
     imgs = R.cfg.N_CRITIC * B * world * args.steps
     value = imgs / dt
@@ -195,7 +210,7 @@ def main():
     # the overlap the north star asks for, behind a switch) and the same launches with the collective replaced by nothing
     # (the replicas drift apart from there on: nothing below compares them).  exposed = loop time - loop time without the collective.
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         def timed_loop(e, k):
             nonlocal it
             for _ in range(3):
@@ -461,7 +476,7 @@ def run_ab_legs(args, rank, world, legs, ports, steps, extra=()):
         env = {k: v for k, v in os.environ.items() if not k.startswith('TORCHELASTIC_')}     # (the agent's store is not the leg's store)
         env.update(MASTER_PORT=str(port), MASTER_ADDR='127.0.0.1')
         cmd = [sys.executable, os.path.abspath(__file__), '--gpus', str(world), '--steps', str(steps), '--warmup', '3', '--leg', name,
-               '--launcher', 'never'] + (['--backend', args.backend] if args.backend else []) + list(extra)
+               '--launcher', 'never', '--full'] + (['--backend', args.backend] if args.backend else []) + list(extra)
         t0 = time.time()
         pr = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE if rank == 0 else subprocess.DEVNULL, stderr=sys.stderr)
         try:
@@ -700,6 +715,8 @@ def run_unconditional(args):
     per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     last = {k: float(out[k].item()) for k in ('cost', 'wgan_only', 'ct', 'gp') if out.get(k) is not None}
     sane = all(v == v and abs(v) < 1e4 for v in last.values())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, getattr(eng, 'g_out', None), tr)
     ms_per_step = 1e3 * dt / args.steps
     n_crit = M.cfg.CRITIC_ITERS
     roofline = None
@@ -1043,6 +1060,37 @@ def measure_gp_unit(trainer, batch, torch):
             'note': 'frac_executed = (time the launched FLOPs take at the peak of the pipe each kernel runs on: fp32 MFMA 157.3, split mode '
                     '2500/6 TFLOP/s) / measured time - the roofline fraction (ConvMeanPool runs as a 4x4 stride-2 conv: 2.25x fewer MACs on '
                     '69 % of F_D); effective_frac prices the same time with the reference formulation\'s 139.3 GFLOP at the fp32 MFMA peak'}
+
+
+DUMP_MAX_ELEMENTS = 4 << 20          # per array (16 MB of float32): larger arrays are written as a fixed, seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, d_out, g_out, trainer):
+    """--dump-outputs: what the last timed iteration handed back - the last critic step's loss terms (d_<name>), the generator step's
+    (g_<name>) - and the weights it left (critic_params / generator_params, the flat Adam buffers), as <path>/<name>.npy.  An array of
+    more than DUMP_MAX_ELEMENTS is replaced by its elements at DUMP_MAX_ELEMENTS sorted positions drawn from default_rng(0): the same
+    positions for every run of the same configuration."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for prefix, src in (('d_', d_out), ('g_', g_out)):
+        for k, v in sorted((src or {}).items()):
+            if isinstance(v, torch.Tensor):
+                arrays[prefix + k] = v
+    arrays['critic_params'] = trainer.d_opt.theta
+    arrays['generator_params'] = trainer.g_opt.theta
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32).numpy().reshape(t.shape)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit('bench: --dump-outputs would write more than %d bytes' % DUMP_MAX_BYTES)
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def build_provenance():
