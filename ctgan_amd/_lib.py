@@ -187,6 +187,8 @@ SIGNATURES = {
     'ctgan_softmax_ce_bwd': (c_int, [_p, _p, _p, c_int32, c_int32, _p, _p]),
     'ctgan_mean_diff_fwd': (c_int, [_p, c_int32, c_int32, c_float, c_float, _p, _p]),
     'ctgan_mean_diff_bwd': (c_int, [_p, c_int32, c_int32, c_float, c_float, _p, _p]),
+    'ctgan_gan_loss_fwd': (c_int, [_p, c_int32, c_int32, _p, _p]),
+    'ctgan_gan_loss_bwd': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
     'ctgan_critic_heads_fwd': (c_int, [_p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_critic_heads_bwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_tail_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, _p]),
@@ -211,6 +213,9 @@ SIGNATURES = {
     'ctgan_adam_step_packed': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float, c_float,
                                        c_float, c_float, _p]),
     'ctgan_pack': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p]),
+    'ctgan_rmsprop_step': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
+    'ctgan_rmsprop_step_packed': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float, c_float,
+                                          c_float, c_float, _p]),
     'ctgan_dropout_rng': (c_int, [_p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_dropout_rng_mask': (c_int, [_p, _p, _p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_lrelu_dropout_rng': (c_int, [_p, _p, _p, c_int64, c_float, c_float, c_uint64, c_uint64, _p, _p]),

@@ -2,8 +2,8 @@
 
 The reference has no resume for its CIFAR/MNIST scripts (`np.save("param.pyn", ...)` of the critic only,
 TF/CT_gan_cifar.py:216-222; a `tf.train.Saver` in the LSUN script).  Here the registry's names make it
-trivial: one file holds every parameter by its reference name and layout, both Adam slot sets (m, v,
-beta-power state, step count), the Philox step counter and the loop iteration - enough for a bit-exact
+trivial: one file holds every parameter by its reference name and layout, both optimizers' slots (Adam m, v and
+beta-power state, or RMSProp ms - tagged with the optimizer kind, so a resume under another MODE fails clearly -, step count), the Philox step counter and the loop iteration - enough for a bit-exact
 continuation (tests/test_gpu_checkpoint.py)."""
 import torch
 

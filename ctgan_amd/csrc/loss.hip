@@ -164,6 +164,55 @@ __global__ void mean_diff_bwd_kernel(const float* __restrict__ gout, int na, int
     gx[i] = gout[0] * (i < na ? sa / (float)na : sb / (float)nb);
 }
 
+// ---- loss heads of the 'dcgan' / 'lsgan' objectives (ctgan_gan_loss_fwd/bwd in ctgan_hip.h): d = [D(real) ; D(fake)] for the critic
+// kinds, D(fake) for the generator kinds.  Row i < nr of a critic kind is a real row (label 1), the rest fake (label 0); the generator
+// kinds label every row 1.
+__device__ __forceinline__ float bce_logits(float x, float z) {          // max(x,0) - x z + log1p(exp(-|x|)): finite for any finite x
+    return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x)));
+}
+__device__ __forceinline__ float sigmoidf_stable(float x) {
+    if (x >= 0.f) return 1.f / (1.f + expf(-x));
+    const float e = expf(x);
+    return e / (1.f + e);
+}
+// per-row loss term, and its derivative, before the 1/n of the mean and the 1/2 of the critic kinds
+__device__ __forceinline__ float gan_term(int kind, bool real_row, float x) {
+    switch (kind) {
+    case CTGAN_LOSS_BCE_D: return bce_logits(x, real_row ? 1.f : 0.f);
+    case CTGAN_LOSS_BCE_G: return bce_logits(x, 1.f);
+    case CTGAN_LOSS_LS_D: { const float r = real_row ? x - 1.f : x; return r * r; }
+    default: { const float r = x - 1.f; return r * r; }
+    }
+}
+__device__ __forceinline__ float gan_dterm(int kind, bool real_row, float x) {
+    switch (kind) {
+    case CTGAN_LOSS_BCE_D: return real_row ? -sigmoidf_stable(-x) : sigmoidf_stable(x);      // sigmoid(x) - z; sigmoid(x) - 1 = -sigmoid(-x)
+    case CTGAN_LOSS_BCE_G: return -sigmoidf_stable(-x);
+    case CTGAN_LOSS_LS_D: return 2.f * (real_row ? x - 1.f : x);
+    default: return 2.f * (x - 1.f);
+    }
+}
+__device__ __forceinline__ bool gan_kind_is_critic(int kind) { return kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D; }
+
+__global__ __launch_bounds__(256) void gan_loss_fwd_kernel(const float* __restrict__ d, int B, int kind, float* __restrict__ out) {
+    __shared__ float sh[4];
+    const bool critic = gan_kind_is_critic(kind);
+    float a = 0.f, b = 0.f;                                               // real rows (generator kinds: all rows), fake rows
+    for (int i = threadIdx.x; i < B; i += 256) a += gan_term(kind, critic, d[i]);
+    if (critic)
+        for (int i = threadIdx.x; i < B; i += 256) b += gan_term(kind, false, d[B + i]);
+    a = block_sum(a, sh);
+    b = block_sum(b, sh);
+    if (threadIdx.x == 0) out[0] = critic ? (b / (float)B + a / (float)B) / 2.f : a / (float)B;
+}
+__global__ void gan_loss_bwd_kernel(const float* __restrict__ d, const float* __restrict__ gout, int B, int kind, float* __restrict__ gd) {
+    const bool critic = gan_kind_is_critic(kind);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (critic ? 2 * B : B)) return;
+    const float w = critic ? 2.f * (float)B : (float)B;
+    gd[i] = gout[0] * (gan_dterm(kind, !critic || i < B, d[i]) / w);
+}
+
 
 // ---- all critic loss heads of one D step in one launch (forward) / one launch (backward) ------------------
 // d [3B], f [3B,nf], a [3B,ncls] are the outputs of the batched dropout passes: rows [0,B) real pass 1,
@@ -903,6 +952,18 @@ int ctgan_mean_diff_fwd(const float* x, int32_t na, int32_t nb, float sa, float 
     if (!x || !out || na < 0 || nb < 0 || na + nb <= 0) return ctgan_fail(CTGAN_E_BADARG, "mean_diff_fwd: bad argument");
     hipLaunchKernelGGL(mean_diff_fwd_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(s), x, na, nb, sa, sb, out);
     return ctgan_check_launch("mean_diff_fwd");
+}
+int ctgan_gan_loss_fwd(const float* d, int32_t B, int32_t kind, float* out, ctgan_stream_t s) {
+    if (!d || !out || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_LS_G) return ctgan_fail(CTGAN_E_BADARG, "gan_loss_fwd: bad argument");
+    hipLaunchKernelGGL(gan_loss_fwd_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(s), d, B, kind, out);
+    return ctgan_check_launch("gan_loss_fwd");
+}
+int ctgan_gan_loss_bwd(const float* d, const float* gout, int32_t B, int32_t kind, float* gd, ctgan_stream_t s) {
+    if (!d || !gout || !gd || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_LS_G)
+        return ctgan_fail(CTGAN_E_BADARG, "gan_loss_bwd: bad argument");
+    const int n = (kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D) ? 2 * B : B;
+    hipLaunchKernelGGL(gan_loss_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(s), d, gout, B, kind, gd);
+    return ctgan_check_launch("gan_loss_bwd");
 }
 int ctgan_mean_diff_bwd(const float* gout, int32_t na, int32_t nb, float sa, float sb, float* gx, ctgan_stream_t s) {
     if (!gout || !gx || na < 0 || nb < 0 || na + nb <= 0) return ctgan_fail(CTGAN_E_BADARG, "mean_diff_bwd: bad argument");

@@ -105,6 +105,61 @@ __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, 
     }
 }
 
+// tf.train.RMSPropOptimizer (decay rho, momentum 0, not centered; TF's ApplyRMSProp):  ms += (g^2 - ms)(1 - rho);
+// mom = lr g / sqrt(ms + eps);  theta -= mom - followed here by the weight clip of the 'wgan' objective (tf.clip_by_value after every
+// critic update, TF/CT_gan_mnist.py:134-143) when clip > 0.  Contraction off for the same reason as adam_elem: the plain and the packed
+// kernel round identically.  A non-finite scaled gradient skips the element (counted in state[3], as adam_elem) - its weight is still
+// clipped, since the reference's clip op runs over every critic variable whatever the update did.
+__device__ __forceinline__ float clip_to(float x, float c) { return c > 0.f ? fminf(fmaxf(x, -c), c) : x; }
+__device__ __forceinline__ void rmsprop_elem(float& th, float& ms, float graw, float gscale, float rho, float eps, float lr, float clip,
+                                             float* skipped) {
+#pragma clang fp contract(off)
+    const float gi = graw * gscale;
+    if (!(fabsf(gi) <= 3.0e38f)) { atomicAdd(skipped, 1.0f); th = clip_to(th, clip); return; }
+    const float mi = ms + (gi * gi - ms) * (1.f - rho);
+    ms = mi;
+    th = clip_to(th - (gi * lr) / sqrtf(mi + eps), clip);
+}
+__global__ void rmsprop_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ ms, long long n, float* state,
+                               float rho, float eps, float clip, float gscale) {
+    const float lr = state[0];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        rmsprop_elem(th[i], ms[i], g[i], gscale, rho, eps, lr, clip, state + 3);
+}
+// pack_kernel + rmsprop_kernel in one launch: adam_packed_kernel's layout (pointer table in the arguments, grid.y = tensor, 4-wide body
+// when the segment allows it, scalar otherwise); the flat bucket is still written.
+__global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ flat, float* __restrict__ th, float* __restrict__ ms,
+                                      float* state, float rho, float eps, float clip, float gscale) {
+    const float lr = state[0];
+    const float* src = t.src[blockIdx.y];
+    const long long off = t.dst_off[blockIdx.y], n = t.n[blockIdx.y];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    if (((n | off) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {        // (the flat buffers are 16-B aligned: checked by the host)
+        const long long n4 = n >> 2;
+        const float4* src4 = reinterpret_cast<const float4*>(src);
+        float4* f4 = reinterpret_cast<float4*>(flat + off);
+        float4* th4 = reinterpret_cast<float4*>(th + off);
+        float4* ms4 = reinterpret_cast<float4*>(ms + off);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+            const float4 gr = src ? src4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            f4[i] = gr;
+            float4 mm = ms4[i], tt = th4[i];
+            const float gv[4] = {gr.x, gr.y, gr.z, gr.w};
+            float* mp = &mm.x; float* tp = &tt.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rmsprop_elem(tp[k], mp[k], gv[k], gscale, rho, eps, lr, clip, state + 3);
+            ms4[i] = mm; th4[i] = tt;
+        }
+    } else {
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+            const float gr = src ? src[i] : 0.f;
+            flat[off + i] = gr;
+            rmsprop_elem(th[off + i], ms[off + i], gr, gscale, rho, eps, lr, clip, state + 3);
+        }
+    }
+}
+
 // ---- Philox4x32-10 (Salmon et al., SC'11); constants of the Random123 reference
 
 __global__ void rng_uniform_kernel(float* __restrict__ out, long long n, uint64_t seed, uint32_t sid,
@@ -414,6 +469,33 @@ int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, co
     hipLaunchKernelGGL(adam_packed_kernel, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t,
                        flat, theta, m, v, state, beta1, beta2, eps, grad_scale);
     return ctgan_check_launch("adam_step_packed");
+}
+int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                       float grad_scale, ctgan_stream_t s) {
+    if (!theta || !g || !ms || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step: bad argument");
+    if (n == 0) return CTGAN_OK;
+    hipLaunchKernelGGL(rmsprop_kernel, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, ms,
+                       (long long)n, state, rho, eps, clip, grad_scale);
+    return ctgan_check_launch("rmsprop_step");
+}
+int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
+                              ctgan_stream_t s) {
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0)
+        return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step_packed: bad argument");
+    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "rmsprop_step_packed: more than %d tensors", PACK_MAX);
+    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(ms)) & 15)
+        return ctgan_fail(CTGAN_E_UNSUPPORTED, "rmsprop_step_packed: flat buffers must be 16-byte aligned");
+    PackTable t;
+    long long mx = 1;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (counts[i] < 0 || dst_offs[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step_packed: negative extent");
+        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs[i]; t.n[i] = counts[i];
+        if (t.n[i] > mx) mx = t.n[i];
+    }
+    hipLaunchKernelGGL(rmsprop_packed_kernel, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s),
+                       t, flat, theta, ms, state, rho, eps, clip, grad_scale);
+    return ctgan_check_launch("rmsprop_step_packed");
 }
 int ctgan_adam_advance(float* state, float beta1, float beta2, ctgan_stream_t s) {
     if (!state) return ctgan_fail(CTGAN_E_BADARG, "adam_advance: null");

@@ -33,7 +33,8 @@ MERGED_BWD = _os.environ.get('CTGAN_DCGAN_MERGED_BWD', '1') != '0'
 def usable(tr, rnd, fake, real_in):
     m = tr.mod
     spec = getattr(m, 'SCHEDULED_CRITIC', None)
-    return bool(MERGED_BWD and spec is not None and rnd is None and fake is not None and tr.piecewise and F.LRELU_DROP_FUSION and F.DEFER_WGRADS
+    # (the schedule is the CT objective's: consistency term and gradient penalty over an unnormalised critic)
+    return bool(MERGED_BWD and spec is not None and tr.mode.loss == 'ct' and rnd is None and fake is not None and tr.piecewise and F.LRELU_DROP_FUSION and F.DEFER_WGRADS
                 and m.cfg.DIM % 32 == 0 and fake.is_contiguous() and real_in.is_contiguous())
 
 

@@ -10,13 +10,20 @@ and the two dropout passes over the real batch share it; the WGAN difference, th
 gradient penalty are one fused loss-heads launch each way (rows ordered real, fake, real); the dead 4th call `disc_fake_2` and the extra
 generators are not executed.  Without injected draws (`rnd=None`) the dropout masks are regenerated from the
 Philox streams inside the kernels.
+
+The scripts' other MODE branches - 'wgan' (weight-clipped WGAN, RMSProp), 'dcgan' (sigmoid cross-entropy, Adam) and 'lsgan' (least
+squares, RMSProp) - run on the same trainer from the module's MODES table (GanMode): only D(real) and D(fake) reach their losses (TF
+prunes the other critic calls of the graph), evaluated as one batch of 2B rows [real ; fake] whose batch-normalised layers keep one
+statistic group per reference call.
 """
+from typing import NamedTuple
+
 import torch
 
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatRMSProp
 from .rng import DeviceRNG
 
 
@@ -30,6 +37,34 @@ TRUNK_SHARE = _os.environ.get('CTGAN_UNCOND_TRUNK_SHARE', '1') != '0'
 BATCH_FAKES = _os.environ.get('CTGAN_DCGAN_BATCH_FAKES', '1') != '0'
 
 
+class GanMode(NamedTuple):
+    """One MODE branch of a script: its objective, optimizer and loop literals (TF/CT_gan_mnist.py:122-206,238-249;
+    TF/CT_gan_64x64.py:490-579,634-646)."""
+    loss: str                    # 'ct' (WGAN + consistency term + gradient penalty), 'wgan', 'bce' (MODE 'dcgan'), 'ls' (MODE 'lsgan')
+    optimizer: str               # 'adam' | 'rmsprop' (the same for critic and generator)
+    lr: float = None             # None: the module's CT learning rate (cfg.LR, or its lr(iteration))
+    betas: tuple = None          # Adam (beta1, beta2); None: the module's ADAM_BETAS
+    clip: float = None           # critic weights clipped to [-clip, clip] after every critic update
+    critic_iters: int = None     # critic steps per iteration; None: cfg.CRITIC_ITERS
+
+
+CT_MODE = GanMode('ct', 'adam')
+
+
+def validate_mode(module_name, modes, mode):
+    """Config(MODE=...) of the modules with a MODES table: a value no branch of the script codes raises."""
+    if mode not in modes:
+        raise NotImplementedError('%s: MODE %r is not supported (supported: %s)' % (module_name, mode, ', '.join(sorted(modes))))
+
+
+def mode_of(module):
+    modes = getattr(module, 'MODES', None)
+    if modes is None:                # the ResNet / LSUN scripts have no MODE switch: their CT objective
+        return CT_MODE
+    validate_mode(module.__name__, modes, module.cfg.MODE)
+    return modes[module.cfg.MODE]
+
+
 class DCGANTrainer:
     def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
@@ -40,9 +75,18 @@ class DCGANTrainer:
         self.rng = DeviceRNG(seed, rank, self.dev)
         self.d_named = lib.named_params_with_name('Discriminator', trainable_only=True)
         self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
-        b1, b2 = getattr(module, 'ADAM_BETAS', (0.5, 0.9))
-        self.d_opt = FlatAdam(self.d_named, b1, b2)
-        self.g_opt = FlatAdam(self.g_named, b1, b2)
+        self.mode = mode_of(module)
+        self.disc_iters = self.mode.critic_iters or module.cfg.CRITIC_ITERS     # critic steps per iteration
+        if self.mode.optimizer == 'rmsprop':
+            self.d_opt = FlatRMSProp(self.d_named, clip=self.mode.clip)
+            self.g_opt = FlatRMSProp(self.g_named)
+        else:
+            b1, b2 = self.mode.betas or getattr(module, 'ADAM_BETAS', (0.5, 0.9))
+            self.d_opt = FlatAdam(self.d_named, b1, b2)
+            self.g_opt = FlatAdam(self.g_named, b1, b2)
+        # the clip op also covers the critic's non-trainable BatchNorm moving statistics; nothing else writes them (training-mode
+        # statistics only), so clamping them once, at the first critic update, is exact
+        self._stats_to_clip = [p for n, p in lib.named_params_with_name('Discriminator') if n in lib._non_trainable] if self.mode.clip else []
         self.towers = getattr(module, 'GEN_TOWERS', 1)                    # generator calls per batch, each with its own BN statistics
         self.piecewise = getattr(module, 'PIECEWISE_LINEAR_CRITIC', True)
         self.iteration = 0
@@ -62,7 +106,44 @@ class DCGANTrainer:
             self._seed_val = self.loss_scale
         return self._seed
 
+    def lr(self):
+        """The learning rate of this iteration's updates: the mode's literal, or the module's CT rate."""
+        if self.mode.lr is not None:
+            return self.mode.lr
+        return self.mod.lr(self.iteration) if hasattr(self.mod, 'lr') else self.mod.cfg.LR
+
+    def clip_stats(self):
+        """The clip op on the critic's moving statistics (see __init__): run once, after the first critic update."""
+        if self._stats_to_clip:
+            with torch.no_grad():
+                for p in self._stats_to_clip:
+                    p.clamp_(-self.mode.clip, self.mode.clip)
+            self._stats_to_clip = []
+
+    def _critic(self, x, u, groups):
+        """The critic on rows made of `groups` reference calls (each its own BatchNorm statistics) - the non-CT objectives."""
+        m = self.mod
+        return m.Discriminator(x, u=u, groups=groups) if u is not None else m.Discriminator(x, rng=self.rng, groups=groups)
+
+    def _d_losses_plain(self, real_in, rnd, fake):
+        """Critic cost of the 'wgan' / 'dcgan' / 'lsgan' objectives over D(real) (masks u_real) and D(fake) (masks u_fake) - one batch of
+        2B rows, two statistic groups per generator tower."""
+        m, B = self.mod, self.mod.cfg.BATCH_SIZE
+        with torch.no_grad():
+            if fake is None:
+                fake = self._gen(B, rnd['z'] if rnd is not None else None)
+            real = m.real_prep(real_in)
+        u = [torch.cat([a, c], 0) for a, c in zip(rnd['u_real'], rnd['u_fake'])] if rnd is not None else None
+        d, _ = self._critic(torch.cat([real, fake], 0), u, 2 * self.towers)
+        if self.mode.loss == 'wgan':
+            cost = F.mean_diff(d, B, B, -1.0, 1.0)             # mean(D(fake)) - mean(D(real))
+        else:
+            cost = F.gan_loss(d, B, self.mode.loss, 'd')
+        return {'cost': cost, 'fake': fake, 'd_real': d[:B].detach(), 'd_fake': d[B:].detach()}
+
     def d_losses(self, real_in, rnd=None, fake=None):
+        if self.mode.loss != 'ct':
+            return self._d_losses_plain(real_in, rnd, fake)
         m, cfg = self.mod, self.mod.cfg
         B = cfg.BATCH_SIZE
         with torch.no_grad():
@@ -130,11 +211,19 @@ class DCGANTrainer:
         m, B = self.mod, self.mod.cfg.BATCH_SIZE
         x = self._gen(B, rnd['z'] if rnd is not None else None)
         with F.weight_grads(False):
-            d, _ = m.Discriminator(x, u=rnd['u_fake']) if rnd is not None else m.Discriminator(x, rng=self.rng)
-        return {'cost': F.mean_diff(d, B, 0, -1.0, 0.0), 'samples': x}
+            u = rnd['u_fake'] if rnd is not None else None
+            if self.mode.loss == 'ct':
+                d, _ = m.Discriminator(x, u=u) if rnd is not None else m.Discriminator(x, rng=self.rng)
+            else:
+                d, _ = self._critic(x, u, self.towers)
+        if self.mode.loss in ('ct', 'wgan'):
+            cost = F.mean_diff(d, B, 0, -1.0, 0.0)                # -mean(D(fake))
+        else:
+            cost = F.gan_loss(d, B, self.mode.loss, 'g')
+        return {'cost': cost, 'samples': x}
 
     def _apply(self, opt, grads):
-        opt.set_lr(self.mod.lr(self.iteration) if hasattr(self.mod, 'lr') else self.mod.cfg.LR)
+        opt.set_lr(self.lr())
         scale = 1.0 / (self.world * self.loss_scale)
         if self.allreduce is None or self.world <= 1:
             opt.update(grads, scale, rng=self.rng)          # bucket + Adam: one launch; end of the step (beta powers, Philox counter): one launch
@@ -153,7 +242,8 @@ class DCGANTrainer:
     def d_step(self, real_in, rnd=None, fake=None):
         self.rng.begin_step()
         out, grads = self.d_grads(real_in, rnd, fake=fake)
-        self._apply(self.d_opt, grads)
+        self._apply(self.d_opt, grads)          # (the weight clip of MODE 'wgan' is fused into the update, on every rank)
+        self.clip_stats()
         out['grads'] = dict(zip([n for n, _ in self.d_named], self._unscaled(grads)))
         return out
 
@@ -171,7 +261,7 @@ class DCGANTrainer:
         if iteration > 0:
             self.g_step()
         out = None
-        n = self.mod.cfg.CRITIC_ITERS
+        n = self.disc_iters
         fakes = self.generate_fakes(n) if BATCH_FAKES else None
         for i in range(n):
             out = self.d_step(next_batch(), fake=None if fakes is None else fakes[i])

@@ -187,7 +187,7 @@ class GraphedTrainer:
         from . import kernels as K
         K.reset_capture_workspaces()
         opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in (o.m, o.v, o.state)] + [t.rng.ctr]
+        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
         snap = [b.clone() for b in bufs]
         steps = [o.t for o in opts]
         for o in opts:
@@ -374,7 +374,7 @@ class GraphedDCGANTrainer:
         self.it_graph = None
         self.it_out = None
         self.it_graph_error = None
-        n_it = trainer.mod.cfg.CRITIC_ITERS
+        n_it = trainer.disc_iters
         self.real_all = torch.zeros((n_it,) + tuple(real_shape), dtype=real_dtype, device=trainer.dev) if self.batch_fakes else None
         self.adam_in_graph = trainer.world == 1
         self.d_graph = self.g_graph = None
@@ -392,12 +392,12 @@ class GraphedDCGANTrainer:
     def _it_body(self):
         g_out = self._body('g')
         fakes = self._f_body()
-        return {'g': g_out, 'd': [self._body('d', self.real_all[i], fakes[i]) for i in range(self.t.mod.cfg.CRITIC_ITERS)]}
+        return {'g': g_out, 'd': [self._body('d', self.real_all[i], fakes[i]) for i in range(self.t.disc_iters)]}
 
     def _f_body(self):
         lib.bump_epoch('Generator')       # runs after the generator update of the iteration
         F.prepare_filters()
-        return self.t.generate_fakes(self.t.mod.cfg.CRITIC_ITERS)
+        return self.t.generate_fakes(self.t.disc_iters)
 
     def _body(self, which, real=None, fake=None):
         t = self.t
@@ -426,7 +426,7 @@ class GraphedDCGANTrainer:
         from . import kernels as K
         K.reset_capture_workspaces()
         opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in (o.m, o.v, o.state)] + [t.rng.ctr]
+        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
         snap = [b.clone() for b in bufs]
         steps = [o.t for o in opts]
         for o in opts:
@@ -477,8 +477,7 @@ class GraphedDCGANTrainer:
         return self.d_graph is not None
 
     def _lr(self):
-        m = self.t.mod
-        return m.lr(self.t.iteration) if hasattr(m, 'lr') else m.cfg.LR
+        return self.t.lr()
 
     def d_step(self, real_in, fake=None):
         t = self.t
@@ -496,6 +495,7 @@ class GraphedDCGANTrainer:
             lib.bump_epoch()           # the in-graph Adam step ran after the graph's own filter rebuild (see GraphedTrainer._weights_moved)
         else:
             self._reduce_update(t.d_opt)
+        t.clip_stats()
         return self.d_out
 
     def g_step(self):
@@ -520,9 +520,10 @@ class GraphedDCGANTrainer:
         opt.step(1.0 / (t.world * t.loss_scale))
 
     def train_iteration(self, iteration, next_batch):
-        """[G step if it > 0] + CRITIC_ITERS x (batch, D step)  (TF/CT_gan_cifar.py:190-204)."""
+        """[G step if it > 0] + disc_iters x (batch, D step)  (TF/CT_gan_cifar.py:190-204; disc_iters = CRITIC_ITERS, or 1 for the
+        'dcgan' / 'lsgan' objectives)."""
         self.t.iteration = iteration
-        n = self.t.mod.cfg.CRITIC_ITERS
+        n = self.t.disc_iters
         if self.it_graph is not None and iteration > 0:
             t = self.t
             for i in range(n):
@@ -533,6 +534,7 @@ class GraphedDCGANTrainer:
             t.g_opt.t += 1
             t.d_opt.t += n
             lib.bump_epoch()
+            t.clip_stats()
             self.g_out = self.it_out['g']
             return self.it_out['d'][-1]
         if iteration > 0:

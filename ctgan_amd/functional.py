@@ -1871,3 +1871,23 @@ def softmax_cross_entropy(logits, labels):
 
 def mean_diff(x, na, nb, sa, sb):
     return MeanDiffFn.apply(x, int(na), int(nb), float(sa), float(sb))
+
+
+class GanLossFn(Function):
+    """Cost of the 'dcgan' (sigmoid cross-entropy) / 'lsgan' (least-squares) objectives over critic outputs (kernels.gan_loss_fwd)."""
+
+    @staticmethod
+    def forward(ctx, d, B, kind):
+        ctx.save_for_backward(d)
+        ctx.cfg = (B, kind)
+        return K.gan_loss_fwd(d, B, kind)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (d,) = ctx.saved_tensors
+        return K.gan_loss_bwd(d, gout, *ctx.cfg).view(d.shape), None, None
+
+
+def gan_loss(d, B, loss, net):
+    """loss 'bce' | 'ls'; net 'd': d = [D(real) ; D(fake)] (2B rows) -> the critic cost; net 'g': d = D(fake) (B rows) -> the generator cost."""
+    return GanLossFn.apply(d, int(B), K.GAN_LOSS_KINDS[(loss, net)])

@@ -4,10 +4,21 @@
 differentiates the normalisation twice - Adam(1e-4, beta1 = 0, beta2 = 0.9) without decay (:561-565)."""
 from . import functional as F
 from . import kernels as K
+from .dcgan_step import CT_MODE, GanMode, validate_mode
 from .tflib.ops import batchnorm as _bn
 from .tflib.ops import conv2d as _conv2d
 from .tflib.ops import layernorm as _ln
 from .tflib.ops import linear as _linear
+
+
+# MODE -> objective, optimizer literals, clip, critic steps per iteration (:490-579, :634-646).  Every mode but 'wgan-ct' normalises the
+# critic with BatchNorm (Normalize).  'wgan-gp' is named in the script's comment (:30) but its branches raise (:540, :579).
+MODES = {
+    'wgan-ct': CT_MODE,
+    'wgan': GanMode('wgan', 'rmsprop', lr=5e-5, clip=0.01),                               # :492-494, :548-558
+    'dcgan': GanMode('bce', 'adam', lr=2e-4, betas=(0.5, 0.999), critic_iters=1),        # :521-533, :566-570
+    'lsgan': GanMode('ls', 'rmsprop', lr=1e-4, critic_iters=1),                          # :535-537, :572-576
+}
 
 
 class Config:
@@ -28,6 +39,7 @@ class Config:
             if not hasattr(Config, k):
                 raise AttributeError('unknown hyper-parameter %s' % k)
             setattr(self, k, v)
+        validate_mode(__name__, MODES, self.MODE)
 
 
 cfg = Config()
@@ -78,7 +90,7 @@ def UpsampleConv(name, input_dim, output_dim, filter_size, inputs, he_init=True,
 
 
 def ResidualBlock(name, input_dim, output_dim, filter_size, inputs, resample=None, he_init=True, groups=1):
-    """:127-162 (Conv1 has no bias, :157)"""
+    """:127-162 (Conv1 has no bias, :157).  `groups`: statistic groups of the BatchNorms (generator; the critic outside MODE 'wgan-ct')."""
     if resample not in (None, 'down', 'up'):
         raise Exception('invalid resample value')
     if output_dim == input_dim and resample is None:
@@ -124,17 +136,18 @@ def critic_is_per_sample():
     return cfg.MODE == 'wgan-ct'
 
 
-def DiscriminatorTrunk(inputs):
-    """Input conv + Res1 + Res2: everything before the first dropout (:358-363); deterministic and per-sample, shared by the two
-    dropout passes over the real batch of a critic step (dcgan_step.DCGANTrainer.d_losses)."""
+def DiscriminatorTrunk(inputs, groups=1):
+    """Input conv + Res1 + Res2: everything before the first dropout (:358-363); deterministic and per-sample (MODE 'wgan-ct'), shared by
+    the two dropout passes over the real batch of a critic step (dcgan_step.DCGANTrainer.d_losses).  `groups`: the critic calls batched in
+    `inputs`, each with its own statistics (BatchNorm critic of the other modes)."""
     dim = cfg.DIM
     out = inputs.reshape(-1, 3, 64, 64)
     out = _conv2d.Conv2D('Discriminator.Input', 3, dim, 3, out, he_init=False)
-    out = ResidualBlock('Discriminator.Res1', dim, 2 * dim, 3, out, resample='down')
-    return ResidualBlock('Discriminator.Res2', 2 * dim, 4 * dim, 3, out, resample='down')
+    out = ResidualBlock('Discriminator.Res1', dim, 2 * dim, 3, out, resample='down', groups=groups)
+    return ResidualBlock('Discriminator.Res2', 2 * dim, 4 * dim, 3, out, resample='down', groups=groups)
 
 
-def DiscriminatorTail(h, kp1=0.8, kp2=0.5, kp3=0.5, u=None, rng=None):
+def DiscriminatorTail(h, kp1=0.8, kp2=0.5, kp3=0.5, u=None, rng=None, groups=1):
     """dropout -> Res3 -> dropout -> Res4 -> dropout -> Linear (:364-373)."""
     dim = cfg.DIM
 
@@ -143,18 +156,18 @@ def DiscriminatorTail(h, kp1=0.8, kp2=0.5, kp3=0.5, u=None, rng=None):
             return x
         return F.dropout(x, kp, u[i]) if u is not None else F.dropout(x, kp, rng=rng)
     out = drop(0, h, kp1)
-    out = ResidualBlock('Discriminator.Res3', 4 * dim, 8 * dim, 3, out, resample='down')
+    out = ResidualBlock('Discriminator.Res3', 4 * dim, 8 * dim, 3, out, resample='down', groups=groups)
     out = drop(1, out, kp2)
-    out = ResidualBlock('Discriminator.Res4', 8 * dim, 8 * dim, 3, out, resample='down')
+    out = ResidualBlock('Discriminator.Res4', 8 * dim, 8 * dim, 3, out, resample='down', groups=groups)
     out = drop(2, out, kp3)
     output2 = F.to_nchw(out).reshape(-1, 4 * 4 * 8 * dim)
     out = _linear.Linear('Discriminator.Output', 4 * 4 * 8 * dim, 1, output2)
     return out.reshape(-1), output2
 
 
-def Discriminator(inputs, kp1=0.8, kp2=0.5, kp3=0.5, u=None, rng=None):
+def Discriminator(inputs, kp1=0.8, kp2=0.5, kp3=0.5, u=None, rng=None, groups=1):
     """GoodDiscriminator :357-373 -> (D [n], D_ [n, 4*4*8*DIM])."""
-    return DiscriminatorTail(DiscriminatorTrunk(inputs), kp1, kp2, kp3, u=u, rng=rng)
+    return DiscriminatorTail(DiscriminatorTrunk(inputs, groups), kp1, kp2, kp3, u=u, rng=rng, groups=groups)
 
 
 def build_params(device=None):

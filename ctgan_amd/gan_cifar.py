@@ -2,10 +2,15 @@
 Same `Generator(n_samples, noise=None)` / `Discriminator(inputs)` surface (MODE 'wgan-CT')."""
 from . import functional as F
 from . import kernels as K
+from .dcgan_step import CT_MODE, validate_mode
 from .tflib.ops import batchnorm as _bn
 from .tflib.ops import conv2d as _conv2d
 from .tflib.ops import deconv2d as _deconv2d
 from .tflib.ops import linear as _linear
+
+
+# TF/CT_gan_cifar.py codes only the CT branch (:123-156): any other MODE raises
+MODES = {'wgan-CT': CT_MODE}
 
 
 class Config:
@@ -26,6 +31,7 @@ class Config:
             if not hasattr(Config, k):
                 raise AttributeError('unknown hyper-parameter %s' % k)
             setattr(self, k, v)
+        validate_mode(__name__, MODES, self.MODE)
 
 
 cfg = Config()

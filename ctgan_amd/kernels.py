@@ -1673,6 +1673,29 @@ def mean_diff_bwd(gout, na, nb, sa, sb):
     return gx
 
 
+# loss heads of the 'dcgan' / 'lsgan' objectives (csrc/loss.hip; kinds as in ctgan_hip.h)
+GAN_LOSS_KINDS = {('bce', 'd'): 0, ('bce', 'g'): 1, ('ls', 'd'): 2, ('ls', 'g'): 3}
+
+
+def gan_loss_fwd(d, B, kind):
+    """Cost of `kind` (0..3, GAN_LOSS_KINDS) over d = [D(real) ; D(fake)] (critic kinds, 2B rows) or D(fake) (generator kinds, B rows)."""
+    _need_dev(d)
+    d = d.contiguous()
+    assert d.dtype == torch.float32 and d.numel() == (2 * B if kind in (0, 2) else B)
+    out = torch.empty((), dtype=torch.float32, device=d.device)
+    check(lib.ctgan_gan_loss_fwd(_ptr(d), B, kind, _ptr(out), _stream()), 'gan_loss_fwd')
+    return out
+
+
+def gan_loss_bwd(d, gout, B, kind):
+    _need_dev(d, gout)
+    d = d.contiguous()
+    assert d.numel() == (2 * B if kind in (0, 2) else B)
+    gd = torch.empty(d.numel(), dtype=torch.float32, device=d.device)
+    check(lib.ctgan_gan_loss_bwd(_ptr(d), _ptr(gout.contiguous()), B, kind, _ptr(gd), _stream()), 'gan_loss_bwd')
+    return gd
+
+
 # ------------------------------------------------------------------------------- optimizer / rng
 def adam_step(theta, g, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0):
     """In-place TF-Adam on flat fp32 buffers; `state` = device float[4] {lr, beta1^t, beta2^t, -}."""
@@ -1705,6 +1728,29 @@ def adam_step_packed(srcs, dst_offs, counts, flat, theta, m, v, state, beta1, be
     C = (ctypes.c_int64 * n)(*counts)
     check(lib.ctgan_adam_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps, grad_scale,
                                      _stream()), 'adam_step_packed')
+
+
+def rmsprop_step(theta, g, ms, state, rho, eps, clip=0.0, grad_scale=1.0):
+    """In-place TF-RMSProp (+ clip to [-clip, clip] when clip > 0) on flat fp32 buffers; `state` = device float[4] {lr, -, -, skipped}."""
+    _need_dev(theta, g, ms, state)
+    for t in (theta, g, ms):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == theta.numel()
+    check(lib.ctgan_rmsprop_step(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, _stream()),
+          'rmsprop_step')
+
+
+def rmsprop_step_packed(srcs, dst_offs, counts, flat, theta, ms, state, rho, eps, clip=0.0, grad_scale=1.0):
+    """pack(srcs -> flat) + rmsprop_step in one launch (len(srcs) <= ADAM_PACKED_MAX)."""
+    _need_dev(flat, theta, ms, state, *[t for t in srcs if t is not None])
+    n = len(srcs)
+    assert n <= ADAM_PACKED_MAX
+    for t, c in zip(srcs, counts):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c)
+    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
+    O = (ctypes.c_int64 * n)(*dst_offs)
+    C = (ctypes.c_int64 * n)(*counts)
+    check(lib.ctgan_rmsprop_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale, _stream()),
+          'rmsprop_step_packed')
 
 
 def pack(srcs, dst_offs, counts, flat):

@@ -1,8 +1,10 @@
-"""TF-form Adam over one flat fp32 buffer per network (csrc/optim_rng.hip: adam_kernel).
+"""TF-form Adam and RMSProp over one flat fp32 buffer per network (csrc/optim_rng.hip: adam_kernel, rmsprop_kernel).
 
-Mirrors `tf.train.AdamOptimizer(learning_rate=LR*decay, beta1, beta2)` + compute_gradients /
-apply_gradients (TF/CT_gan_cifar_resnet.py:333-338; TF/CT_gan_cifar.py:153-154).  The flat
-parameter / gradient buffers double as the all-reduce buckets of the batch-sharded step (ddp.py).
+FlatAdam mirrors `tf.train.AdamOptimizer(learning_rate=LR*decay, beta1, beta2)` + compute_gradients /
+apply_gradients (TF/CT_gan_cifar_resnet.py:333-338; TF/CT_gan_cifar.py:153-154); FlatRMSProp
+`tf.train.RMSPropOptimizer(learning_rate)` of the 'wgan' / 'lsgan' objectives (TF/CT_gan_mnist.py:125-131,
+TF/CT_gan_64x64.py:548-576), with the 'wgan' weight clip fused into its update.  The flat parameter /
+gradient buffers double as the all-reduce buckets of the batch-sharded step (ddp.py).
 """
 import torch
 
@@ -11,6 +13,8 @@ from . import tflib as lib
 
 
 class FlatAdam:
+    kind = 'adam'
+
     def __init__(self, named_params, beta1, beta2, eps=1e-8, state=None):
         """named_params: [(name, Parameter)] - the trainable variable list, in registry order.  state: optional float[4] device
         slice to keep {lr, beta1^t, beta2^t, -} in (two optimizers sharing one allocation take a common learning rate in one fill)."""
@@ -26,8 +30,7 @@ class FlatAdam:
         total = sum(self.sizes)
         self.theta = torch.empty(total, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._alloc_slots(total, dev)
         # re-home every parameter inside the flat buffer (same values, same shapes)
         off = 0
         with torch.no_grad():
@@ -48,6 +51,10 @@ class FlatAdam:
         self.t = 0
         self._keepalive = []
         self.offsets = [sum(self.sizes[:i]) for i in range(len(self.sizes))]
+
+    def _alloc_slots(self, total, dev):
+        self.m = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(total, dtype=torch.float32, device=dev)
 
     def set_lr(self, lr):
         """Write the scalar learning rate into the device-resident state (outside any captured graph).  The value rides in
@@ -111,6 +118,10 @@ class FlatAdam:
         self._keepalive = srcs
         self._end(rng)
 
+    def slots(self):
+        """The device tensors a step writes besides the weights: what a graph capture's warm-up steps must leave as they found them."""
+        return [self.m, self.v, self.state]
+
     def load_named_slots(self, m_by_name, v_by_name, t):
         """Overwrite the Adam slots from per-parameter tensors (teacher-forced parity tests, resume)."""
         off = 0
@@ -123,9 +134,70 @@ class FlatAdam:
         self.state[2] = self.beta2 ** (self.t + 1)
 
     def state_dict(self):
-        return {'m': self.m.cpu().clone(), 'v': self.v.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t}
+        return {'kind': self.kind, 'm': self.m.cpu().clone(), 'v': self.v.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t}
+
+    def _check_kind(self, sd):
+        kind = sd.get('kind', 'adam')          # (checkpoints written before the tag are Adam's)
+        if kind != self.kind:
+            raise ValueError('optimizer state of a %s optimizer cannot be loaded into a %s optimizer (another MODE?)' % (kind, self.kind))
 
     def load_state_dict(self, sd):
+        self._check_kind(sd)
         self.m.copy_(sd['m']); self.v.copy_(sd['v']); self.state.copy_(sd['state']); self.t = int(sd['t'])
         self.state[3:4].zero_()            # skipped() counts THIS session's skips: a resumed run does not inherit the saved run's
+        self._lr_last = None
+
+
+class FlatRMSProp(FlatAdam):
+    """tf.train.RMSPropOptimizer(learning_rate) with TF 1.x's defaults - decay rho = 0.9, momentum 0, epsilon 1e-10, not centered - over
+    the flat buffer (kernels.rmsprop_step):  ms <- ms + (g^2 - ms)(1 - rho);  theta <- theta - lr g / sqrt(ms + eps).  With momentum 0
+    TF's `mom` slot only ever holds the step just applied, so it is not kept.  TF creates the `rms` slot at ONES, not zeros (its
+    slot initialiser; not visible in the reference tree): the first step is ~ lr g, not lr sign(g) sqrt(10).
+
+    `clip` > 0: theta <- clip_by_value(theta, -clip, clip) fused into every update - the 'wgan' objective's clip op run after every critic
+    update (TF/CT_gan_mnist.py:134-143, :248-249).  The same interface as FlatAdam; state = device float[4] {lr, 1, 1, skipped}."""
+
+    kind = 'rmsprop'
+
+    def __init__(self, named_params, rho=0.9, eps=1e-10, clip=None, state=None):
+        # (FlatAdam's flat buffers, gather and end-of-step launch; its beta powers stay 1, so step_advance only moves the Philox counter)
+        super().__init__(named_params, 1.0, 1.0, eps, state)
+        self.rho, self.clip = float(rho), float(clip or 0.0)
+
+    def _alloc_slots(self, total, dev):
+        self.ms = torch.ones(total, dtype=torch.float32, device=dev)
+
+    def slots(self):
+        """The device tensors a step writes besides the weights - and the weights too when the update clips them (a step at learning
+        rate 0, as in a graph capture's warm-up, still clips)."""
+        return [self.ms, self.state] + ([self.theta] if self.clip > 0 else [])
+
+    def step(self, grad_scale=1.0, rng=None):
+        K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale)
+        self._end(rng)
+
+    def update(self, grads, grad_scale=1.0, rng=None):
+        if self.grad.device.type != 'cuda' or len(grads) > K.ADAM_PACKED_MAX:
+            self.gather_grads(grads)
+            return self.step(grad_scale, rng)
+        srcs = [g.contiguous() if g is not None else None for g in grads]
+        K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
+                              grad_scale)
+        self._keepalive = srcs
+        self._end(rng)
+
+    def load_named_slots(self, ms_by_name, t):
+        off = 0
+        for name, n in zip(self.names, self.sizes):
+            self.ms[off:off + n].copy_(ms_by_name[name].reshape(-1).to(self.ms.device, torch.float32))
+            off += n
+        self.t = int(t)
+
+    def state_dict(self):
+        return {'kind': self.kind, 'ms': self.ms.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t}
+
+    def load_state_dict(self, sd):
+        self._check_kind(sd)
+        self.ms.copy_(sd['ms']); self.state.copy_(sd['state']); self.t = int(sd['t'])
+        self.state[3:4].zero_()
         self._lr_last = None

@@ -452,6 +452,16 @@ int ctgan_mean_diff_fwd(const float* x, int32_t na, int32_t nb, float sa, float 
                         ctgan_stream_t stream);
 int ctgan_mean_diff_bwd(const float* gout, int32_t na, int32_t nb, float sa, float sb, float* gx,
                         ctgan_stream_t stream);
+/* Loss heads of the scripts' other MODE branches over critic outputs (TF/CT_gan_mnist.py:165-195, TF/CT_gan_64x64.py:521-537).
+ * kind CTGAN_LOSS_BCE_D / CTGAN_LOSS_LS_D: d [2B] with rows [0,B) = D(real), [B,2B) = D(fake);
+ *   BCE_D = (mean_i bce(d_fake_i, 0) + mean_i bce(d_real_i, 1)) / 2,  bce(x, z) = max(x,0) - x z + log1p(exp(-|x|))
+ *   LS_D  = (mean_i (d_real_i - 1)^2 + mean_i d_fake_i^2) / 2
+ * kind CTGAN_LOSS_BCE_G / CTGAN_LOSS_LS_G: d [B] = D(fake);  BCE_G = mean_i bce(d_i, 1),  LS_G = mean_i (d_i - 1)^2.
+ * fwd: out[0] = the cost (one workgroup, fixed-order reduction).  bwd: gd = gout[0] * d cost / d d (for BCE (sigmoid(x) - z) / n,
+ * finite for any finite logit).                                                                                                   */
+enum { CTGAN_LOSS_BCE_D = 0, CTGAN_LOSS_BCE_G = 1, CTGAN_LOSS_LS_D = 2, CTGAN_LOSS_LS_G = 3 };
+int ctgan_gan_loss_fwd(const float* d, int32_t B, int32_t kind, float* out, ctgan_stream_t stream);
+int ctgan_gan_loss_bwd(const float* d, const float* gout, int32_t B, int32_t kind, float* gd, ctgan_stream_t stream);
 
 /* All loss heads of one critic step over the batched dropout passes (TF/CT_gan_cifar_resnet.py:244-248,288-291):
  * d [3B], f [3B,nf], a [3B,ncls] (a may be NULL) with rows [0,B) = real pass 1, [B,2B) = fake pass 1, [2B,3B) = real
@@ -544,6 +554,17 @@ int ctgan_accuracy2(const float* logits, const int32_t* labels, int32_t B, int32
 int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state,
                     float beta1, float beta2, float eps, float grad_scale, ctgan_stream_t stream);
 int ctgan_adam_advance(float* state, float beta1, float beta2, ctgan_stream_t stream);
+/* tf.train.RMSPropOptimizer (decay rho, momentum 0, not centered) on a flat buffer, with an optional fused weight clip
+ * (TF/CT_gan_mnist.py:134-143, TF/CT_gan_64x64.py:548-558):  ms += (g^2 - ms) (1 - rho);  theta = clip(theta - lr g / sqrt(ms + eps))
+ * with g = grad * grad_scale, lr = state[0] (graph-replay safe), clip(x) = min(max(x, -clip), clip) when clip > 0 (no clip otherwise).
+ * TF creates the ms slot at ONES: the caller initialises it so.  A non-finite scaled gradient leaves the element's ms unchanged and its
+ * weight only clipped, and adds one to state[3], as ctgan_adam_step.  The packed form = ctgan_pack + the update in one launch
+ * (n_tensors <= 64, 16-byte aligned flat buffers), bit-identical to ctgan_pack + ctgan_rmsprop_step.                              */
+int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                       float grad_scale, ctgan_stream_t stream);
+int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
+                              ctgan_stream_t stream);
 /* End of a step in one launch: ctgan_adam_advance(state) and, with rng_ctr != NULL, ctgan_rng_advance(rng_ctr, rng_by).            */
 int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, ctgan_stream_t stream);
 /* ctgan_pack + ctgan_adam_step in one launch (n_tensors <= 64, 16-byte aligned flat buffers; CTGAN_E_UNSUPPORTED otherwise):
