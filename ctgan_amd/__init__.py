@@ -8,6 +8,7 @@ Layout
   tflib/                 the reference's operator library API: lib.param registry + tflib.ops.*
   gan_cifar_resnet.py    ResNet CT-WGAN (Generator/Discriminator, D/G step, train loop)
   gan_cifar.py, gan_mnist.py   the DCGAN scripts
+  evaluate.py            held-out critic cost, score samples (the evaluation half of the scripts' loops)
   ddp.py                 batch-sharded step over RCCL (flat gradient buckets)
 """
 __version__ = '0.1.0'

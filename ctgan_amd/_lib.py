@@ -173,6 +173,7 @@ SIGNATURES = {
     'ctgan_spatial_sum': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p]),
     'ctgan_spatial_bcast': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p]),
     'ctgan_real_prep': (c_int, [_p, _p, _p, c_int64, c_float, _p]),
+    'ctgan_pixels_u8': (c_int, [_p, _p, c_int64, c_int32, c_int32, c_float, _p]),
     'ctgan_interpolate': (c_int, [_p, _p, _p, _p, c_int32, c_int32, _p]),
     'ctgan_bn_stats': (c_int, [_p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_size_t, _p]),
     'ctgan_bn_apply': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, _p]),

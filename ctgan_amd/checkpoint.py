@@ -4,10 +4,13 @@ The reference has no resume for its CIFAR/MNIST scripts (`np.save("param.pyn", .
 TF/CT_gan_cifar.py:216-222; a `tf.train.Saver` in the LSUN script).  Here the registry's names make it
 trivial: one file holds every parameter by its reference name and layout, both optimizers' slots (Adam m, v and
 beta-power state, or RMSProp ms - tagged with the optimizer kind, so a resume under another MODE fails clearly -, step count), the Philox step counter and the loop iteration - enough for a bit-exact
-continuation (tests/test_gpu_checkpoint.py)."""
+continuation (tests/test_gpu_checkpoint.py).  The `rng` entry also holds the step counter of the evaluation stream (evaluate.eval_stream:
+`eval_ctr`), so that a resumed run logs the dev costs of the uninterrupted one; a file written before that entry existed loads with the
+counter at 0."""
 import torch
 
 from . import tflib as lib
+from .evaluate import eval_stream
 
 
 def save(path, trainer, iteration, extra=None):
@@ -17,7 +20,8 @@ def save(path, trainer, iteration, extra=None):
         'params': lib.state_dict(),
         'd_opt': trainer.d_opt.state_dict(),
         'g_opt': trainer.g_opt.state_dict(),
-        'rng': {'seed': trainer.rng.seed, 'rank': trainer.rng.rank, 'ctr': int(trainer.rng.ctr.item())},
+        'rng': {'seed': trainer.rng.seed, 'rank': trainer.rng.rank, 'ctr': int(trainer.rng.ctr.item()),
+                'eval_ctr': int(eval_stream(trainer).ctr.item())},
         'extra': extra or {},
     }, path)
 
@@ -33,4 +37,5 @@ def load(path, trainer):
     trainer.g_opt.load_state_dict(ck['g_opt'])
     trainer.rng.seed = ck['rng']['seed']
     trainer.rng.ctr.fill_(ck['rng']['ctr'])
+    eval_stream(trainer).ctr.fill_(ck['rng'].get('eval_ctr', 0))
     return ck['iteration']

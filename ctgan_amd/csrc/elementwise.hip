@@ -153,6 +153,46 @@ __global__ void real_prep_kernel(const int32_t* __restrict__ xi, const float* __
     }
 }
 
+// score-sample pixels: trunc((x + 1) * scale) clamped to [0, 255], NCHW fp32 -> NHWC uint8.  Add then multiply, each rounded on its
+// own (no fused multiply-add), so that finite inputs are bit-equal to ((x + 1.) * scale).to(int32).clamp(0, 255); a non-finite
+// input gives 0.
+__device__ __forceinline__ unsigned pixel_u8(float x, float scale) {
+    const float v = __fmul_rn(__fadd_rn(x, 1.0f), scale);
+    if (!isfinite(x) || !(v > 0.f)) return 0u;
+    return v >= 256.f ? 255u : (unsigned)(int)v;
+}
+
+// three channel planes, hw % 4 == 0: a lane reads 16 B from each plane (four pixels) and writes their 12 output bytes as three words
+__global__ void pixels_u8_c3_kernel(const float* __restrict__ x, uint32_t* __restrict__ out, long long quads, int hw4, float scale) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += stride) {
+        const long long img = q / hw4;
+        const int p4 = (int)(q - img * hw4);
+        const float4* px = reinterpret_cast<const float4*>(x) + img * 3 * hw4 + p4;
+        const float4 r = px[0], g = px[hw4], b = px[2 * hw4];
+        const unsigned r0 = pixel_u8(r.x, scale), g0 = pixel_u8(g.x, scale), b0 = pixel_u8(b.x, scale);
+        const unsigned r1 = pixel_u8(r.y, scale), g1 = pixel_u8(g.y, scale), b1 = pixel_u8(b.y, scale);
+        const unsigned r2 = pixel_u8(r.z, scale), g2 = pixel_u8(g.z, scale), b2 = pixel_u8(b.z, scale);
+        const unsigned r3 = pixel_u8(r.w, scale), g3 = pixel_u8(g.w, scale), b3 = pixel_u8(b.w, scale);
+        uint32_t* o = out + q * 3;
+        o[0] = r0 | (g0 << 8) | (b0 << 16) | (r1 << 24);
+        o[1] = g1 | (b1 << 8) | (r2 << 16) | (g2 << 24);
+        o[2] = b2 | (r3 << 8) | (g3 << 16) | (b3 << 24);
+    }
+}
+
+// any channel count / extent: one output byte per lane
+__global__ void pixels_u8_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, long long total, int c, int hw, float scale) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int cc = (int)(i % c);
+        const long long pix = i / c;
+        const long long img = pix / hw;
+        const int p = (int)(pix - img * hw);
+        out[i] = (uint8_t)pixel_u8(x[(img * c + cc) * hw + p], scale);
+    }
+}
+
 __global__ void interpolate_kernel(const float* __restrict__ real, const float* __restrict__ fake,
                                    const float* __restrict__ alpha, float* __restrict__ out, int b, int d) {
     const long long total = (long long)b * d;
@@ -590,6 +630,21 @@ int ctgan_real_prep(const int32_t* x_int, const float* noise, float* y, int64_t 
     hipLaunchKernelGGL(real_prep_kernel, dim3(ctgan_blocks(n, TPB)), dim3(TPB), 0, static_cast<hipStream_t>(s), x_int,
                        noise, y, (long long)n, denom);
     return ctgan_check_launch("real_prep");
+}
+
+int ctgan_pixels_u8(const float* x, uint8_t* out, int64_t n, int32_t c, int32_t hw, float scale, ctgan_stream_t s) {
+    if (n < 0 || c <= 0 || hw <= 0 || !(scale > 0.f) || (n > 0 && (!x || !out))) return ctgan_fail(CTGAN_E_BADARG, "pixels_u8: bad argument");
+    if (n == 0) return CTGAN_OK;
+    const long long total = (long long)n * c * hw;
+    if (c == 3 && hw % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) & 15) | (reinterpret_cast<uintptr_t>(out) & 3)) == 0) {
+        const long long quads = total / 12;
+        hipLaunchKernelGGL(pixels_u8_c3_kernel, dim3(ctgan_blocks(quads, TPB)), dim3(TPB), 0, static_cast<hipStream_t>(s), x,
+                           reinterpret_cast<uint32_t*>(out), quads, hw / 4, scale);
+    } else {
+        hipLaunchKernelGGL(pixels_u8_kernel, dim3(ctgan_blocks(total, TPB)), dim3(TPB), 0, static_cast<hipStream_t>(s), x, out, total, c,
+                           hw, scale);
+    }
+    return ctgan_check_launch("pixels_u8");
 }
 
 int ctgan_interpolate(const float* real, const float* fake, const float* alpha, float* out, int32_t b, int32_t d,

@@ -266,3 +266,84 @@ class DCGANTrainer:
         for i in range(n):
             out = self.d_step(next_batch(), fake=None if fakes is None else fakes[i])
         return out
+
+
+def build_params(module, device=None):
+    """Instantiate every parameter of `module` once (the reference does this while building its graph)."""
+    if hasattr(module, 'build_params'):
+        module.build_params(device)
+        return
+    if device is not None:
+        lib.set_device(device)
+    dev = lib._dev()
+    with torch.no_grad():
+        x = module.Generator(2, noise=torch.zeros(2, 128, device=dev))
+        module.Discriminator(x, u=[torch.full((2,) + tuple(s), 0.9, device=dev) for s in module.feat_shapes()])
+
+
+def sample_grid(module, noise):
+    """generate_image of the scripts (TF/CT_gan_cifar.py:162-165, TF/CT_gan_mnist.py:211-216, TF/CT_gan_64x64.py:588-592): the fixed-noise
+    samples as the array tflib.save_images takes - [n, 28, 28] floats in [0, 1] (MNIST) or [n, 3, H, W] integer pixels."""
+    import math
+    F.prepare_filters()
+    with torch.no_grad():
+        s = module.Generator(noise.shape[0], noise=noise)
+    n, d = s.shape
+    if d % 3:
+        side = int(round(math.sqrt(d)))
+        return s.reshape(n, side, side).cpu().numpy()
+    from .evaluate import SCORE_SCALE
+    side = int(round(math.sqrt(d // 3)))
+    scale = SCORE_SCALE.get(module.__name__.rsplit('.', 1)[-1], 255.99 / 2)
+    return ((s + 1.) * scale).to(torch.int32).reshape(n, 3, side, side).cpu().numpy()
+
+
+def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
+          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print):
+    """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
+    `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
+    (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
+    (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series; the fixed-noise sample
+    grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
+    `dev_every`-th.  Returns the trainer."""
+    import os
+    import time
+
+    from . import checkpoint, evaluate
+    from .engine import GraphedDCGANTrainer
+    from .tflib import save_images
+    from .train_log import Series
+    cfg = module.cfg
+    iters = cfg.ITERS if iters is None else iters
+    build_params(module)
+    trainer = DCGANTrainer(module, seed=seed)
+    start = checkpoint.load(resume, trainer) if resume else 0
+    first = next_batch()
+    eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)
+    pending = [first]
+    feed = lambda: pending.pop() if pending else next_batch()          # noqa: E731
+    ev = evaluate.Evaluator(trainer)
+    n_fixed = {'gan_cifar': 128, 'gan_mnist': 128, 'gan_lsun128': 64}.get(ev.name, cfg.BATCH_SIZE)
+    fixed_noise = torch.randn(n_fixed, 128, generator=torch.Generator().manual_seed(seed)).to(trainer.dev)
+    series = Series(os.path.join(out_dir, 'log.jsonl'), echo=log)
+    series.iteration = start
+    for iteration in range(start, iters):
+        t0 = time.time()
+        out = eng.train_iteration(iteration, feed)
+        series.add('train disc cost', out['cost'].item())
+        series.add('time', time.time() - t0)
+        if classifier is not None and score_every and iteration % score_every == score_every - 1:
+            evaluate.record_score(ev, series, classifier)
+        if dev_batches is not None and dev_every and iteration % dev_every == dev_every - 1:
+            dev = ev.dev_cost(dev_batches())
+            if 'slope_real' in dev:
+                series.add('slope_real', dev['slope_real'])
+            series.add('dev disc cost', dev['dev_cost'])
+        if sample_every and iteration % sample_every == sample_every - 1:
+            save_images.save_images(sample_grid(module, fixed_noise), os.path.join(out_dir, 'samples_%d.png' % iteration))
+        if checkpoint_every and iteration % checkpoint_every == checkpoint_every - 1:
+            checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, iteration + 1)
+        if iteration < 5 or (dev_every and iteration % dev_every == dev_every - 1):
+            series.flush()
+        series.tick()
+    return trainer

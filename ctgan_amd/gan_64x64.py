@@ -179,3 +179,13 @@ def build_params(device=None):
     with torch.no_grad():
         x = Generator(2, noise=torch.zeros(2, 128, device=dev))
         Discriminator(x, 1.0, 1.0, 1.0)
+
+
+def train(next_batch, dev_batches=None, dev_every=200, **kw):
+    """The training loop of TF/CT_gan_64x64.py:628-669 (dev cost and sample grid every 200 iterations, :660-665) on the caller's feeds:
+    `next_batch()` -> int32 [BATCH_SIZE, 3*64*64] on the device, `dev_batches()` -> an iterable over the held-out batches."""
+    import sys
+
+    from . import dcgan_step
+    kw.setdefault('sample_every', dev_every)
+    return dcgan_step.train(sys.modules[__name__], next_batch, dev_batches, dev_every=dev_every, **kw)

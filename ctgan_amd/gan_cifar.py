@@ -100,3 +100,18 @@ def Discriminator(inputs, u=None, rng=None):
     output2 = F.to_nchw(output).reshape(-1, 4 * 4 * 4 * D)
     output = _linear.Linear('Discriminator.Output', 4 * 4 * 4 * D, 1, output2)
     return output.reshape(-1), output2
+
+
+def train(data_dir, n_examples=1000, **kw):
+    """The training loop of TF/CT_gan_cifar.py:178-236 on tflib.cifar10.load(BATCH_SIZE, data_dir, n_examples) (:27,179: the 1000-example
+    regime): dcgan_step.train with the held-out test batch as dev set (dev cost and slope_real every 100 iterations)."""
+    import sys
+
+    from . import dcgan_step
+    from . import tflib as lib
+    from .tflib import cifar10
+    dcgan_step.build_params(sys.modules[__name__])
+    dev = lib._dev()
+    train_gen, dev_gen = cifar10.load(cfg.BATCH_SIZE, data_dir, n_examples)
+    feed = cifar10.prefetch_to_device(cifar10.inf_train_gen(train_gen), dev, depth=2 * cfg.CRITIC_ITERS)
+    return dcgan_step.train(sys.modules[__name__], lambda: next(feed)[0], lambda: cifar10.prefetch_to_device(dev_gen(), dev), **kw)

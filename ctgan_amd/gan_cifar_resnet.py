@@ -735,15 +735,16 @@ class Trainer:
 
 
 def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100,
-          checkpoint_every=1000, resume=None, log=print):
-    """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434) minus the Inception
-    score (needs the 2015 Inception graph + network): CIFAR-10 generator factories, `time` /
+          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None):
+    """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434): CIFAR-10 generator factories, `time` /
     `cost` / `wgan` / `acgan` / `acc_real` / `acc_fake` series (train_log.Series), fixed-noise sample grids every
-    `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only)."""
+    `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
+    every `dev_every` iterations (:421-427, evaluate.Evaluator.dev_cost) and - with a `classifier` (no Inception graph ships: the 2015
+    graph needs a network, SURVEY.md 2 #9) - `inception_50k` / `inception_50k_std` every `score_every` iterations (:414-418)."""
     import os
     import time
 
-    from . import checkpoint
+    from . import checkpoint, evaluate
     from .engine import GraphedTrainer
     from .tflib import cifar10, save_images
     from .train_log import Series
@@ -752,6 +753,7 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     trainer = Trainer(seed=seed)
     start = checkpoint.load(resume, trainer) if resume else 0
     eng = GraphedTrainer(trainer, use_graphs=use_graphs)
+    ev = evaluate.Evaluator(trainer)
     train_gen, dev_gen = cifar10.load(cfg.BATCH_SIZE, data_dir, n_examples)
     feed = cifar10.prefetch_to_device(cifar10.inf_train_gen(train_gen), trainer.dev)
     fixed_noise = trainer.rng.normal(100, 128)
@@ -765,6 +767,10 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
             for k in ('wgan', 'acgan', 'acc_real', 'acc_fake'):
                 series.add(k, out[k].item())
         series.add('time', time.time() - t0)
+        if classifier is not None and score_every and iteration % score_every == score_every - 1:
+            evaluate.record_score(ev, series, classifier)
+        if dev_every and iteration % dev_every == dev_every - 1:
+            series.add('dev_cost', ev.dev_cost(cifar10.prefetch_to_device(dev_gen(), trainer.dev))['dev_cost'])
         if iteration % sample_every == sample_every - 1:
             _, px = trainer.generate_samples(fixed_noise, fixed_labels)
             save_images.save_images(px.reshape(100, 3, 32, 32).cpu().numpy(), os.path.join(out_dir, 'samples_%d.png' % iteration))

@@ -174,3 +174,12 @@ def build_params(device=None):
     with torch.no_grad():
         x = Generator(2, noise=torch.zeros(2, 128, device=dev))
         Discriminator(x, 1.0, 1.0, 1.0)
+
+
+def train(next_batch, **kw):
+    """The training loop on the caller's feed (`next_batch()` -> int32 [BATCH_SIZE, 3*128*128] on the device).  No dev pass: the script
+    has none (LS/wgan_LSUN_Bedrooms128.py:366-398)."""
+    import sys
+
+    from . import dcgan_step
+    return dcgan_step.train(sys.modules[__name__], next_batch, None, **kw)

@@ -115,3 +115,25 @@ def Discriminator(inputs, u=None, rng=None, groups=1):
     output2 = F.to_nchw(output).reshape(-1, 4 * 4 * 4 * D)
     output = _linear.Linear('Discriminator.Output', 4 * 4 * 4 * D, 1, output2)
     return output.reshape(-1), output2
+
+
+def train(data_path, n_examples=1000, **kw):
+    """The training loop of TF/CT_gan_mnist.py:218-270 on tflib.mnist.load(BATCH_SIZE, BATCH_SIZE, n_examples) (:28,219) read from
+    `data_path` (mnist.pkl.gz): dcgan_step.train with the dev split as dev set (every 100 iterations)."""
+    import sys
+
+    import torch
+
+    from . import dcgan_step
+    from . import tflib as lib
+    from .tflib import mnist
+    dcgan_step.build_params(sys.modules[__name__])
+    dev = lib._dev()
+    train_gen, dev_gen, _ = mnist.load(cfg.BATCH_SIZE, cfg.BATCH_SIZE, n_examples, filepath=data_path)
+
+    def inf_train_gen():
+        while True:
+            for images, _targets in train_gen():
+                yield torch.from_numpy(images).to(dev)
+    feed = inf_train_gen()
+    return dcgan_step.train(sys.modules[__name__], lambda: next(feed), dev_gen, **kw)

@@ -1459,6 +1459,17 @@ def real_prep(x_int, noise, denom):
     return y
 
 
+def pixels_u8(x, channels, scale):
+    """Score-sample pixels: x fp32 [n, C*H*W] (NCHW, as the generators return it) -> uint8 [n, H*W, C], trunc((x + 1) * scale)
+    clamped to [0, 255] (bit-equal to ((x + 1.) * scale).to(int32).clamp(0, 255) for finite x; a non-finite x gives 0)."""
+    _need_dev(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2 and x.shape[1] % channels == 0
+    n, hw = x.shape[0], x.shape[1] // channels
+    out = torch.empty((n, hw, channels), dtype=torch.uint8, device=x.device)
+    check(lib.ctgan_pixels_u8(_ptr(x), _ptr(out), n, channels, hw, float(scale), _stream()), 'pixels_u8')
+    return out
+
+
 def interpolate(real, fake, alpha):
     _need_dev(real, fake, alpha)
     B, D = real.shape

@@ -400,6 +400,10 @@ int ctgan_spatial_bcast(const float* g, float* y, int32_t n, int32_t hw, int32_t
  * TF/CT_gan_cifar.py:103 with denom 255)                                                       */
 int ctgan_real_prep(const int32_t* x_int, const float* noise, float* y, int64_t n, float denom,
                     ctgan_stream_t stream);
+/* score-sample pixels (TF/CT_gan_cifar_resnet.py:355-357): out[n,hw,c] (uint8, NHWC) = trunc((x[n,c,hw] + 1) * scale)
+ * clamped to [0, 255], x fp32 NCHW; add, then multiply, each rounded in fp32.  A non-finite x gives 0.  scale > 0.  */
+int ctgan_pixels_u8(const float* x, uint8_t* out, int64_t n, int32_t c, int32_t hw, float scale,
+                    ctgan_stream_t stream);
 /* out[b,:] = real[b,:] + alpha[b]*(fake[b,:]-real[b,:])   (:282-283)                           */
 int ctgan_interpolate(const float* real, const float* fake, const float* alpha, float* out,
                       int32_t b, int32_t d, ctgan_stream_t stream);
