@@ -37,6 +37,20 @@ def test_product_header_carries_no_debug_switches():
     assert all(n.startswith('ctgan_debug_') for n in _header_functions('ctgan_hip_debug.h'))
 
 
+def test_removed_step_variants_stay_removed():
+    """The three structural variants of the critic step that were measured level or slower are deleted, not switched off: no
+    side-stream flush / filter rebuild in functional, no 8x8 chain in kernels or the C ABI, no `join` state in the weight-gradient queue."""
+    import ctgan_amd.functional as F
+    import ctgan_amd.kernels as K
+    from ctgan_amd import _lib
+    for name in ('flush_async', 'prepare_filters_async', 'prepare_dgrad_filters', 'WGRAD_OVERLAP', 'PREP_ASYNC'):
+        assert not hasattr(F, name), name
+    for name in ('CHAIN8X8', 'conv_chain8x8'):
+        assert not hasattr(K, name), name
+    assert 'join' not in F._DEFER
+    assert not [n for n in list(_lib.SIGNATURES) + list(_lib.DEBUG_SIGNATURES) if 'chain8x8' in n]
+
+
 def test_conv_desc_layout_matches_header():
     """struct ctgan_conv_desc: 14 int32 then 2 x int64[4] (8-byte aligned) = 120 bytes."""
     from ctgan_amd._lib import ConvDesc
