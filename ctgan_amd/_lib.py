@@ -212,6 +212,19 @@ SIGNATURES = {
     'ctgan_rows_cat_bwd2': (c_int, [_p, c_int64, c_int64, c_int64, c_int64, _p, _p]),
     'ctgan_gp_bwd_mean': (c_int, [_p, _p, _p, c_int32, c_int32, c_float, _p, _p, _p, _p]),
     'ctgan_rows_gather_dropout': (c_int, [_p, POINTER(RowSegment), c_int32, c_int64, c_uint64, _p, _p, _p]),
+    # semi-supervised classifier (csrc/ssl.hip)
+    'ctgan_wn_fwd': (c_int, [_p, _p, c_int32, c_int32, c_float, _p, _p, _p]),
+    'ctgan_wn_bwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_dense_noise_fwd': (c_int, [_p, _p, c_int64, c_int32, c_int32, c_float, c_uint64, c_uint64, _p, c_int64, _p, _p, _p]),
+    'ctgan_dense_noise_bwd': (c_int, [_p, _p, _p, _p, c_int64, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_wn_init': (c_int, [_p, c_int64, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_ssl_head_fwd': (c_int, [_p, _p, c_int32, c_int32, c_float, c_float, _p, _p, _p]),
+    'ctgan_ssl_head_bwd': (c_int, [_p, _p, _p, c_int32, c_int32, c_float, c_float, _p, _p]),
+    'ctgan_featmatch_fwd': (c_int, [_p, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_featmatch_bwd': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
+    'ctgan_bn2d_fwd': (c_int, [_p, _p, c_int32, c_int32, c_float, c_int32, _p, _p, _p, _p]),
+    'ctgan_bn2d_bwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_adam_theano_step': (c_int, [_p, _p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
 }
 
 

@@ -548,3 +548,98 @@ class GraphedDCGANTrainer:
         for i in range(n):
             out = self.d_step(next_batch(), fake=None if fakes is None else fakes[i])
         return out
+
+
+class GraphedSSLTrainer:
+    """hipGraph replay of the two steps of ct_mnist.SSLTrainer.  Each step - forward, backward, gradient packing, Theano-form Adam with
+    the parameter average, the advance of Adam's beta powers and of the Philox step counter - is captured once on a single stream (no
+    parallel branches) and replayed; the batches are staged into fixed buffers, the learning rate, beta powers and stream counter live
+    in device memory.  The capture's warm-up runs at learning rate 0 and every slot it touches (Adam m, v, state, the averages, the
+    stream counter) is restored afterwards, so a graphed run equals an eager one bit for bit."""
+
+    def __init__(self, trainer, use_graphs=True, warmup=2):
+        from . import ct_mnist as M
+        self.t = trainer
+        B, dev = M.cfg.BATCH_SIZE, trainer.dev
+        self.x_lab = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.x_unl = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.x_unl2 = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.d_graph = self.g_graph = None
+        self.d_out = self.g_out = None
+        self.graph_error = None
+        if use_graphs:
+            try:
+                self._capture(warmup)
+            except Exception as e:
+                self.graph_error = '%s: %s' % (type(e).__name__, e)
+                self.d_graph = self.g_graph = None
+                torch.cuda.synchronize()
+
+    def _capture(self, warmup):
+        t = self.t
+        K.reset_capture_workspaces()
+        opts = (t.d_opt, t.g_opt)
+        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
+        snap = [b.clone() for b in bufs]
+        steps = [o.t for o in opts]
+        for o in opts:
+            o.set_lr(0.0)
+        try:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(warmup):
+                    t.d_body(self.x_lab, self.labels, self.x_unl)
+                    t.g_body(self.x_unl2)
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            quiesce_collectives()
+            self.d_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.d_graph, **_capture_kw()):
+                self.d_out = t.d_body(self.x_lab, self.labels, self.x_unl)
+            self.g_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_graph, **_capture_kw()):
+                self.g_out = t.g_body(self.x_unl2)
+        finally:
+            torch.cuda.synchronize()
+            for b, sn in zip(bufs, snap):
+                b.copy_(sn)
+            for o, n in zip(opts, steps):
+                o.t, o._lr_last = n, None
+            torch.cuda.synchronize()
+
+    @property
+    def graphed(self):
+        return self.d_graph is not None
+
+    def d_step(self, x_lab, labels, x_unl):
+        t = self.t
+        if not self.graphed:
+            dev = t.dev
+            return t.d_step(x_lab.to(dev), labels.to(dev), x_unl.to(dev))
+        self.x_lab.copy_(x_lab, non_blocking=True)
+        self.labels.copy_(labels, non_blocking=True)
+        self.x_unl.copy_(x_unl, non_blocking=True)
+        t.d_opt.set_lr(t.lr())
+        self.d_graph.replay()
+        t.d_opt.t += 1
+        lib.bump_epoch('Classifier')
+        return self.d_out
+
+    def g_step(self, x_unl2):
+        t = self.t
+        if not self.graphed:
+            return t.g_step(x_unl2.to(t.dev))
+        self.x_unl2.copy_(x_unl2, non_blocking=True)
+        t.g_opt.set_lr(t.lr())
+        self.g_graph.replay()
+        t.g_opt.t += 1
+        lib.bump_epoch('Generator')
+        return self.g_out
+
+    def train_iteration(self, x_lab, labels, x_unl, x_unl2):
+        out = dict(self.d_step(x_lab, labels, x_unl))
+        out.update(self.g_step(x_unl2))
+        self.t.iteration += 1
+        return out

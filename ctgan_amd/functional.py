@@ -1806,3 +1806,127 @@ class GanLossFn(Function):
 def gan_loss(d, B, loss, net):
     """loss 'bce' | 'ls'; net 'd': d = [D(real) ; D(fake)] (2B rows) -> the critic cost; net 'g': d = D(fake) (B rows) -> the generator cost."""
     return GanLossFn.apply(d, int(B), K.GAN_LOSS_KINDS[(loss, net)])
+
+
+# ---------------------------------------------------------------- semi-supervised classifier (csrc/ssl.hip; ct_mnist.py)
+class WeightNormFn(Function):
+    """W = theta * s / sqrt(eps + column sums of theta^2)   (TH/nn.py:407; eps 1e-6: l2normalize :263)"""
+
+    @staticmethod
+    def forward(ctx, theta, s, eps):
+        w, rnorm = K.wn_fwd(theta, s, eps)
+        ctx.save_for_backward(theta, s, rnorm)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        theta, s, rnorm = ctx.saved_tensors
+        gtheta, gs = K.wn_bwd(gw, theta, s, rnorm, want_gs=ctx.needs_input_grad[1])
+        return gtheta, gs, None
+
+
+def weight_norm(theta, s, eps=0.0):
+    return WeightNormFn.apply(theta, s, float(eps))
+
+
+class DenseNoiseFn(Function):
+    """(h, a): a = [relu](y + b), h = a + sigma N(0,1) - the epilogue of a dense layer and the GaussianNoiseLayer behind it in one
+    launch (TH/nn.py:428-430, :232-244).  spec = (seed, stream id, step counter) of the noise site, row_offset the first row's place in
+    that stream.  The noise is additive, so the backward is the ReLU mask (recomputed from the sign of y + b) on the sum of the two
+    cotangents, with the bias gradient reduced in the same launch; no noise tensor exists."""
+
+    @staticmethod
+    def forward(ctx, y, b, relu, sigma, spec, row_offset, want_a):
+        seed, sid, ctr = spec if spec is not None else (0, 0, None)
+        h, a = K.dense_noise_fwd(y, b, relu, sigma, seed, sid, ctr, row_offset, want_a)
+        ctx.relu, ctx.has_b = bool(relu), b is not None
+        ctx.save_for_backward(y, b)
+        ctx.set_materialize_grads(False)
+        if not want_a:
+            return h, None
+        return h, a
+
+    @staticmethod
+    def backward(ctx, gh, ga):
+        y, b = ctx.saved_tensors
+        if gh is None and ga is None:
+            return None, None, None, None, None, None, None
+        if not ctx.relu and not ctx.has_b:
+            g = gh if ga is None else (ga if gh is None else add(gh, ga))      # x + sigma N: the identity
+            return g, None, None, None, None, None, None
+        gz, gb = K.dense_noise_bwd(gh, ga, y, b, ctx.relu, want_gb=ctx.has_b and ctx.needs_input_grad[1])
+        return gz, gb, None, None, None, None, None
+
+
+def dense_noise(y, b, relu, sigma, spec=None, row_offset=0, want_a=False):
+    """-> h, or (h, a) with want_a."""
+    h, a = DenseNoiseFn.apply(y, b, bool(relu), float(sigma), spec, int(row_offset), bool(want_a))
+    return (h, a) if want_a else h
+
+
+def noise_spec(rng):
+    """(seed, stream id, step counter) of the next random call site of `rng` (rng.DeviceRNG)."""
+    return (rng.seed, rng._sid(), rng.ctr)
+
+
+class SSLHeadFn(Function):
+    """(out4 = {loss_lab, loss_unl, CT, train_err}, ct_i) of the classifier step over logits [4B, nc] = [lab ; unl ; unl2 ; fake]
+    (TH/CT_MNIST.py:70-90).  Differentiable in out4[0] and out4[1]."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, B, lam2, M):
+        out4, ct_i = K.ssl_head_fwd(logits, labels, B, lam2, M)
+        ctx.save_for_backward(logits, labels)
+        ctx.cfg = (B, lam2, M)
+        ctx.mark_non_differentiable(ct_i)
+        return out4, ct_i
+
+    @staticmethod
+    def backward(ctx, gout, _):
+        logits, labels = ctx.saved_tensors
+        return K.ssl_head_bwd(logits, labels, gout, *ctx.cfg), None, None, None, None
+
+
+def ssl_head(logits, labels, B, lam2, M):
+    return SSLHeadFn.apply(logits, labels, int(B), float(lam2), float(M))
+
+
+class FeatMatchFn(Function):
+    """mean_j (mean_i f_ij - mean_i f_(B+i)j)^2 over f [2B, C]   (TH/CT_MNIST.py:92-94)"""
+
+    @staticmethod
+    def forward(ctx, f, B):
+        loss, diff = K.featmatch_fwd(f, B)
+        ctx.save_for_backward(diff)
+        ctx.B = B
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (diff,) = ctx.saved_tensors
+        return K.featmatch_bwd(diff, gout, ctx.B), None
+
+
+def feature_matching(f, B):
+    return FeatMatchFn.apply(f, int(B))
+
+
+class BatchNorm2dFn(Function):
+    """[softplus](batch-normalised x + offset) on [B, C]: batch statistics, no gain (TH/nn.py:194-216 under batch_norm(g=None))."""
+
+    @staticmethod
+    def forward(ctx, x, offset, eps, act):
+        y, xhat, rstd = K.bn2d_fwd(x, offset, eps, act)
+        ctx.save_for_backward(xhat, offset, rstd)
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xhat, offset, rstd = ctx.saved_tensors
+        gx, go = K.bn2d_bwd(gy, xhat, offset, rstd, ctx.act, want_goffset=offset is not None and ctx.needs_input_grad[1])
+        return gx, go, None, None
+
+
+def batch_norm_2d(x, offset, eps=1e-6, softplus=False):
+    return BatchNorm2dFn.apply(x, offset, float(eps), bool(softplus))

@@ -1991,3 +1991,144 @@ def rows_cat_bwd(g, n_src, n_extra, n_pass=0):
 def rng_advance(ctr, by=1):
     assert ctr.is_cuda and ctr.dtype == torch.int64
     check(lib.ctgan_rng_advance(_ptr(ctr), by, _stream()), 'rng_advance')
+
+
+# ---------------------------------------------------------------- semi-supervised classifier (csrc/ssl.hip; ct_mnist.py)
+def _rows2d(t):
+    assert t.dim() == 2 and t.is_contiguous() and t.dtype == torch.float32, 'dense [rows, cols] fp32 tensor expected'
+    return t.shape
+
+
+def wn_fwd(theta, s, eps=0.0):
+    """-> (W, rnorm): W = theta * s / sqrt(eps + column sum of theta^2) over the [in, out] theta."""
+    _need_dev(theta, s)
+    n_in, n_out = _rows2d(theta)
+    assert s.is_contiguous() and s.numel() == n_out
+    w = torch.empty_like(theta)
+    rnorm = torch.empty(n_out, dtype=torch.float32, device=theta.device)
+    check(lib.ctgan_wn_fwd(_ptr(theta), _ptr(s), n_in, n_out, eps, _ptr(w), _ptr(rnorm), _stream()), 'wn_fwd')
+    return w, rnorm
+
+
+def wn_bwd(gw, theta, s, rnorm, want_gs=True):
+    """-> (gtheta, gs or None) of wn_fwd."""
+    _need_dev(gw, theta, s, rnorm)
+    n_in, n_out = _rows2d(theta)
+    gw = gw.contiguous()
+    assert tuple(gw.shape) == (n_in, n_out) and rnorm.numel() == n_out and s.numel() == n_out
+    gtheta = torch.empty_like(theta)
+    gs = torch.empty(n_out, dtype=torch.float32, device=theta.device) if want_gs else None
+    check(lib.ctgan_wn_bwd(_ptr(gw), _ptr(theta), _ptr(s), _ptr(rnorm), n_in, n_out, _ptr(gtheta), _ptr(gs), _stream()), 'wn_bwd')
+    return gtheta, gs
+
+
+def dense_noise_fwd(y, bias, relu, sigma, seed, stream_id, ctr, row_offset=0, want_a=False, out=None):
+    """-> (h, a or None): a = [relu](y + bias), h = a + sigma N(0,1) drawn in the kernel at stream position row_offset * cols."""
+    _need_dev(y, bias, out)
+    rows, cols = _rows2d(y)
+    assert bias is None or (bias.is_contiguous() and bias.numel() == cols)
+    assert ctr is None or (ctr.is_cuda and ctr.dtype == torch.int64)
+    h = torch.empty_like(y) if out is None else out
+    assert h.is_contiguous() and tuple(h.shape) == (rows, cols)
+    a = torch.empty_like(y) if want_a else None
+    check(lib.ctgan_dense_noise_fwd(_ptr(y), _ptr(bias), rows, cols, int(bool(relu)), float(sigma), int(seed), int(stream_id), _ptr(ctr),
+                                    int(row_offset), _ptr(h), _ptr(a), _stream()), 'dense_noise_fwd')
+    return h, a
+
+
+def dense_noise_bwd(gh, ga, y, bias, relu, want_gb=True):
+    """-> (gz, gb or None): the cotangent of y given those of h and a (either may be None), and its column sums."""
+    _need_dev(gh, ga, y, bias)
+    rows, cols = _rows2d(y)
+    gh = gh.contiguous() if gh is not None else None
+    ga = ga.contiguous() if ga is not None else None
+    assert gh is not None or ga is not None
+    for t in (gh, ga):
+        assert t is None or tuple(t.shape) == (rows, cols)
+    gz = torch.empty_like(y)
+    gb = torch.empty(cols, dtype=torch.float32, device=y.device) if want_gb else None
+    check(lib.ctgan_dense_noise_bwd(_ptr(gh), _ptr(ga), _ptr(y), _ptr(bias), rows, cols, int(bool(relu)), _ptr(gz), _ptr(gb), _stream()),
+          'dense_noise_bwd')
+    return gz, gb
+
+
+def wn_init(y, s, b, relu):
+    """Data-dependent init of one layer, in place: y normalised per column (then relu), s /= stdv, b = -mean / stdv."""
+    _need_dev(y, s, b)
+    rows, cols = _rows2d(y)
+    assert s.is_contiguous() and b.is_contiguous() and s.numel() == cols and b.numel() == cols
+    check(lib.ctgan_wn_init(_ptr(y), rows, cols, int(bool(relu)), _ptr(s), _ptr(b), _stream()), 'wn_init')
+    return y
+
+
+def ssl_head_fwd(logits, labels, B, lam2, M):
+    """logits [4B, nc] = [lab ; unl ; unl2 ; fake] -> (out4 = {loss_lab, loss_unl, CT, train_err}, ct_i [B])."""
+    _need_dev(logits, labels)
+    rows, nc = _rows2d(logits)
+    assert rows == 4 * B and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B
+    out4 = torch.empty(4, dtype=torch.float32, device=logits.device)
+    ct_i = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(lib.ctgan_ssl_head_fwd(_ptr(logits), _ptr(labels), B, nc, lam2, M, _ptr(out4), _ptr(ct_i), _stream()), 'ssl_head_fwd')
+    return out4, ct_i
+
+
+def ssl_head_bwd(logits, labels, gout, B, lam2, M):
+    """-> glogits [4B, nc] of gout[0] * loss_lab + gout[1] * loss_unl."""
+    _need_dev(logits, labels, gout)
+    rows, nc = _rows2d(logits)
+    gout = gout.contiguous()
+    assert rows == 4 * B and labels.dtype == torch.int32 and labels.numel() == B and gout.numel() >= 2
+    gl = torch.empty_like(logits)
+    check(lib.ctgan_ssl_head_bwd(_ptr(logits), _ptr(labels), _ptr(gout), B, nc, lam2, M, _ptr(gl), _stream()), 'ssl_head_bwd')
+    return gl
+
+
+def featmatch_fwd(f, B):
+    """f [2B, C] = [f(G(z)) ; f(x)] -> (loss, diff [C])."""
+    _need_dev(f)
+    rows, C = _rows2d(f)
+    assert rows == 2 * B
+    loss = torch.empty((), dtype=torch.float32, device=f.device)
+    diff = torch.empty(C, dtype=torch.float32, device=f.device)
+    check(lib.ctgan_featmatch_fwd(_ptr(f), B, C, _ptr(loss), _ptr(diff), _stream()), 'featmatch_fwd')
+    return loss, diff
+
+
+def featmatch_bwd(diff, gout, B):
+    _need_dev(diff, gout)
+    C = diff.numel()
+    gf = torch.empty(2 * B, C, dtype=torch.float32, device=diff.device)
+    check(lib.ctgan_featmatch_bwd(_ptr(diff), _ptr(gout.contiguous()), B, C, _ptr(gf), _stream()), 'featmatch_bwd')
+    return gf
+
+
+def bn2d_fwd(x, offset, eps, act):
+    """Batch norm of [B, C] with batch statistics, offset, no gain; act: softplus.  -> (y, xhat, rstd)."""
+    _need_dev(x, offset)
+    B, C = _rows2d(x)
+    assert offset is None or (offset.is_contiguous() and offset.numel() == C)
+    y, xhat = torch.empty_like(x), torch.empty_like(x)
+    rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    check(lib.ctgan_bn2d_fwd(_ptr(x), _ptr(offset), B, C, eps, int(bool(act)), _ptr(y), _ptr(xhat), _ptr(rstd), _stream()), 'bn2d_fwd')
+    return y, xhat, rstd
+
+
+def bn2d_bwd(gy, xhat, offset, rstd, act, want_goffset=True):
+    _need_dev(gy, xhat, offset, rstd)
+    B, C = _rows2d(xhat)
+    gy = gy.contiguous()
+    assert tuple(gy.shape) == (B, C) and rstd.numel() == C
+    gx = torch.empty_like(xhat)
+    go = torch.empty(C, dtype=torch.float32, device=xhat.device) if want_goffset else None
+    check(lib.ctgan_bn2d_bwd(_ptr(gy), _ptr(xhat), _ptr(offset), _ptr(rstd), B, C, int(bool(act)), _ptr(gx), _ptr(go), _stream()), 'bn2d_bwd')
+    return gx, go
+
+
+def adam_theano_step(theta, g, m, v, avg, state, beta1, beta2, eps=1e-8, avg_rate=0.0):
+    """In-place Theano-form Adam (epsilon inside the root) on flat fp32 buffers, the parameter average `avg` (None: not kept) moved
+    in the same launch; `state` = device float[4] {lr, beta1^t, beta2^t, skipped}."""
+    _need_dev(theta, g, m, v, avg, state)
+    for t in (theta, g, m, v, avg):
+        assert t is None or (t.is_contiguous() and t.numel() == theta.numel())
+    check(lib.ctgan_adam_theano_step(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), _ptr(avg), theta.numel(), _ptr(state), beta1, beta2, eps,
+                                     avg_rate, _stream()), 'adam_theano_step')

@@ -201,3 +201,46 @@ class FlatRMSProp(FlatAdam):
         self.ms.copy_(sd['ms']); self.state.copy_(sd['state']); self.t = int(sd['t'])
         self.state[3:4].zero_()
         self._lr_last = None
+
+
+class FlatAdamTheano(FlatAdam):
+    """The Adam of the reference's Theano classifier (TH/nn.py:30-47 `adam_updates`; TH/ = CT-GANs/Theano_classifier) over the flat
+    buffer (kernels.adam_theano_step):  m <- b1 m + (1-b1) g;  v <- b2 v + (1-b2) g^2;
+    theta <- theta - lr (m / (1-b1^t)) / sqrt(v / (1-b2^t) + 1e-8)  - the epsilon INSIDE the root, t from 1, one counter per optimizer.
+    `avg_rate` > 0 keeps the parameter average of TH/CT_MNIST.py:104-105, avg <- avg + avg_rate (theta - avg) from zeros, moved in the
+    update's own launch (`avg`, laid out like the flat parameter buffer; `avg_views()` gives it per parameter).  The same interface
+    and device state {lr, b1^t, b2^t, skipped} as FlatAdam."""
+
+    kind = 'adam_theano'
+
+    def __init__(self, named_params, beta1, beta2, eps=1e-8, avg_rate=0.0, state=None):
+        super().__init__(named_params, beta1, beta2, eps, state)
+        self.avg_rate = float(avg_rate)
+        self.avg = torch.zeros_like(self.theta) if self.avg_rate > 0 else None
+
+    def avg_views(self):
+        """[(name, view of the average shaped like the parameter)]"""
+        return [(n, self.avg[o:o + s].view(p.shape)) for n, p, o, s in zip(self.names, self.params, self.offsets, self.sizes)]
+
+    def step(self, grad_scale=1.0, rng=None):
+        assert grad_scale == 1.0
+        K.adam_theano_step(self.theta, self.grad, self.m, self.v, self.avg, self.state, self.beta1, self.beta2, self.eps, self.avg_rate)
+        self._end(rng)
+
+    def update(self, grads, grad_scale=1.0, rng=None):
+        self.gather_grads(grads)
+        self.step(grad_scale, rng)
+
+    def slots(self):
+        return [self.m, self.v, self.state] + ([self.avg] if self.avg is not None else [])
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.avg is not None:
+            sd['avg'] = self.avg.cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        if self.avg is not None:
+            self.avg.copy_(sd['avg'])

@@ -647,6 +647,54 @@ int ctgan_rows_gather_dropout(const float* src, const ctgan_row_segment* segs, i
                               const uint64_t* ctr, float* dst, ctgan_stream_t stream);
 
 
+/* ---- semi-supervised CT classifier (csrc/ssl.hip; TH/ = CT-GANs/Theano_classifier) ---------------------------------------
+ * Weight-normalised dense layer (TH/nn.py:398-430; the generator's l2normalize, :250-264): w[i,j] = theta[i,j] * s[j] * rnorm[j],
+ * rnorm[j] = 1 / sqrt(eps + sum_i theta[i,j]^2) over the [in, out] row-major theta.  eps = 0 for the classifier's DenseLayer,
+ * 1e-6 for l2normalize.  The backward takes the saved rnorm:  d_j = sum_i gw_ij theta_ij,  gs_j = d_j rnorm_j (gs may be NULL),
+ * gtheta_ij = s_j rnorm_j (gw_ij - theta_ij d_j rnorm_j^2).                                                                 */
+int ctgan_wn_fwd(const float* theta, const float* s, int32_t in, int32_t out, float eps, float* w, float* rnorm,
+                 ctgan_stream_t stream);
+int ctgan_wn_bwd(const float* gw, const float* theta, const float* s, const float* rnorm, int32_t in, int32_t out, float* gtheta,
+                 float* gs, ctgan_stream_t stream);
+/* Epilogue of a dense layer followed by a GaussianNoiseLayer (TH/nn.py:428-430, :232-244) in one launch after the GEMM:
+ * a = y + bias (bias may be NULL), relu != 0: a = max(a, 0); h = a + sigma * N(0,1).  Element (r, c) of the [rows, cols]
+ * tensor draws value (row_offset + r) * cols + c of the stream ctgan_rng_normal(., seed, stream_id, ctr) writes, so a pass that
+ * is a row block of a stacked batch draws what a launch of its own would.  sigma = 0: no draw (deterministic pass).  `a` (may be
+ * NULL) receives the pre-noise activation.  bias = NULL, relu = 0 is the input noise site x + sigma N.  No noise tensor is
+ * written.  The backward: gz = gh + ga (either may be NULL) kept where y + bias > 0 (relu != 0), gb_j = sum_i gz_ij (may be NULL). */
+int ctgan_dense_noise_fwd(const float* y, const float* bias, int64_t rows, int32_t cols, int32_t relu, float sigma, uint64_t seed,
+                          uint64_t stream_id, const uint64_t* ctr, int64_t row_offset, float* h, float* a, ctgan_stream_t stream);
+int ctgan_dense_noise_bwd(const float* gh, const float* ga, const float* y, const float* bias, int64_t rows, int32_t cols,
+                          int32_t relu, float* gz, float* gb, ctgan_stream_t stream);
+/* Data-dependent init of one weight-normalised layer (TH/nn.py:421-426), in place on the pre-activation y = x W [rows, cols]:
+ * y <- (y - mean_j) / stdv_j (then relu), stdv_j the root mean square of the centred column; s_j <- s_j / stdv_j,
+ * b_j <- -mean_j / stdv_j.                                                                                                   */
+int ctgan_wn_init(float* y, int64_t rows, int32_t cols, int32_t relu, float* s, float* b, ctgan_stream_t stream);
+/* Loss head of the classifier step (TH/CT_MNIST.py:70-90) over logits [4b, nc] = [labelled ; unlabelled ; unlabelled, second
+ * noisy pass ; generated]:  out4 = { loss_lab, loss_unl, CT, train_err },  ct_i [b] = mean_k (softmax(unl) - softmax(unl2))^2,
+ * CT = mean_i max(lam2 ct_i - m, 0), loss_unl = (CT - mean lse(unl) + mean softplus(lse(unl)) + mean softplus(lse(fake))) / 2.
+ * Max-subtracted log-sum-exp, softplus(t) = max(t,0) + log1p(exp(-|t|)).  The backward writes the [4b, nc] cotangent of
+ * gout[0] * loss_lab + gout[1] * loss_unl (gout: device float[>= 2]).                                                        */
+int ctgan_ssl_head_fwd(const float* logits, const int32_t* labels, int32_t b, int32_t nc, float lam2, float m, float* out4,
+                       float* ct_i, ctgan_stream_t stream);
+int ctgan_ssl_head_bwd(const float* logits, const int32_t* labels, const float* gout, int32_t b, int32_t nc, float lam2, float m,
+                       float* glogits, ctgan_stream_t stream);
+/* Feature matching (TH/CT_MNIST.py:92-94) over f [2b, c] = [f(G(z)) ; f(x)]: diff_j = mean_i f_ij - mean_i f_(b+i)j,
+ * loss = mean_j diff_j^2; the backward: gf = +-gout * 2 diff_j / (c b).                                                      */
+int ctgan_featmatch_fwd(const float* f, int32_t b, int32_t c, float* loss, float* diff, ctgan_stream_t stream);
+int ctgan_featmatch_bwd(const float* diff, const float* gout, int32_t b, int32_t c, float* gf, ctgan_stream_t stream);
+/* Batch norm of a [b, c] activation with batch statistics, an offset and no gain (TH/nn.py:194-216, batch_norm(g=None)):
+ * xhat = (x - mean_j) rstd_j, rstd_j = 1 / sqrt(eps + var_j); y = xhat + offset_j, act = 1: y = softplus(xhat + offset_j).     */
+int ctgan_bn2d_fwd(const float* x, const float* offset, int32_t b, int32_t c, float eps, int32_t act, float* y, float* xhat,
+                   float* rstd, ctgan_stream_t stream);
+int ctgan_bn2d_bwd(const float* gy, const float* xhat, const float* offset, const float* rstd, int32_t b, int32_t c, int32_t act,
+                   float* gx, float* goffset, ctgan_stream_t stream);
+/* Theano-form Adam (TH/nn.py:30-47) on flat buffers with the parameter average of TH/CT_MNIST.py:104-105 fused:
+ * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; theta -= lr (m / (1 - b1^t)) / sqrt(v / (1 - b2^t) + eps) - eps INSIDE the
+ * root -; avg += avg_rate (theta - avg) (avg may be NULL).  state = {lr, b1^t, b2^t, skipped} as ctgan_adam_step's.           */
+int ctgan_adam_theano_step(float* theta, const float* g, float* m, float* v, float* avg, int64_t n, float* state, float beta1,
+                           float beta2, float eps, float avg_rate, ctgan_stream_t stream);
+
 
 #ifdef __cplusplus
 }
