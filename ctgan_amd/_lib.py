@@ -157,6 +157,7 @@ SIGNATURES = {
     'ctgan_pixels_u8': (c_int, [_p, _p, c_int64, c_int32, c_int32, c_float, _p]),
     'ctgan_interpolate': (c_int, [_p, _p, _p, _p, c_int32, c_int32, _p]),
     'ctgan_bn_stats': (c_int, [_p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_size_t, _p]),
+    'ctgan_bn_stats_f64': (c_int, [_p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_size_t, _p]),
     'ctgan_bn_apply': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, _p]),
     'ctgan_bn_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32,
                              c_int32, _p, c_size_t, _p]),
@@ -225,6 +226,16 @@ SIGNATURES = {
     'ctgan_bn2d_fwd': (c_int, [_p, _p, c_int32, c_int32, c_float, c_int32, _p, _p, _p, _p]),
     'ctgan_bn2d_bwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, _p, _p, _p]),
     'ctgan_adam_theano_step': (c_int, [_p, _p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
+    # convolutional semi-supervised classifier (csrc/ssl_conv.hip)
+    'ctgan_wn_mid_fwd': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, _p]),
+    'ctgan_wn_mid_bwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_wn_init_map': (c_int, [_p, c_int64, c_int32, c_int32, c_float, c_float, _p, _p, _p]),
+    'ctgan_featcons_fwd': (c_int, [_p, _p, c_int32, c_int32, c_int32, _p, _p]),
+    'ctgan_featcons_bwd': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
+    'ctgan_featmatch_l1_fwd': (c_int, [_p, c_int32, c_int32, _p, _p, _p]),
+    'ctgan_featmatch_l1_bwd': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
+    'ctgan_aug_gather': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                 c_int32, _p, c_uint64, c_uint64, _p, _p, _p]),
 }
 
 

@@ -290,23 +290,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* __re
 }
 // Vector partial reductions (same layout of `part`): 16-B loads, each thread sums <= pos*c4n/256 positions of its 4 channels
 // in fp32 (a few dozen values), the row lanes are then combined in fp64.  blockDim = 256 = (c/4) channel lanes x row lanes.
+// Acc = double (ctgan_bn_stats_f64): the per-thread sums run in fp64 too - sum x^2 - mean^2 of a channel whose spread is far below its
+// mean (variance ~ eps = 1e-6 at mean 0.5) loses the variance to the fp32 rounding of a sum of eight 0.25s.
+template <typename Acc>
 __global__ __launch_bounds__(256) void bn_stats_partial_vec_kernel(const float* __restrict__ x, BnShape s, double* __restrict__ part) {
     __shared__ double red[2][256][4];
     const int c4n = s.c >> 2, rls = 256 / c4n;
     const int c4 = threadIdx.x % c4n, rl = threadIdx.x / c4n;
     const int sample = blockIdx.x / s.hc, chunk = blockIdx.x - sample * s.hc;
     const int p0 = chunk * s.pos, p1 = min(s.hw, p0 + s.pos);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    Acc a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     const float* base = x + ((long long)sample * s.hw) * s.c + c4 * 4;
 #pragma unroll 4
     for (int p = p0 + rl; p < p1; p += rls) {
         const float4 v = *reinterpret_cast<const float4*>(base + (long long)p * s.c);
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        b.x += v.x * v.x; b.y += v.y * v.y; b.z += v.z * v.z; b.w += v.w * v.w;
+        const Acc x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+        a0 += x0; a1 += x1; a2 += x2; a3 += x3;
+        b0 += x0 * x0; b1 += x1 * x1; b2 += x2 * x2; b3 += x3 * x3;
     }
     double* ra = red[0][threadIdx.x]; double* rb = red[1][threadIdx.x];
-    ra[0] = a.x; ra[1] = a.y; ra[2] = a.z; ra[3] = a.w;
-    rb[0] = b.x; rb[1] = b.y; rb[2] = b.z; rb[3] = b.w;
+    ra[0] = a0; ra[1] = a1; ra[2] = a2; ra[3] = a3;
+    rb[0] = b0; rb[1] = b1; rb[2] = b2; rb[3] = b3;
     __syncthreads();
     if (rl == 0) {
         double sa[4] = {0., 0., 0., 0.}, sb[4] = {0., 0., 0., 0.};
@@ -392,16 +396,18 @@ size_t ctgan_bn_workspace_bytes(int32_t n, int32_t hw, int32_t c, int32_t groups
     return part_bytes(s) + tot_bytes(s) + bins_bytes(s, n_labels) + (size_t)groups * 2 * c * sizeof(float);
 }
 
-int ctgan_bn_stats(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps, float* mean, float* rstd,
-                   void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+static int bn_stats_impl(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps, float* mean, float* rstd, void* ws,
+                         size_t ws_bytes, bool f64, ctgan_stream_t stream) {
     int rc = check_shape(n, hw, c, groups, "bn_stats");
     if (rc) return rc;
     if (!x || !mean || !rstd || !ws) return ctgan_fail(CTGAN_E_BADARG, "bn_stats: null");
     const BnShape s = mk(n, hw, c, groups);
     if (ws_bytes < part_bytes(s)) return ctgan_fail(CTGAN_E_BADARG, "bn_stats: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (bn_vec_ok(s, x, x, x))
-        hipLaunchKernelGGL(bn_stats_partial_vec_kernel, dim3(n * s.hc), dim3(256), 0, st, x, s, static_cast<double*>(ws));
+    if (bn_vec_ok(s, x, x, x) && f64)
+        hipLaunchKernelGGL(bn_stats_partial_vec_kernel<double>, dim3(n * s.hc), dim3(256), 0, st, x, s, static_cast<double*>(ws));
+    else if (bn_vec_ok(s, x, x, x))
+        hipLaunchKernelGGL(bn_stats_partial_vec_kernel<float>, dim3(n * s.hc), dim3(256), 0, st, x, s, static_cast<double*>(ws));
     else
         hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(n * s.hc, (c + CB - 1) / CB), dim3(CB * RL), 0, st, x, s,
                            static_cast<double*>(ws));
@@ -410,6 +416,16 @@ int ctgan_bn_stats(const float* x, int32_t n, int32_t hw, int32_t c, int32_t gro
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3((c + CB - 1) / CB, groups), dim3(CB * FL), 0, st,
                        static_cast<const double*>(ws), s, eps, mean, rstd);
     return ctgan_check_launch("bn_stats_final");
+}
+
+int ctgan_bn_stats(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps, float* mean, float* rstd,
+                   void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    return bn_stats_impl(x, n, hw, c, groups, eps, mean, rstd, ws, ws_bytes, false, stream);
+}
+
+int ctgan_bn_stats_f64(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps, float* mean, float* rstd,
+                       void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    return bn_stats_impl(x, n, hw, c, groups, eps, mean, rstd, ws, ws_bytes, true, stream);
 }
 
 int ctgan_bn_apply(const float* x, const float* mean, const float* rstd, const float* scale, const float* offset,

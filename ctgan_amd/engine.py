@@ -558,13 +558,8 @@ class GraphedSSLTrainer:
     stream counter) is restored afterwards, so a graphed run equals an eager one bit for bit."""
 
     def __init__(self, trainer, use_graphs=True, warmup=2):
-        from . import ct_mnist as M
         self.t = trainer
-        B, dev = M.cfg.BATCH_SIZE, trainer.dev
-        self.x_lab = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
-        self.x_unl = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
-        self.x_unl2 = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._alloc_staging()
         self.d_graph = self.g_graph = None
         self.d_out = self.g_out = None
         self.graph_error = None
@@ -575,6 +570,21 @@ class GraphedSSLTrainer:
                 self.graph_error = '%s: %s' % (type(e).__name__, e)
                 self.d_graph = self.g_graph = None
                 torch.cuda.synchronize()
+
+    def _alloc_staging(self):
+        """The fixed buffers the batches are staged into (what the captured steps read)."""
+        from . import ct_mnist as M
+        B, dev = M.cfg.BATCH_SIZE, self.t.dev
+        self.x_lab = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.x_unl = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.x_unl2 = torch.zeros(B, M.cfg.IN_DIM, dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _d_body(self):
+        return self.t.d_body(self.x_lab, self.labels, self.x_unl)
+
+    def _g_body(self):
+        return self.t.g_body(self.x_unl2)
 
     def _capture(self, warmup):
         t = self.t
@@ -590,17 +600,17 @@ class GraphedSSLTrainer:
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(warmup):
-                    t.d_body(self.x_lab, self.labels, self.x_unl)
-                    t.g_body(self.x_unl2)
+                    self._d_body()
+                    self._g_body()
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             quiesce_collectives()
             self.d_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.d_graph, **_capture_kw()):
-                self.d_out = t.d_body(self.x_lab, self.labels, self.x_unl)
+                self.d_out = self._d_body()
             self.g_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_graph, **_capture_kw()):
-                self.g_out = t.g_body(self.x_unl2)
+                self.g_out = self._g_body()
         finally:
             torch.cuda.synchronize()
             for b, sn in zip(bufs, snap):
@@ -643,3 +653,39 @@ class GraphedSSLTrainer:
         out.update(self.g_step(x_unl2))
         self.t.iteration += 1
         return out
+
+
+class GraphedCifarSSLTrainer(GraphedSSLTrainer):
+    """GraphedSSLTrainer for ct_cifar.CifarSSLTrainer: what is staged are the INDEX batches into the trainer's device-resident uint8
+    set, and the augmenting gathers (kernels.aug_gather, drawn at the step's own counter value) are the first launches of the two
+    captured graphs.  The steps take int32 index / label tensors (host or device)."""
+
+    def _alloc_staging(self):
+        from . import ct_cifar as M
+        assert self.t.data is not None, 'bind the uint8 training set first (CifarSSLTrainer.bind_data)'
+        B, dev = M.cfg.BATCH_SIZE, self.t.dev
+        self.x_lab = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.x_unl = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.x_unl2 = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _d_body(self):
+        return self.t.d_body_idx(self.x_lab, self.labels, self.x_unl)
+
+    def _g_body(self):
+        return self.t.g_body_idx(self.x_unl2)
+
+    def d_step(self, i_lab, labels, i_unl):
+        t = self.t
+        if not self.graphed:
+            dev = t.dev
+            t.d_opt.set_lr(t.lr())
+            return t.d_body_idx(i_lab.to(dev), labels.to(dev), i_unl.to(dev))
+        return super().d_step(i_lab, labels, i_unl)
+
+    def g_step(self, i_unl2):
+        t = self.t
+        if not self.graphed:
+            t.g_opt.set_lr(t.lr())
+            return t.g_body_idx(i_unl2.to(t.dev))
+        return super().g_step(i_unl2)

@@ -1261,27 +1261,28 @@ def to_nchw(x):
 
 
 class CropFn(Function):
-    """x[:, :, :h, :w] as a dense channels-last tensor (MNIST generator, TF/CT_gan_mnist.py:76)."""
+    """x[:, :, top:top+h, left:left+w] as a dense channels-last tensor (MNIST generator, TF/CT_gan_mnist.py:76: top = left = 0; the
+    pad-0 conv of ct_cifar.py as the centre of the SAME result)."""
 
     @staticmethod
-    def forward(ctx, x, h, w):
+    def forward(ctx, x, h, w, top, left):
         ctx.shape = x.shape
-        ctx.hw = (h, w)
-        v = x[:, :, :h, :w]
+        ctx.win = (h, w, top, left)
+        v = x[:, :, top:top + h, left:left + w]
         return K.copy4d(v, K.empty_cl(*v.shape, device=x.device))
 
     @staticmethod
     def backward(ctx, g):
-        h, w = ctx.hw
+        h, w, top, left = ctx.win
         N, C, H, W = ctx.shape
         full = K.empty_cl(N, C, H, W, device=g.device)
         full.zero_()
-        K.copy4d(g, full[:, :, :h, :w])
-        return full, None, None
+        K.copy4d(g, full[:, :, top:top + h, left:left + w])
+        return full, None, None, None, None
 
 
-def crop(x, h, w):
-    return CropFn.apply(x, h, w)
+def crop(x, h, w, top=0, left=0):
+    return CropFn.apply(x, h, w, int(top), int(left))
 
 
 class AddFn(Function):
@@ -1354,8 +1355,8 @@ class BatchNormFn(Function):
     """Training-mode BN (+ optional per-label scale/offset, + optional fused ReLU)."""
 
     @staticmethod
-    def forward(ctx, x, scale, offset, labels, groups, relu):
-        y, mean, rstd, x4 = K.bn_fwd(x, scale, offset, labels, groups, relu)
+    def forward(ctx, x, scale, offset, labels, groups, relu, eps=1e-5, f64_stats=False):
+        y, mean, rstd, x4 = (K.bn_fwd_f64 if f64_stats else K.bn_fwd)(x, scale, offset, labels, groups, relu, eps)
         ctx.groups, ctx.relu = groups, relu
         ctx.labels = labels
         ctx.in_shape = x.shape
@@ -1368,11 +1369,12 @@ class BatchNormFn(Function):
         gx, gs, go = K.bn_bwd(gy, x4, mean, rstd, scale, offset, ctx.labels, ctx.groups, ctx.relu)
         if len(ctx.in_shape) == 2:
             gx = gx.reshape(ctx.in_shape)
-        return gx, gs.view(scale.shape), go.view(offset.shape), None, None, None
+        return gx, gs.view(scale.shape), go.view(offset.shape), None, None, None, None, None
 
 
-def batch_norm(x, scale, offset, labels=None, groups=1, relu=False):
-    return BatchNormFn.apply(x, scale, offset, labels, groups, relu)
+def batch_norm(x, scale, offset, labels=None, groups=1, relu=False, eps=1e-5, f64_stats=False):
+    """f64_stats: the moments summed in fp64 throughout (kernels.bn_fwd_f64) - for an eps far below the default."""
+    return BatchNormFn.apply(x, scale, offset, labels, groups, relu, float(eps), bool(f64_stats))
 
 
 # --------------------------------------------------------------------------------- layer norm (config[4] critic)
@@ -1930,3 +1932,72 @@ class BatchNorm2dFn(Function):
 
 def batch_norm_2d(x, offset, eps=1e-6, softplus=False):
     return BatchNorm2dFn.apply(x, offset, float(eps), bool(softplus))
+
+
+# ---------------------------------------------------------------- convolutional semi-supervised classifier (csrc/ssl_conv.hip; ct_cifar.py)
+class WeightNormMidFn(Function):
+    """W = theta * s[out] / sqrt(eps + sums of theta^2 over (k, k, in)) of a [k, k, out, in] transposed-conv filter
+    (TH/nn.py:70-81: Deconv2DLayer's W [in, out, k, k] is normalised over axes (0, 2, 3))."""
+
+    @staticmethod
+    def forward(ctx, theta, s, eps):
+        w, rnorm = K.wn_mid_fwd(theta, s, eps)
+        ctx.save_for_backward(theta, s, rnorm)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        theta, s, rnorm = ctx.saved_tensors
+        gtheta, gs = K.wn_mid_bwd(gw, theta, s, rnorm, want_gs=ctx.needs_input_grad[1])
+        return gtheta, gs, None
+
+
+def weight_norm_mid(theta, s, eps=1e-6):
+    return WeightNormMidFn.apply(theta, s, float(eps))
+
+
+def weight_norm_filter(w_hwio, s, eps=1e-6):
+    """Weight norm of an HWIO conv filter per output channel: wn_fwd on the [k k in, out] view (TH/nn.py:75-81, axes (1, 2, 3) of W [out, in, k, k])."""
+    R, S, C, Kout = w_hwio.shape
+    return weight_norm(w_hwio.view(R * S * C, Kout), s, eps).view(R, S, C, Kout)
+
+
+class FeatConsFn(Function):
+    """out2 = {mean (f[B:2B] - f[2B:3B])^2, train_err2} over the features f [4B, F] (and the logits [4B, nc]) of the stacked classifier
+    pass (TH/CT_CIFAR.py:120, :128).  Differentiable in out2[0] with respect to f."""
+
+    @staticmethod
+    def forward(ctx, f, logits, B):
+        out2 = K.featcons_fwd(f, B, logits)
+        ctx.save_for_backward(f)
+        ctx.B = B
+        return out2
+
+    @staticmethod
+    def backward(ctx, gout):
+        (f,) = ctx.saved_tensors
+        return K.featcons_bwd(f, gout, ctx.B), None, None
+
+
+def feature_consistency(f, B, logits=None):
+    return FeatConsFn.apply(f, None if logits is None else logits.detach(), int(B))
+
+
+class FeatMatchL1Fn(Function):
+    """mean_j |mean_i f_ij - mean_i f_(B+i)j| over f [2B, C]   (TH/CT_CIFAR.py:152-156)"""
+
+    @staticmethod
+    def forward(ctx, f, B):
+        loss, diff = K.featmatch_l1_fwd(f, B)
+        ctx.save_for_backward(diff)
+        ctx.B = B
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (diff,) = ctx.saved_tensors
+        return K.featmatch_l1_bwd(diff, gout, ctx.B), None
+
+
+def feature_matching_l1(f, B):
+    return FeatMatchL1Fn.apply(f, int(B))

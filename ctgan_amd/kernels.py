@@ -1472,7 +1472,12 @@ def conv_fwd_bn_in(x, w, bias, g, mean, rstd, scale, offset, groups, relu_in=Tru
     return y
 
 
-def bn_fwd(x, scale, offset, labels, groups, relu, eps=1e-5):
+def bn_fwd_f64(x, scale, offset, labels, groups, relu, eps=1e-5):
+    """bn_fwd with the statistics summed in fp64 throughout (ctgan_bn_stats_f64): for eps far below 1e-5 (ct_cifar's generator)."""
+    return bn_fwd(x, scale, offset, labels, groups, relu, eps, _stats=lib.ctgan_bn_stats_f64)
+
+
+def bn_fwd(x, scale, offset, labels, groups, relu, eps=1e-5, _stats=None):
     """x channels-last [N,C,H,W] (or [N,C]); returns y, mean[groups,C], rstd[groups,C]."""
     _need_dev(x, scale, offset, labels)
     x4 = x if x.dim() == 4 else x.view(x.shape[0], x.shape[1], 1, 1)
@@ -1483,7 +1488,7 @@ def bn_fwd(x, scale, offset, labels, groups, relu, eps=1e-5):
     rstd = torch.empty((groups, C), dtype=torch.float32, device=x.device)
     nb = lib.ctgan_bn_workspace_bytes(N, hw, C, groups, 1)
     ws = workspace(nb, x.device)
-    check(lib.ctgan_bn_stats(_ptr(x4), N, hw, C, groups, eps, _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream()),
+    check((_stats or lib.ctgan_bn_stats)(_ptr(x4), N, hw, C, groups, eps, _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream()),
           'bn_stats')
     y = empty_cl(N, C, H, W, x.device)
     check(lib.ctgan_bn_apply(_ptr(x4), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(offset), _ptr(labels), _ptr(y), N, hw,
@@ -2132,3 +2137,122 @@ def adam_theano_step(theta, g, m, v, avg, state, beta1, beta2, eps=1e-8, avg_rat
         assert t is None or (t.is_contiguous() and t.numel() == theta.numel())
     check(lib.ctgan_adam_theano_step(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), _ptr(avg), theta.numel(), _ptr(state), beta1, beta2, eps,
                                      avg_rate, _stream()), 'adam_theano_step')
+
+
+# ---------------------------------------------------------------- convolutional semi-supervised classifier (csrc/ssl_conv.hip; ct_cifar.py)
+def wn_mid_fwd(theta, s, eps=0.0):
+    """-> (W, rnorm) of a [k, k, out, in] transposed-conv filter: W = theta * s[out] / sqrt(eps + sum over (k, k, in) of theta^2)."""
+    _need_dev(theta, s)
+    assert theta.dim() == 4 and theta.is_contiguous() and theta.dtype == torch.float32, 'dense [k, k, out, in] fp32 filter expected'
+    R, S, n_out, n_in = theta.shape
+    assert s.is_contiguous() and s.numel() == n_out
+    w = torch.empty_like(theta)
+    rnorm = torch.empty(n_out, dtype=torch.float32, device=theta.device)
+    check(lib.ctgan_wn_mid_fwd(_ptr(theta), _ptr(s), R * S, n_out, n_in, eps, _ptr(w), _ptr(rnorm), _stream()), 'wn_mid_fwd')
+    return w, rnorm
+
+
+def wn_mid_bwd(gw, theta, s, rnorm, want_gs=True):
+    """-> (gtheta, gs or None) of wn_mid_fwd."""
+    _need_dev(gw, theta, s, rnorm)
+    assert theta.dim() == 4 and theta.is_contiguous() and theta.dtype == torch.float32
+    R, S, n_out, n_in = theta.shape
+    gw = gw.contiguous()
+    assert gw.shape == theta.shape and rnorm.numel() == n_out and s.numel() == n_out
+    gtheta = torch.empty_like(theta)
+    gs = torch.empty(n_out, dtype=torch.float32, device=theta.device) if want_gs else None
+    check(lib.ctgan_wn_mid_bwd(_ptr(gw), _ptr(theta), _ptr(s), _ptr(rnorm), R * S, n_out, n_in, _ptr(gtheta), _ptr(gs), _stream()), 'wn_mid_bwd')
+    return gtheta, gs
+
+
+WN_INIT_ACTS = {None: 0, 'identity': 0, 'lrelu': 1, 'tanh': 2}
+
+
+def wn_init_map(y, g, b, act=None, slope=0.2, init_stdv=1.0):
+    """Data-dependent init of one layer in place on the channels-last pre-activation y ([rows, C], or logical [N,C,H,W] with NHWC
+    memory): y <- act((y - mean_c) inv_c), inv_c = init_stdv / rms of the centred channel; g *= inv; b = -mean inv.
+    act: None | 'lrelu' (slope) | 'tanh'."""
+    _need_dev(y, g, b)
+    if y.dim() == 4:
+        assert y.permute(0, 2, 3, 1).is_contiguous(), 'channels-last map expected'
+        rows, cols = y.shape[0] * y.shape[2] * y.shape[3], y.shape[1]
+    else:
+        rows, cols = _rows2d(y)
+    assert y.dtype == torch.float32 and g.is_contiguous() and b.is_contiguous() and g.numel() == cols and b.numel() == cols
+    check(lib.ctgan_wn_init_map(_ptr(y), rows, cols, WN_INIT_ACTS[act], float(slope), float(init_stdv), _ptr(g), _ptr(b), _stream()),
+          'wn_init_map')
+    return y
+
+
+def featcons_fwd(f, B, logits=None):
+    """f [4B, F] = features of [lab ; unl ; unl2 ; fake] -> out2 = {mean (f[B:2B] - f[2B:3B])^2, train_err2 of logits [4B, nc] (0 without)}."""
+    _need_dev(f, logits)
+    rows, F_ = _rows2d(f)
+    assert rows == 4 * B
+    nc = 0
+    if logits is not None:
+        lrows, nc = _rows2d(logits)
+        assert lrows == 4 * B
+    out2 = torch.empty(2, dtype=torch.float32, device=f.device)
+    check(lib.ctgan_featcons_fwd(_ptr(f), _ptr(logits), B, F_, nc, _ptr(out2), _stream()), 'featcons_fwd')
+    return out2
+
+
+def featcons_bwd(f, gout, B):
+    """-> gf [4B, F] of gout[0] * out2[0]."""
+    _need_dev(f, gout)
+    rows, F_ = _rows2d(f)
+    assert rows == 4 * B and gout.numel() >= 1
+    gf = torch.empty_like(f)
+    check(lib.ctgan_featcons_bwd(_ptr(f), _ptr(gout.contiguous()), B, F_, _ptr(gf), _stream()), 'featcons_bwd')
+    return gf
+
+
+def featmatch_l1_fwd(f, B):
+    """f [2B, C] -> (loss = mean_j |mean_i f[:B] - mean_i f[B:]|, diff [C])."""
+    _need_dev(f)
+    rows, C = _rows2d(f)
+    assert rows == 2 * B
+    loss = torch.empty((), dtype=torch.float32, device=f.device)
+    diff = torch.empty(C, dtype=torch.float32, device=f.device)
+    check(lib.ctgan_featmatch_l1_fwd(_ptr(f), B, C, _ptr(loss), _ptr(diff), _stream()), 'featmatch_l1_fwd')
+    return loss, diff
+
+
+def featmatch_l1_bwd(diff, gout, B):
+    _need_dev(diff, gout)
+    C = diff.numel()
+    gf = torch.empty(2 * B, C, dtype=torch.float32, device=diff.device)
+    check(lib.ctgan_featmatch_l1_bwd(_ptr(diff), _ptr(gout.contiguous()), B, C, _ptr(gf), _stream()), 'featmatch_l1_bwd')
+    return gf
+
+
+def aug_gather(data, idx, lut, win, pad, spec=None, offset=None, flip=False, rot180=True, channels_last=True, out=None):
+    """Rows idx of the device-resident uint8 set data [N, C, S, S] -> float32 logical [rows, C, win, win] windows of the
+    reflect-padded images, bytes converted through the 256-entry table `lut`.  spec = (seed, stream id, step counter): the flip and
+    the two offsets of row r are elements 3r, 3r+1, 3r+2 of that uniform stream; spec None: the fixed `offset` = (oy, ox) into the
+    padded image and `flip`.  rot180: the window is written rotated by 180 degrees (the coordinates the SAME-padded kernels run the
+    Theano network in); channels_last: NHWC memory under the logical NCHW shape, else plain NCHW."""
+    _need_dev(idx, lut, out)
+    if not data.is_cuda:
+        raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % data.device)
+    assert data.dtype == torch.uint8 and data.dim() == 4 and data.is_contiguous() and data.shape[2] == data.shape[3]
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and lut.numel() == 256
+    N, C, S, _ = data.shape
+    rows = idx.numel()
+    if out is None:
+        out = empty_cl(rows, C, win, win, data.device) if channels_last else torch.empty(rows, C, win, win, dtype=torch.float32, device=data.device)
+    assert tuple(out.shape) == (rows, C, win, win) and out.dtype == torch.float32
+    assert (out.permute(0, 2, 3, 1) if channels_last else out).is_contiguous()
+    if spec is not None:
+        seed, sid, ctr = spec
+        assert ctr is None or (ctr.is_cuda and ctr.dtype == torch.int64)
+        aug, oy, ox = 1, 0, 0
+    else:
+        seed, sid, ctr, aug = 0, 0, None, 0
+        oy, ox = (pad, pad) if offset is None else offset
+    check(lib.ctgan_aug_gather(data.data_ptr(), _ptr(idx), N, rows, C, S, int(pad), int(win), aug, int(oy), int(ox), int(bool(flip)),
+                               int(bool(rot180)), int(bool(channels_last)), _ptr(lut), int(seed), int(sid), _ptr(ctr), _ptr(out), _stream()),
+          'aug_gather')
+    return out

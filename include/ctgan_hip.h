@@ -416,6 +416,11 @@ int ctgan_interpolate(const float* real, const float* fake, const float* alpha, 
 int ctgan_bn_stats(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps,
                    float* mean /*[groups,c]*/, float* rstd /*[groups,c]*/,
                    void* ws, size_t ws_bytes, ctgan_stream_t stream);
+/* The same with every partial sum in fp64 (ctgan_bn_stats keeps short per-thread sums in fp32 on its vector path): for eps as small
+ * as 1e-6, where sum x^2 / n - mean^2 of a channel whose spread is far below its mean must not lose the variance to rounding.    */
+int ctgan_bn_stats_f64(const float* x, int32_t n, int32_t hw, int32_t c, int32_t groups, float eps,
+                       float* mean /*[groups,c]*/, float* rstd /*[groups,c]*/,
+                       void* ws, size_t ws_bytes, ctgan_stream_t stream);
 int ctgan_bn_apply(const float* x, const float* mean, const float* rstd, const float* scale,
                    const float* offset, const int32_t* labels, float* y, int32_t n, int32_t hw,
                    int32_t c, int32_t groups, int32_t relu, ctgan_stream_t stream);
@@ -694,6 +699,42 @@ int ctgan_bn2d_bwd(const float* gy, const float* xhat, const float* offset, cons
  * root -; avg += avg_rate (theta - avg) (avg may be NULL).  state = {lr, b1^t, b2^t, skipped} as ctgan_adam_step's.           */
 int ctgan_adam_theano_step(float* theta, const float* g, float* m, float* v, float* avg, int64_t n, float* state, float beta1,
                            float beta2, float eps, float avg_rate, ctgan_stream_t stream);
+
+
+/* ---- convolutional semi-supervised CT classifier (csrc/ssl_conv.hip; TH/CT_CIFAR.py) -----------------------------------------
+ * Weight norm of a filter whose output axis is in the middle (TH/nn.py:70-81, Deconv2DLayer): theta [outer, out, inner] row-major
+ * (a [k,k,out,in] transposed-conv filter: outer = k k, inner = in), w[a,o,i] = theta[a,o,i] * s[o] * rnorm[o],
+ * rnorm[o] = 1 / sqrt(eps + sum_{a,i} theta[a,o,i]^2).  The backward has the contract of ctgan_wn_bwd (saved rnorm, gs may be NULL). */
+int ctgan_wn_mid_fwd(const float* theta, const float* s, int32_t outer, int32_t out, int32_t inner, float eps, float* w, float* rnorm,
+                     ctgan_stream_t stream);
+int ctgan_wn_mid_bwd(const float* gw, const float* theta, const float* s, const float* rnorm, int32_t outer, int32_t out,
+                     int32_t inner, float* gtheta, float* gs, ctgan_stream_t stream);
+/* Data-dependent init of a weight-normalised conv / NIN / dense layer (TH/nn.py:85-95) in place on the channels-last
+ * pre-activation y [rows = N H W, cols = C]: m_c the column mean, inv_c = init_stdv / sqrt(mean_i (y_ic - m_c)^2);
+ * y <- act((y - m_c) inv_c) - no b is added in this pass -; g_c <- g_c inv_c; b_c <- -m_c inv_c.
+ * act: 0 identity, 1 LeakyReLU with `slope`, 2 tanh.                                                                           */
+int ctgan_wn_init_map(float* y, int64_t rows, int32_t cols, int32_t act, float slope, float init_stdv, float* g, float* b,
+                      ctgan_stream_t stream);
+/* Feature consistency (TH/CT_CIFAR.py:120) over the features f [4b, fdim] of [labelled ; unlabelled ; unlabelled, second pass ;
+ * generated]: out2[0] = mean_{i,j} (f[b+i,j] - f[2b+i,j])^2; with logits [4b, nc] (may be NULL) out2[1] = train_err2 =
+ * mean_{i<b} (max_k logits[i,k] <= 0) (:128), else 0.  The backward writes the [4b, fdim] cotangent of gout[0] * out2[0].       */
+int ctgan_featcons_fwd(const float* f, const float* logits, int32_t b, int32_t fdim, int32_t nc, float* out2, ctgan_stream_t stream);
+int ctgan_featcons_bwd(const float* f, const float* gout, int32_t b, int32_t fdim, float* gf, ctgan_stream_t stream);
+/* L1 feature matching (TH/CT_CIFAR.py:152-156) over f [2b, c]: diff_j = mean_i f_ij - mean_i f_(b+i)j, loss = mean_j |diff_j|;
+ * the backward: gf = +-gout sign(diff_j) / (c b), zero where diff_j = 0.                                                        */
+int ctgan_featmatch_l1_fwd(const float* f, int32_t b, int32_t c, float* loss, float* diff, ctgan_stream_t stream);
+int ctgan_featmatch_l1_bwd(const float* diff, const float* gout, int32_t b, int32_t c, float* gf, ctgan_stream_t stream);
+/* Augmenting gather (TH/CT_CIFAR.py:48, :211-265): output row r is a win x win window of image idx[r] of the uint8 set
+ * data [n_data, channels, size, size], reflect-padded by `pad` through index arithmetic, flipped horizontally or not, each byte
+ * converted through the 256-entry float table `lut`.  In the reference's orientation out[c,y,x] = P'[c, oy + y, ox + x] with P'
+ * the padded image after the flip.  augment != 0: flip = u[3r] > 0.5, oy = min(int((2 pad + 1) u[3r+1]), 2 pad), ox the same of
+ * u[3r+2], u the stream ctgan_rng_uniform(., seed, stream_id, ctr) writes (win <= size); augment == 0: off_y, off_x, flip as given
+ * (the window must lie inside the padded image).  rot180 != 0 writes the window rotated by 180 degrees; channels_last != 0 writes
+ * rows of [win, win, channels], else [channels, win, win].  An index outside [0, n_data) reads nothing and writes NaN.         */
+int ctgan_aug_gather(const uint8_t* data, const int32_t* idx, int32_t n_data, int32_t rows, int32_t channels, int32_t size,
+                     int32_t pad, int32_t win, int32_t augment, int32_t off_y, int32_t off_x, int32_t flip, int32_t rot180,
+                     int32_t channels_last, const float* lut, uint64_t seed, uint64_t stream_id, const uint64_t* ctr, float* out,
+                     ctgan_stream_t stream);
 
 
 #ifdef __cplusplus
