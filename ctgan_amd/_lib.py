@@ -236,6 +236,10 @@ SIGNATURES = {
     'ctgan_featmatch_l1_bwd': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
     'ctgan_aug_gather': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                  c_int32, _p, c_uint64, c_uint64, _p, _p, _p]),
+    # temporal-ensembling classifier (csrc/ssl_te.hip)
+    'ctgan_te_head_fwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
+    'ctgan_te_head_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p]),
+    'ctgan_te_ensemble_update': (c_int, [_p, _p, _p, c_int64, c_float, c_float, _p]),
 }
 
 

@@ -39,3 +39,8 @@ def load(path, trainer):
     trainer.rng.ctr.fill_(ck['rng']['ctr'])
     eval_stream(trainer).ctr.fill_(ck['rng'].get('eval_ctr', 0))
     return ck['iteration']
+
+
+def load_extra(path):
+    """The `extra` dict a checkpoint was saved with (empty if none): state that belongs to one trainer class, restored by its caller."""
+    return torch.load(path, map_location='cpu', weights_only=False).get('extra') or {}

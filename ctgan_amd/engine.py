@@ -586,11 +586,15 @@ class GraphedSSLTrainer:
     def _g_body(self):
         return self.t.g_body(self.x_unl2)
 
+    def _extra_slots(self):
+        """Further device buffers the bodies write, snapshotted and restored around the capture with the optimizers' slots."""
+        return []
+
     def _capture(self, warmup):
         t = self.t
         K.reset_capture_workspaces()
         opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
+        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr] + self._extra_slots()
         snap = [b.clone() for b in bufs]
         steps = [o.t for o in opts]
         for o in opts:
@@ -689,3 +693,18 @@ class GraphedCifarSSLTrainer(GraphedSSLTrainer):
             t.g_opt.set_lr(t.lr())
             return t.g_body_idx(i_unl2.to(t.dev))
         return super().g_step(i_unl2)
+
+
+class GraphedCifarTETrainer(GraphedCifarSSLTrainer):
+    """GraphedCifarSSLTrainer for ct_cifar_te.CifarTETrainer.  Staged are i_lab, labels, i_unl and i_unl2; the staged i_unl serves the
+    augmenting gather AND the loss head, which reads the target rows and writes the prediction rows of those indices inside the
+    captured classifier graph (kernels.te_head_fwd / te_head_bwd) - no table row crosses to the host within an epoch.  One stream,
+    no parallel branches.  The capture's warm-up runs on the staged all-zero indices (duplicates: memory-safe) and so writes row 0
+    of the two prediction tables: both tables are snapshotted and restored with the other slots, so a graphed run equals an eager
+    one bit for bit, tables included.  The graphs hold the tables' addresses: CifarTETrainer changes them in place only
+    (end_epoch, load_te_state); bind the data before building the engine.  end_epoch() is not captured - two launches per epoch."""
+
+    def _extra_slots(self):
+        t = self.t
+        assert t.epoch_pred is not None, 'bind the uint8 training set first (CifarTETrainer.bind_data allocates the tables)'
+        return [t.epoch_pred, t.epoch_pred2]

@@ -2001,3 +2001,30 @@ class FeatMatchL1Fn(Function):
 
 def feature_matching_l1(f, B):
     return FeatMatchL1Fn.apply(f, int(B))
+
+
+# ---------------------------------------------------------------- temporal-ensembling classifier (csrc/ssl_te.hip; ct_cifar_te.py)
+class TEHeadFn(Function):
+    """out8 = {loss_lab, loss_unl, CT_, train_err, train_err2, mean ct, mean ctf, 0} of the classifier step of TH/CT_CIFAR-10_TE.py
+    (:102-126) over logits [3B, nc] and features [3B, F] = [lab ; unl ; fake], against the rows idx of the target tables.
+    Differentiable in out8[0] and out8[1] with respect to the logits and the features; the targets, the indices and the prediction
+    tables (written in place by the forward) carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, feat, labels, idx, targets, targets2, pred, pred2, B, lam2, feat_w, M):
+        out8 = K.te_head_fwd(logits, feat, labels, idx, targets, targets2, pred, pred2, B, lam2, feat_w, M)
+        ctx.save_for_backward(logits, feat, labels, idx)
+        ctx.tables = (targets, targets2)          # constants of the step; not versioned: the epoch-end update rewrites them in place
+        ctx.cfg = (B, lam2, feat_w, M)
+        return out8
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, feat, labels, idx = ctx.saved_tensors
+        gl, gf = K.te_head_bwd(logits, feat, labels, idx, ctx.tables[0], ctx.tables[1], gout, *ctx.cfg)
+        return (gl, gf) + (None,) * 10
+
+
+def te_head(logits, feat, labels, idx, targets, targets2, pred, pred2, B, lam2, feat_w, M):
+    return TEHeadFn.apply(logits, feat, labels, idx, targets.detach(), targets2.detach(), pred.detach(), pred2.detach(), int(B), float(lam2),
+                          float(feat_w), float(M))

@@ -2256,3 +2256,53 @@ def aug_gather(data, idx, lut, win, pad, spec=None, offset=None, flip=False, rot
                                int(bool(rot180)), int(bool(channels_last)), _ptr(lut), int(seed), int(sid), _ptr(ctr), _ptr(out), _stream()),
           'aug_gather')
     return out
+
+
+# ---------------------------------------------------------------- temporal-ensembling classifier (csrc/ssl_te.hip; ct_cifar_te.py)
+def _te_head_args(logits, feat, labels, idx, targets, targets2, B):
+    _need_dev(logits, feat, labels, idx, targets, targets2)
+    rows, nc = _rows2d(logits)
+    frows, F_ = _rows2d(feat)
+    assert rows == 3 * B and frows == 3 * B, 'logits and features of the stacked [lab ; unl ; fake] batch expected'
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous() and idx.numel() == B
+    N, tnc = _rows2d(targets)
+    assert tnc == nc and tuple(_rows2d(targets2)) == (N, F_), 'contiguous tables [N, nc] and [N, F] expected'
+    return nc, F_, N
+
+
+def te_head_fwd(logits, feat, labels, idx, targets, targets2, pred, pred2, B, lam2, feat_w, M):
+    """logits [3B, nc], feat [3B, F] = [lab ; unl ; fake]; idx int32 [B]: the rows of this batch's unlabelled examples in the
+    contiguous fp32 tables targets / pred [N, nc] and targets2 / pred2 [N, F] -> out8 = {loss_lab, loss_unl, CT_, train_err,
+    train_err2, mean ct, mean ctf, 0}; the unlabelled logits and feature rows are stored into pred[idx] and pred2[idx] IN PLACE in
+    the same launch.  The indices of one batch must be distinct (slices of a permutation): with duplicates the stores stay inside the
+    tables but which of the rows survives is unspecified.  An index outside [0, N) makes loss_unl NaN and touches no table row."""
+    nc, F_, N = _te_head_args(logits, feat, labels, idx, targets, targets2, B)
+    _need_dev(pred, pred2)
+    assert tuple(_rows2d(pred)) == (N, nc) and tuple(_rows2d(pred2)) == (N, F_), 'contiguous prediction tables [N, nc] and [N, F] expected'
+    out8 = torch.empty(8, dtype=torch.float32, device=logits.device)
+    check(lib.ctgan_te_head_fwd(_ptr(logits), _ptr(feat), _ptr(labels), _ptr(idx), _ptr(targets), _ptr(targets2), B, nc, F_, N, lam2, feat_w, M,
+                                _ptr(out8), _ptr(pred), _ptr(pred2), _stream()), 'te_head_fwd')
+    return out8
+
+
+def te_head_bwd(logits, feat, labels, idx, targets, targets2, gout, B, lam2, feat_w, M):
+    """-> (glogits [3B, nc], gfeat [3B, F]) of gout[0] * loss_lab + gout[1] * loss_unl; the targets are constants."""
+    nc, F_, N = _te_head_args(logits, feat, labels, idx, targets, targets2, B)
+    _need_dev(gout)
+    gout = gout.contiguous()
+    assert gout.numel() >= 2
+    gl, gf = torch.empty_like(logits), torch.empty_like(feat)
+    check(lib.ctgan_te_head_bwd(_ptr(logits), _ptr(feat), _ptr(labels), _ptr(idx), _ptr(targets), _ptr(targets2), _ptr(gout), B, nc, F_, N, lam2,
+                                feat_w, M, _ptr(gl), _ptr(gf), _stream()), 'te_head_bwd')
+    return gl, gf
+
+
+def te_ensemble_update(ens, targets, pred, decay, epoch):
+    """In place on three contiguous fp32 tensors of one shape: ens = decay ens + (1 - decay) pred; targets = ens / (1 - decay^(epoch + 1))
+    (the correction formed here in double precision); pred = 0."""
+    _need_dev(ens, targets, pred)
+    for t in (ens, targets, pred):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == ens.shape, 'three contiguous fp32 tables of one shape expected'
+    inv_corr = 1.0 / (1.0 - float(decay) ** (int(epoch) + 1))
+    check(lib.ctgan_te_ensemble_update(_ptr(ens), _ptr(targets), _ptr(pred), ens.numel(), float(decay), inv_corr, _stream()), 'te_ensemble_update')

@@ -737,6 +737,32 @@ int ctgan_aug_gather(const uint8_t* data, const int32_t* idx, int32_t n_data, in
                      ctgan_stream_t stream);
 
 
+/* ---- temporal-ensembling CT classifier (csrc/ssl_te.hip; TH/CT_CIFAR-10_TE.py) ------------------------------------------------
+ * Loss head of the classifier step (:102-126) over logits [3b, nc] and features [3b, fdim] = [labelled ; unlabelled ; generated],
+ * the consistency term taken against the rows idx[i] (int32 [b]) of the device tables targets [n, nc] (raw ensembled logits,
+ * softmaxed here) and targets2 [n, fdim], read by index inside the kernel:  ct_i = mean_k (softmax(unl_i) - softmax(t_i))_k^2,
+ * ctf_i = mean_j (f_ij - t2_ij)^2, CT_i = lam2 (ct_i + feat_w ctf_i) - m, CT_ = mean_i max(CT_i, 0),
+ * loss_unl = (CT_ - mean lse(unl) + mean softplus(lse(unl)) + mean softplus(lse(fake))) / 2;
+ * out8 = { loss_lab, loss_unl, CT_, train_err, train_err2, mean ct, mean ctf, 0 }.  The same launch stores the unlabelled logits
+ * and feature rows into pred[idx[i]] [n, nc] and pred2[idx[i]] [n, fdim] (:300-302) with plain stores: the indices of a batch
+ * are distinct by contract (slices of a permutation); duplicates are memory-safe, the surviving row unspecified.  Numerics as
+ * ctgan_ssl_head_fwd.  A label outside [0, nc) makes loss_lab NaN and reads nothing; an index outside [0, n) makes loss_unl, CT_,
+ * mean ct and mean ctf NaN and reads and writes no table row.  Fixed-order reductions, no atomics.  The backward writes the
+ * cotangents glogits [3b, nc] and gfeat [3b, fdim] of gout[0] * loss_lab + gout[1] * loss_unl (gout: device float[>= 2]),
+ * recomputed from the logits, features and target rows (the targets are constants); gfeat is exactly 0 on the labelled and
+ * generated rows; an unlabelled row with an index outside [0, n) gets NaN.                                                     */
+int ctgan_te_head_fwd(const float* logits, const float* feat, const int32_t* labels, const int32_t* idx, const float* targets,
+                      const float* targets2, int32_t b, int32_t nc, int32_t fdim, int32_t n, float lam2, float feat_w, float m,
+                      float* out8, float* pred, float* pred2, ctgan_stream_t stream);
+int ctgan_te_head_bwd(const float* logits, const float* feat, const int32_t* labels, const int32_t* idx, const float* targets,
+                      const float* targets2, const float* gout, int32_t b, int32_t nc, int32_t fdim, int32_t n, float lam2,
+                      float feat_w, float m, float* glogits, float* gfeat, ctgan_stream_t stream);
+/* Epoch-end update of one table triple of n elements (:305-309, :273-274): ens = decay ens + (1 - decay) pred,
+ * targets = ens inv_corr with inv_corr = 1 / (1 - decay^(epoch + 1)) formed by the caller in double precision, pred = 0.
+ * float4 accesses where the three pointers are 16-byte aligned, a scalar tail.                                                  */
+int ctgan_te_ensemble_update(float* ens, float* targets, float* pred, int64_t n, float decay, float inv_corr, ctgan_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif
