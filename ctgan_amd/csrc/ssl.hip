@@ -6,32 +6,14 @@
 //
 // Every reduction runs in a fixed order (per-thread strided partial sums, then a fixed LDS combine): no float atomics, so a
 // replayed graph is bit-stable.  Column reductions put lanes along the contiguous `out` axis (RED_COLS columns per workgroup) and
-// RED_SL row slices down the reduced axis.
+// RED_SL row slices down the reduced axis; they, the row softmax pieces and the feature-matching forward are ssl_common.h's.
 #include "common.h"
 #include "philox.h"
+#include "ssl_common.h"
 
 namespace {
 using namespace ctgan_philox;
-
-// 16 columns x 32 row slices: a [784, 1000] weight gives 63 workgroups of 512 threads with 25 rows per thread (64 columns x 16 slices
-// left it on 16 workgroups with 49 dependent iterations each: 15 us a launch); a wave covers 16 columns (64 B) of four rows.
-constexpr int RED_COLS = 16;      // lanes along the contiguous axis
-constexpr int RED_SL = 32;        // row slices per workgroup
-constexpr int RED_THREADS = RED_COLS * RED_SL;
-
-// sum of the RED_SL slice partials of column cx, in slice order
-__device__ __forceinline__ float combine_slices(float (*part)[RED_COLS], int cx) {
-    float t = 0.f;
-#pragma unroll
-    for (int s = 0; s < RED_SL; ++s) t += part[s][cx];
-    return t;
-}
-
-__device__ __forceinline__ float softplus_f(float t) { return fmaxf(t, 0.f) + log1pf(expf(-fabsf(t))); }
-__device__ __forceinline__ float sigmoid_f(float t) {
-    const float e = expf(-fabsf(t));
-    return t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
+using namespace ctgan_ssl;
 
 // ------------------------------------------------------------------------------------------------ weight norm
 // W[i,j] = theta[i,j] * s[j] / sqrt(eps + sum_i theta[i,j]^2)
@@ -143,19 +125,10 @@ __global__ void __launch_bounds__(RED_THREADS) wn_init_kernel(float* __restrict_
     __shared__ float part[RED_SL][RED_COLS];
     const int cx = threadIdx.x % RED_COLS, sl = threadIdx.x / RED_COLS;
     const long long j = (long long)blockIdx.x * RED_COLS + cx;
-    const bool on = j < cols;
-    float acc = 0.f;
-    if (on) for (long long i = sl; i < rows; i += RED_SL) acc += y[i * cols + j];
-    part[sl][cx] = acc;
-    __syncthreads();
-    const float mean = combine_slices(part, cx) / (float)rows;
-    __syncthreads();
-    acc = 0.f;
-    if (on) for (long long i = sl; i < rows; i += RED_SL) { const float d = y[i * cols + j] - mean; acc += d * d; }
-    part[sl][cx] = acc;
-    __syncthreads();
-    if (!on) return;
-    const float stdv = sqrtf(combine_slices(part, cx) / (float)rows);
+    float mean, ssd;
+    col_mean_ssd(y, rows, cols, j, part, mean, ssd);
+    if (j >= cols) return;
+    const float stdv = sqrtf(ssd / (float)rows);
     for (long long i = sl; i < rows; i += RED_SL) {
         float v = (y[i * cols + j] - mean) / stdv;
         if (relu) v = fmaxf(v, 0.f);
@@ -165,22 +138,6 @@ __global__ void __launch_bounds__(RED_THREADS) wn_init_kernel(float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ semi-supervised loss head
-struct RowStat { float mx, rse, lse; };      // rse = 1 / sum exp(l - mx);  lse = mx + log(sum exp(l - mx))
-__device__ __forceinline__ RowStat row_stat(const float* __restrict__ l, int nc) {
-    float mx = l[0];
-    for (int k = 1; k < nc; ++k) mx = fmaxf(mx, l[k]);
-    float se = 0.f;
-    for (int k = 0; k < nc; ++k) se += expf(l[k] - mx);
-    return {mx, 1.f / se, mx + logf(se)};
-}
-// softmax(l)_k: from the max-subtracted exponent, not from lse (whose rounding at |l| ~ 80 is 4e-6 relative to a probability)
-__device__ __forceinline__ float prob(float l, RowStat s) { return expf(l - s.mx) * s.rse; }
-// consistency term of one unlabelled row: ct = mean_k (softmax(u)_k - softmax(u2)_k)^2
-__device__ __forceinline__ float row_ct(const float* __restrict__ u, const float* __restrict__ u2, RowStat su, RowStat s2, int nc) {
-    float acc = 0.f;
-    for (int k = 0; k < nc; ++k) { const float d = prob(u[k], su) - prob(u2[k], s2); acc += d * d; }
-    return acc / (float)nc;
-}
 constexpr int HEAD_THREADS = 256;
 // logits [4B, nc] = [lab ; unl ; unl2 ; fake];  out = {loss_lab, loss_unl, CT, train_err};  one workgroup
 __global__ void __launch_bounds__(HEAD_THREADS) ssl_head_fwd_kernel(const float* __restrict__ lg, const int32_t* __restrict__ labels, int B, int nc,
@@ -194,7 +151,7 @@ __global__ void __launch_bounds__(HEAD_THREADS) ssl_head_fwd_kernel(const float*
         const float* f = lg + (long long)(3 * B + i) * nc;
         const RowStat sl = row_stat(l, nc), su = row_stat(u, nc), s2 = row_stat(u2, nc), sf = row_stat(f, nc);
         const int yi = labels[i];
-        const float ly = (yi >= 0 && yi < nc) ? l[yi] : __int_as_float(0x7fc00000);      // a label outside [0, nc) poisons the loss, reads nothing
+        const float ly = (yi >= 0 && yi < nc) ? l[yi] : nan_f();      // a label outside [0, nc) poisons the loss, reads nothing
         int am = 0;
         for (int k = 1; k < nc; ++k) if (l[k] > l[am]) am = k;                               // first maximum, as argmax
         const float ct = row_ct(u, u2, su, s2, nc);
@@ -205,15 +162,7 @@ __global__ void __launch_bounds__(HEAD_THREADS) ssl_head_fwd_kernel(const float*
         acc[3] += softplus_f(sf.lse);
         acc[4] += am != yi ? 1.f : 0.f;
     }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) red[q][threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int w = HEAD_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red, acc);
     if (threadIdx.x == 0) {
         const float inv = 1.f / (float)B;
         const float CT = red[1][0] * inv;
@@ -258,39 +207,10 @@ __global__ void ssl_head_bwd_kernel(const float* __restrict__ lg, const int32_t*
 }
 
 // ------------------------------------------------------------------------------------------------ feature matching
-// f [2B, C] = [f(G(z)) ; f(x)];  diff_j = mean_i f_ij (i < B) - mean_i f_ij (i >= B);  loss = mean_j diff_j^2.  ONE workgroup (the
-// loss is a sum over all columns) of 64 columns x 16 row slices that walks the column tiles.
-constexpr int FM_COLS = 64, FM_SL = 16, FM_THREADS = FM_COLS * FM_SL;
+// loss = mean_j diff_j^2 (ssl_common.h's body)
 __global__ void __launch_bounds__(FM_THREADS) featmatch_fwd_kernel(const float* __restrict__ f, int B, int C, float* __restrict__ loss,
                                                                    float* __restrict__ diff) {
-    __shared__ float pg[FM_SL][FM_COLS], pr[FM_SL][FM_COLS];
-    __shared__ float sq[FM_COLS];
-    const int cx = threadIdx.x % FM_COLS, sl = threadIdx.x / FM_COLS;
-    float acc2 = 0.f;
-    for (int j0 = 0; j0 < C; j0 += FM_COLS) {
-        const int j = j0 + cx;
-        float ag = 0.f, ar = 0.f;
-        if (j < C)
-            for (int i = sl; i < B; i += FM_SL) { ag += f[(long long)i * C + j]; ar += f[(long long)(B + i) * C + j]; }
-        pg[sl][cx] = ag; pr[sl][cx] = ar;
-        __syncthreads();
-        if (sl == 0 && j < C) {
-            float tg = 0.f, tr = 0.f;
-#pragma unroll
-            for (int s = 0; s < FM_SL; ++s) { tg += pg[s][cx]; tr += pr[s][cx]; }
-            const float d = tg / (float)B - tr / (float)B;
-            diff[j] = d;
-            acc2 += d * d;
-        }
-        __syncthreads();
-    }
-    if (sl == 0) sq[cx] = acc2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int k = 0; k < FM_COLS; ++k) t += sq[k];
-        loss[0] = t / (float)C;
-    }
+    featmatch_fwd_body<false>(f, B, C, loss, diff);
 }
 __global__ void featmatch_bwd_kernel(const float* __restrict__ diff, const float* __restrict__ gout, int B, int C, float* __restrict__ gf) {
     const long long n = 2LL * B * C;
@@ -309,19 +229,10 @@ __global__ void __launch_bounds__(RED_THREADS) bn2d_fwd_kernel(const float* __re
     __shared__ float part[RED_SL][RED_COLS];
     const int cx = threadIdx.x % RED_COLS, sl = threadIdx.x / RED_COLS;
     const long long j = (long long)blockIdx.x * RED_COLS + cx;
-    const bool on = j < C;
-    float acc = 0.f;
-    if (on) for (int i = sl; i < B; i += RED_SL) acc += x[(long long)i * C + j];
-    part[sl][cx] = acc;
-    __syncthreads();
-    const float mean = combine_slices(part, cx) / (float)B;
-    __syncthreads();
-    acc = 0.f;
-    if (on) for (int i = sl; i < B; i += RED_SL) { const float d = x[(long long)i * C + j] - mean; acc += d * d; }
-    part[sl][cx] = acc;
-    __syncthreads();
-    if (!on) return;
-    const float rs = 1.f / sqrtf(eps + combine_slices(part, cx) / (float)B);
+    float mean, ssd;
+    col_mean_ssd(x, B, C, j, part, mean, ssd);
+    if (j >= C) return;
+    const float rs = 1.f / sqrtf(eps + ssd / (float)B);
     if (sl == 0) rstd[j] = rs;
     const float bj = offset ? offset[j] : 0.f;
     for (int i = sl; i < B; i += RED_SL) {
@@ -387,7 +298,6 @@ __global__ void adam_theano_kernel(float* __restrict__ th, const float* __restri
     }
 }
 
-inline hipStream_t S(ctgan_stream_t s) { return static_cast<hipStream_t>(s); }
 inline unsigned col_blocks(long long cols) { return (unsigned)((cols + RED_COLS - 1) / RED_COLS); }
 constexpr long long MAX_COLS = 1LL << 21;      // grid.x of the column kernels stays far below the launch limit
 

@@ -8,9 +8,11 @@
 // float atomics, so a replayed graph is bit-stable.
 #include "common.h"
 #include "philox.h"
+#include "ssl_common.h"
 
 namespace {
 using namespace ctgan_philox;
+using namespace ctgan_ssl;
 
 constexpr int WG = 256;
 // sum over the workgroup in a fixed tree order; every thread receives it
@@ -72,32 +74,16 @@ __global__ void __launch_bounds__(WG) wn_mid_bwd_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------ data-dependent init on a map
 // y [rows = N H W, C] channels-last, in place: m_c = mean, inv_c = init_stdv / sqrt(mean (y - m_c)^2);  y <- act((y - m_c) inv_c)
 // (no b is added in the init pass);  g_c <- g_c inv_c;  b_c <- -m_c inv_c.  act: 0 identity, 1 LeakyReLU(slope), 2 tanh.
-constexpr int IM_COLS = 16, IM_SL = 32, IM_THREADS = IM_COLS * IM_SL;
-__device__ __forceinline__ float combine(float (*part)[IM_COLS], int cx) {
-    float t = 0.f;
-#pragma unroll
-    for (int s = 0; s < IM_SL; ++s) t += part[s][cx];
-    return t;
-}
-__global__ void __launch_bounds__(IM_THREADS) wn_init_map_kernel(float* __restrict__ y, long long rows, int cols, int act, float slope,
+__global__ void __launch_bounds__(RED_THREADS) wn_init_map_kernel(float* __restrict__ y, long long rows, int cols, int act, float slope,
                                                                  float init_stdv, float* __restrict__ g, float* __restrict__ b) {
-    __shared__ float part[IM_SL][IM_COLS];
-    const int cx = threadIdx.x % IM_COLS, sl = threadIdx.x / IM_COLS;
-    const long long j = (long long)blockIdx.x * IM_COLS + cx;
-    const bool on = j < cols;
-    float acc = 0.f;
-    if (on) for (long long i = sl; i < rows; i += IM_SL) acc += y[i * cols + j];
-    part[sl][cx] = acc;
-    __syncthreads();
-    const float mean = combine(part, cx) / (float)rows;
-    __syncthreads();
-    acc = 0.f;
-    if (on) for (long long i = sl; i < rows; i += IM_SL) { const float d = y[i * cols + j] - mean; acc += d * d; }
-    part[sl][cx] = acc;
-    __syncthreads();
-    if (!on) return;
-    const float inv = init_stdv / sqrtf(combine(part, cx) / (float)rows);
-    for (long long i = sl; i < rows; i += IM_SL) {
+    __shared__ float part[RED_SL][RED_COLS];
+    const int cx = threadIdx.x % RED_COLS, sl = threadIdx.x / RED_COLS;
+    const long long j = (long long)blockIdx.x * RED_COLS + cx;
+    float mean, ssd;
+    col_mean_ssd(y, rows, cols, j, part, mean, ssd);
+    if (j >= cols) return;
+    const float inv = init_stdv / sqrtf(ssd / (float)rows);
+    for (long long i = sl; i < rows; i += RED_SL) {
         float v = (y[i * cols + j] - mean) * inv;
         if (act == 1) v = v > 0.f ? v : slope * v;
         else if (act == 2) v = tanhf(v);
@@ -143,39 +129,11 @@ __global__ void featcons_bwd_kernel(const float* __restrict__ f, const float* __
 }
 
 // ------------------------------------------------------------------------------------------------ L1 feature matching
-// f [2B, C]:  diff_j = mean_i f_ij (i < B) - mean_i f_ij (i >= B);  loss = mean_j |diff_j|.  ONE workgroup of 64 columns x 16 row
-// slices that walks the column tiles (the shape of ssl.hip's featmatch_fwd_kernel).
-constexpr int FM_COLS = 64, FM_SL = 16, FM_THREADS = FM_COLS * FM_SL;
+// f [2B, C]:  diff_j = mean_i f_ij (i < B) - mean_i f_ij (i >= B);  loss = mean_j |diff_j|  (ssl_common.h's body, as ssl.hip's
+// featmatch_fwd_kernel)
 __global__ void __launch_bounds__(FM_THREADS) featmatch_l1_fwd_kernel(const float* __restrict__ f, int B, int C, float* __restrict__ loss,
                                                                       float* __restrict__ diff) {
-    __shared__ float pa[FM_SL][FM_COLS], pb[FM_SL][FM_COLS];
-    __shared__ float ab[FM_COLS];
-    const int cx = threadIdx.x % FM_COLS, sl = threadIdx.x / FM_COLS;
-    float acc = 0.f;
-    for (int j0 = 0; j0 < C; j0 += FM_COLS) {
-        const int j = j0 + cx;
-        float a0 = 0.f, a1 = 0.f;
-        if (j < C)
-            for (int i = sl; i < B; i += FM_SL) { a0 += f[(long long)i * C + j]; a1 += f[(long long)(B + i) * C + j]; }
-        pa[sl][cx] = a0; pb[sl][cx] = a1;
-        __syncthreads();
-        if (sl == 0 && j < C) {
-            float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-            for (int s = 0; s < FM_SL; ++s) { t0 += pa[s][cx]; t1 += pb[s][cx]; }
-            const float d = t0 / (float)B - t1 / (float)B;
-            diff[j] = d;
-            acc += fabsf(d);
-        }
-        __syncthreads();
-    }
-    if (sl == 0) ab[cx] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int k = 0; k < FM_COLS; ++k) t += ab[k];
-        loss[0] = t / (float)C;
-    }
+    featmatch_fwd_body<true>(f, B, C, loss, diff);
 }
 // gf = +-gout sign(diff_j) / (C B), zero where diff_j is zero
 __global__ void featmatch_l1_bwd_kernel(const float* __restrict__ diff, const float* __restrict__ gout, int B, int C, float* __restrict__ gf) {
@@ -238,11 +196,9 @@ __global__ void __launch_bounds__(WG) aug_gather_kernel(const uint8_t* __restric
         int X = ox + x;
         if (flip) X = Wp - 1 - X;
         const int sy = reflect(oy + y - pad, S), sx = reflect(X - pad, S);
-        o[e] = bad ? __int_as_float(0x7fc00000) : lut[img[(c * S + sy) * S + sx]];
+        o[e] = bad ? nan_f() : lut[img[(c * S + sy) * S + sx]];
     }
 }
-
-inline hipStream_t S(ctgan_stream_t s) { return static_cast<hipStream_t>(s); }
 
 }  // namespace
 
@@ -271,7 +227,7 @@ int ctgan_wn_init_map(float* y, int64_t rows, int32_t cols, int32_t act, float s
     if (!y || !g || !b) return ctgan_fail(CTGAN_E_BADARG, "wn_init_map: null pointer");
     if (rows <= 0 || cols <= 0 || cols > (1 << 21) || rows > (1LL << 40) / cols || act < 0 || act > 2 || !(init_stdv > 0.f))
         return ctgan_fail(CTGAN_E_BADARG, "wn_init_map: bad argument");
-    hipLaunchKernelGGL(wn_init_map_kernel, dim3((unsigned)((cols + IM_COLS - 1) / IM_COLS)), dim3(IM_THREADS), 0, S(stream), y, (long long)rows,
+    hipLaunchKernelGGL(wn_init_map_kernel, dim3((unsigned)((cols + RED_COLS - 1) / RED_COLS)), dim3(RED_THREADS), 0, S(stream), y, (long long)rows,
                        cols, act, slope, init_stdv, g, b);
     return ctgan_check_launch("wn_init_map");
 }

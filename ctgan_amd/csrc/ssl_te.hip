@@ -6,25 +6,10 @@
 // As in ssl.hip every reduction runs in a fixed order (strided per-lane partial sums, a fixed butterfly inside a 16-lane row group,
 // a fixed LDS tree over the workgroup) and there are no float atomics, so a replayed graph is bit-stable.
 #include "common.h"
+#include "ssl_common.h"
 
 namespace {
-
-__device__ __forceinline__ float softplus_f(float t) { return fmaxf(t, 0.f) + log1pf(expf(-fabsf(t))); }
-__device__ __forceinline__ float sigmoid_f(float t) {
-    const float e = expf(-fabsf(t));
-    return t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
-struct RowStat { float mx, rse, lse; };      // rse = 1 / sum exp(l - mx);  lse = mx + log(sum exp(l - mx))
-__device__ __forceinline__ RowStat row_stat(const float* __restrict__ l, int nc) {
-    float mx = l[0];
-    for (int k = 1; k < nc; ++k) mx = fmaxf(mx, l[k]);
-    float se = 0.f;
-    for (int k = 0; k < nc; ++k) se += expf(l[k] - mx);
-    return {mx, 1.f / se, mx + logf(se)};
-}
-// softmax(l)_k from the max-subtracted exponent (ssl.hip's `prob`)
-__device__ __forceinline__ float prob(float l, RowStat s) { return expf(l - s.mx) * s.rse; }
-__device__ __forceinline__ float nan_f() { return __int_as_float(0x7fc00000); }
+using namespace ctgan_ssl;
 
 constexpr int WG = 256;
 constexpr int LPR = 16;             // lanes of one row group: a wave holds four rows, a workgroup RPB
@@ -44,12 +29,6 @@ __device__ __forceinline__ float row_ctf(const float* __restrict__ f, const floa
     if (t2)
         for (int j = sub; j < F; j += LPR) { const float d = f[j] - t2[j]; acc += d * d; }
     return group_sum(acc) / (float)F;
-}
-// mean_k (softmax(u)_k - softmax(t)_k)^2
-__device__ __forceinline__ float row_ct(const float* __restrict__ u, const float* __restrict__ t, RowStat su, RowStat st, int nc) {
-    float acc = 0.f;
-    for (int k = 0; k < nc; ++k) { const float d = prob(u[k], su) - prob(t[k], st); acc += d * d; }
-    return acc / (float)nc;
 }
 
 // ------------------------------------------------------------------------------------------------ head, forward
@@ -110,15 +89,7 @@ __global__ void __launch_bounds__(WG) te_head_fwd_kernel(const float* __restrict
             acc[3] += softplus_f(row_stat(lg + (long long)(2 * B + i) * nc, nc).lse);
         }
     }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) red[q][threadIdx.x] = acc[q];
-    __syncthreads();
-    for (int w = WG / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red, acc);
     if (threadIdx.x == 0) {
         const float inv = 1.f / (float)B;
         const float CT = red[1][0] * inv;
@@ -217,7 +188,6 @@ __global__ void te_ensemble_kernel(float* __restrict__ ens, float* __restrict__ 
     }
 }
 
-inline hipStream_t S(ctgan_stream_t s) { return static_cast<hipStream_t>(s); }
 inline bool bad_head_shape(int32_t b, int32_t nc, int32_t fdim, int32_t n) {
     return b <= 0 || nc <= 0 || fdim <= 0 || n <= 0 || b > (1 << 24) || nc > (1 << 16) || fdim > (1 << 24);
 }

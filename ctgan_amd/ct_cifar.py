@@ -65,17 +65,16 @@ import os
 import numpy as np
 import torch
 
+from . import ct_common
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
-from .optim import FlatAdamTheano
-from .rng import DeviceRNG
 from .tflib.ops import wn_conv as _wn
 
 SID_AUG_LAB, SID_AUG_UNL = 16, 17      # stream ids of the augmenting gathers (outside the call-site numbering of a step)
 
 
-class Config:
+class Config(ct_common.Config):
     """The literals of TH/CT_CIFAR.py:17-27, :69-93, :123, :142-144 (tests shrink IMG, the widths and the batch sizes)."""
     SEED = 2
     SEED_DATA = 2
@@ -100,12 +99,6 @@ class Config:
     IMG = 32
     D_WIDTHS = (128, 128, 128, 256, 256, 256, 512, 256, 128)
     G_WIDTHS = (512, 256, 128)
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            if not hasattr(Config, k):
-                raise AttributeError('unknown hyper-parameter %s' % k)
-            setattr(self, k, v)
 
 
 cfg = Config()
@@ -203,33 +196,27 @@ def _stack(parts):
     return K.to_channels_last(torch.cat(parts, 0))
 
 
-class CifarSSLTrainer:
+class CifarSSLTrainer(ct_common.SSLTrainerBase):
     """The Theano functions train_batch_disc / train_batch_gen (:147, :160), init_param (:146) and test_batch (:148).  The step methods
     take image batches in the INTERNAL form - rotated, channels-last, as `gather` / `gather_fixed` write them (or `rot180` of images in
-    the reference's orientation); `predict` and `test_error` take the reference's orientation / the uint8 set."""
+    the reference's orientation); `predict` and `test_error` take the reference's orientation / the uint8 set.  A classifier batch
+    is (x_lab, labels, x_unl), train_iteration (:277-288) takes it followed by x_unl2."""
+    cfg = property(lambda self: cfg)
+    D_KEYS = ('out4', 'out2', 'loss_lab', 'loss_unl', 'loss_comp', 'loss_feat', 'train_err', 'train_err2')
+    REPORT = ('Iteration', (('loss_lab', 'loss_lab'), ('loss_unl', 'loss_unl'), ('train err', 'train_err'), ('train err2', 'train_err2')),
+              (('gen loss', 'loss_gen'),))
 
     def __init__(self, seed=None, data=None):
-        self.dev = lib._dev()
-        self.rng = DeviceRNG(cfg.SEED if seed is None else seed, 0, self.dev)
-        build_params()
-        self.d_named = lib.named_params_with_name('Classifier', trainable_only=True)
-        self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
-        self.d_params = [p for _, p in self.d_named]
-        self.g_params = [p for _, p in self.g_named]
-        self.d_opt = FlatAdamTheano(self.d_named, cfg.BETA1, cfg.BETA2, avg_rate=cfg.AVG_RATE)
-        self.g_opt = FlatAdamTheano(self.g_named, cfg.BETA1, cfg.BETA2, avg_rate=0.0)
-        # cotangents of {loss_lab, loss_unl head, CT, train_err} and {feature consistency, train_err2}:
-        # cost = loss_lab + UNLABELED_WEIGHT (head + FEAT_WEIGHT consistency)   (:123, :142)
-        self.d_seed = torch.tensor([1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0], dtype=torch.float32, device=self.dev)
-        self.d_seed2 = torch.tensor([cfg.UNLABELED_WEIGHT * cfg.FEAT_WEIGHT, 0.0], dtype=torch.float32, device=self.dev)
+        super().__init__(build_params, seed)
         self.lut = torch.from_numpy(byte_table()).to(self.dev)
         self.data = None
-        self.iteration = 0
         if data is not None:
             self.bind_data(data)
 
-    def lr(self):
-        return cfg.LR
+    def d_cotangents(self):
+        """out4 = {loss_lab, loss_unl head, CT, train_err}, out2 = {feature consistency, train_err2}:
+        cost = loss_lab + UNLABELED_WEIGHT (head + FEAT_WEIGHT consistency)   (:123, :142)"""
+        return {'out4': [1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0], 'out2': [cfg.UNLABELED_WEIGHT * cfg.FEAT_WEIGHT, 0.0]}
 
     # ---- the device-resident uint8 set
     def bind_data(self, images_u8):
@@ -274,21 +261,6 @@ class CifarSSLTrainer:
         return {'out4': out4, 'out2': out2, 'loss_lab': out4[0], 'loss_unl': loss_unl, 'loss_comp': out4[2], 'loss_feat': out2[0],
                 'train_err': out4[3], 'train_err2': out2[1], 'logits': logits, 'features': feat}
 
-    def d_grads(self, x_lab, labels, x_unl):
-        out = self.d_losses(x_lab, labels, x_unl)
-        grads = torch.autograd.grad([out['out4'], out['out2']], self.d_params, grad_outputs=[self.d_seed, self.d_seed2], allow_unused=True)
-        return out, grads
-
-    def d_body(self, x_lab, labels, x_unl):
-        """Losses, gradients, Adam + average, end of step - everything a replayed graph holds (the learning rate is device state)."""
-        out, grads = self.d_grads(x_lab, labels, x_unl)
-        self.d_opt.update(grads, rng=self.rng)
-        return {k: out[k].detach() for k in ('out4', 'out2', 'loss_lab', 'loss_unl', 'loss_comp', 'loss_feat', 'train_err', 'train_err2')}
-
-    def d_step(self, x_lab, labels, x_unl):
-        self.d_opt.set_lr(self.lr())
-        return self.d_body(x_lab, labels, x_unl)
-
     # ---- generator step
     def g_losses(self, x_unl):
         B = x_unl.shape[0]
@@ -296,27 +268,6 @@ class CifarSSLTrainer:
         fake = _generator(B, rng=self.rng)
         feats = _classifier(_stack([fake, x_unl]), rng=self.rng, features=True, frozen=True)
         return {'loss_gen': F.feature_matching_l1(feats, B)}
-
-    def g_grads(self, x_unl):
-        out = self.g_losses(x_unl)
-        grads = torch.autograd.grad(out['loss_gen'], self.g_params, allow_unused=True)
-        return out, grads
-
-    def g_body(self, x_unl):
-        out, grads = self.g_grads(x_unl)
-        self.g_opt.update(grads, rng=self.rng)
-        return {'loss_gen': out['loss_gen'].detach()}
-
-    def g_step(self, x_unl):
-        self.g_opt.set_lr(self.lr())
-        return self.g_body(x_unl)
-
-    def train_iteration(self, x_lab, labels, x_unl, x_unl2):
-        """One classifier step and one generator step (:277-288) on image batches in internal form."""
-        out = self.d_step(x_lab, labels, x_unl)
-        out.update(self.g_step(x_unl2))
-        self.iteration += 1
-        return out
 
     # ---- the same from index batches into the bound uint8 set: the gathers run at the counter value of the step they feed
     def d_body_idx(self, i_lab, labels, i_unl):
@@ -334,16 +285,6 @@ class CifarSSLTrainer:
         return out
 
     # ---- evaluation on the averaged parameters (:132-133, :145, :148)
-    def _averaged(self, fn, averaged):
-        if averaged:
-            lib.alias_params({p: a for p, (_, a) in zip(self.d_opt.params, self.d_opt.avg_views())})
-        try:
-            with torch.no_grad():
-                return fn()
-        finally:
-            if averaged:
-                lib.delete_param_aliases()
-
     def predict(self, x, averaged=True):
         """Logits of the deterministic pass over images in the reference's orientation; averaged: every trained classifier parameter
         replaced by its average (`givens`, :145) - the g of layers 1-9 are not trained, have no average and stay live."""
@@ -424,6 +365,15 @@ class CifarSSLData:
         s = slice(t * self.batch_size, (t + 1) * self.batch_size)
         return self.i_lab[s], self.y_lab[s], self.i_unl[s], self.i_unl2[s]
 
+    def test_set(self):
+        return self.test_x, self.test_y
+
+
+def init_from_stream(trainer, data):
+    """The data-dependent init on the padded images of data.init_indices() (:205; after the first begin_epoch())."""
+    idx = torch.from_numpy(np.ascontiguousarray(data.init_indices())).to(trainer.dev)
+    trainer.init_params(trainer.gather_fixed(idx, cfg.IMG + 2 * cfg.PAD, (0, 0)))
+
 
 def train(data_dir=None, epochs=None, seed=None, seed_data=None, use_graphs=True, out_dir=None, resume=None, checkpoint_every=1, log=print,
           max_batches=None, arrays=None):
@@ -433,48 +383,8 @@ def train(data_dir=None, epochs=None, seed=None, seed_data=None, use_graphs=True
     the averaged parameters, and the script's report line (also one record of train_log.Series in `out_dir`/log.jsonl).  A checkpoint
     (checkpoint.py) is written to `out_dir` every `checkpoint_every` epochs; `resume` continues from one at the epoch it was written.
     max_batches: shorten the epochs (smoke runs).  Returns the trainer."""
-    import time
-
-    from . import checkpoint
     from .engine import GraphedCifarSSLTrainer
-    from .train_log import Series
     data = CifarSSLData(data_dir, seed=seed, seed_data=seed_data, arrays=arrays)
     lib.delete_all_params()
-    trainer = CifarSSLTrainer(seed=seed, data=data.train_x)
-    dev = trainer.dev
-    start = 0
-    if resume:
-        start = checkpoint.load(resume, trainer)
-    for _ in range(start):             # the host streams of the epochs already run
-        data.begin_epoch()
-    eng = None
-    series = Series(os.path.join(out_dir, 'log.jsonl') if out_dir else None, echo=None)
-    series.iteration = start
-    for epoch in range(start, cfg.EPOCHS if epochs is None else epochs):
-        begin = time.time()
-        n = data.begin_epoch()
-        n = n if max_batches is None else min(n, max_batches)
-        if epoch == 0:
-            idx = torch.from_numpy(np.ascontiguousarray(data.init_indices())).to(dev)
-            trainer.init_params(trainer.gather_fixed(idx, cfg.IMG + 2 * cfg.PAD, (0, 0)))
-        if eng is None:
-            eng = GraphedCifarSSLTrainer(trainer, use_graphs=use_graphs)
-        outs, gen_loss = [], []
-        for t in range(n):
-            i_lab, y, i_unl, i_unl2 = data.batch(t)
-            out = eng.train_iteration(torch.from_numpy(i_lab), torch.from_numpy(y), torch.from_numpy(i_unl), torch.from_numpy(i_unl2))
-            outs.append(torch.stack([out['loss_lab'], out['loss_unl'], out['train_err'], out['train_err2']]))
-            gen_loss.append(out['loss_gen'].clone())
-        m = torch.stack(outs).cpu().numpy().mean(0)
-        gl = float(torch.stack(gen_loss).sum().item())
-        test_err = trainer.test_error(data.test_x, data.test_y)
-        log("Iteration %d, time = %ds, loss_lab = %.4f, loss_unl = %.4f, train err = %.4f, train err2 = %.4f,gen loss = %.4f,test err = %.4f"
-            % (epoch, time.time() - begin, m[0], m[1], m[2], m[3], gl, test_err))
-        for k, v in (('loss_lab', m[0]), ('loss_unl', m[1]), ('train err', m[2]), ('train err2', m[3]), ('gen loss', gl),
-                     ('test err', test_err), ('time', time.time() - begin)):
-            series.add(k, v)
-        series.tick()
-        series.flush()
-        if out_dir and checkpoint_every and (epoch + 1) % checkpoint_every == 0:
-            checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, epoch + 1)
-    return trainer
+    return ct_common.train_loop(CifarSSLTrainer(seed=seed, data=data.train_x), data, GraphedCifarSSLTrainer, init_from_stream, epochs, use_graphs,
+                                out_dir, resume, checkpoint_every, log, max_batches)

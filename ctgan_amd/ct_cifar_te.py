@@ -55,12 +55,10 @@ Configuration.  ct_cifar's network functions read `ct_cifar.cfg`; this module's 
 the construction of a trainer) installs it there, so that both modules see one object.  ct_cifar.configure() puts that module's own
 back.
 """
-import os
-
-import numpy as np
 import torch
 
 from . import ct_cifar as C
+from . import ct_common
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
@@ -74,12 +72,6 @@ class Config(C.Config):
     FACTOR_M = 0.0
     FEAT_WEIGHT = 0.1
     PREDICTION_DECAY = 0.6
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            if not hasattr(Config, k):
-                raise AttributeError('unknown hyper-parameter %s' % k)
-            setattr(self, k, v)
 
 
 cfg = Config()
@@ -95,16 +87,20 @@ def configure(**kw):
 
 class CifarTETrainer(CifarSSLTrainer):
     """train_batch_disc / train_batch_gen (:143, :157), init_param (:142), test_batch (:144) and the six tables of the loop.  Batches
-    in the internal form of ct_cifar.CifarSSLTrainer; `i_unl` (int32, device) names the table rows of the unlabelled batch."""
+    in the internal form of ct_cifar.CifarSSLTrainer; `i_unl` (int32, device) names the table rows of the unlabelled batch: a
+    classifier batch is (x_lab, labels, x_unl, i_unl), train_iteration (:289-299) takes it followed by x_unl2."""
+    D_KEYS = ('out8', 'loss_lab', 'loss_unl', 'loss_ct', 'train_err', 'train_err2', 'ct', 'ctf')
+    REPORT = ('Epoch',) + CifarSSLTrainer.REPORT[1:]
 
     def __init__(self, seed=None, data=None):
         C.cfg = cfg
         self.epoch = 0
         self.ensemble = self.ensemble2 = self.targets = self.targets2 = self.epoch_pred = self.epoch_pred2 = None
         super().__init__(seed=seed, data=data)
-        # cotangents of out8 = {loss_lab, loss_unl, CT_, train_err, train_err2, mean ct, mean ctf, 0}: cost = loss_lab + UNLABELED_WEIGHT loss_unl (:138)
-        self.d_seed = torch.tensor([1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=self.dev)
-        self.d_seed2 = None
+
+    def d_cotangents(self):
+        """out8 = {loss_lab, loss_unl, CT_, train_err, train_err2, mean ct, mean ctf, 0}: cost = loss_lab + UNLABELED_WEIGHT loss_unl (:138)"""
+        return {'out8': [1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]}
 
     # ---- the device-resident set and the tables over it (:177-180, :273-274)
     def bind_data(self, images_u8):
@@ -133,28 +129,6 @@ class CifarTETrainer(CifarSSLTrainer):
                          cfg.FEAT_WEIGHT, cfg.FACTOR_M)
         return {'out8': out8, 'loss_lab': out8[0], 'loss_unl': out8[1], 'loss_ct': out8[2], 'train_err': out8[3], 'train_err2': out8[4],
                 'ct': out8[5], 'ctf': out8[6], 'logits': logits, 'features': feat}
-
-    def d_grads(self, x_lab, labels, x_unl, i_unl):
-        out = self.d_losses(x_lab, labels, x_unl, i_unl)
-        grads = torch.autograd.grad([out['out8']], self.d_params, grad_outputs=[self.d_seed], allow_unused=True)
-        return out, grads
-
-    def d_body(self, x_lab, labels, x_unl, i_unl):
-        """Losses (with the table gather and scatter), gradients, Adam + average, end of step - everything a replayed graph holds."""
-        out, grads = self.d_grads(x_lab, labels, x_unl, i_unl)
-        self.d_opt.update(grads, rng=self.rng)
-        return {k: out[k].detach() for k in ('out8', 'loss_lab', 'loss_unl', 'loss_ct', 'train_err', 'train_err2', 'ct', 'ctf')}
-
-    def d_step(self, x_lab, labels, x_unl, i_unl):
-        self.d_opt.set_lr(self.lr())
-        return self.d_body(x_lab, labels, x_unl, i_unl)
-
-    def train_iteration(self, x_lab, labels, x_unl, i_unl, x_unl2):
-        """One classifier step and one generator step (:289-299) on image batches in internal form."""
-        out = self.d_step(x_lab, labels, x_unl, i_unl)
-        out.update(self.g_step(x_unl2))
-        self.iteration += 1
-        return out
 
     # ---- the same from index batches: i_unl feeds the gather and names the table rows
     def d_body_idx(self, i_lab, labels, i_unl):
@@ -186,6 +160,13 @@ class CifarTETrainer(CifarSSLTrainer):
         self.epoch_pred2.zero_()
         self.epoch = int(state['te_epoch'])
 
+    checkpoint_extra = te_state
+
+    def restore_extra(self, path, epoch):
+        from . import checkpoint
+        self.load_te_state(checkpoint.load_extra(path))
+        assert self.epoch == epoch, 'the checkpoint was not written at an epoch boundary'
+
 
 def train(data_dir=None, epochs=None, seed=None, seed_data=None, use_graphs=True, out_dir=None, resume=None, checkpoint_every=1, log=print,
           max_batches=None, arrays=None):
@@ -197,52 +178,9 @@ def train(data_dir=None, epochs=None, seed=None, seed_data=None, use_graphs=True
     (checkpoint.py, the tables in its `extra`) is written to `out_dir` every `checkpoint_every` epochs; `resume` continues from one
     at the epoch it was written.  max_batches: shorten the epochs (smoke runs; unvisited rows then decay, as in the script).
     Returns the trainer."""
-    import time
-
-    from . import checkpoint
     from .engine import GraphedCifarTETrainer
-    from .train_log import Series
     C.cfg = cfg
     data = CifarSSLData(data_dir, seed=seed, seed_data=seed_data, arrays=arrays)
     lib.delete_all_params()
-    trainer = CifarTETrainer(seed=seed, data=data.train_x)
-    dev = trainer.dev
-    start = 0
-    if resume:
-        start = checkpoint.load(resume, trainer)
-        trainer.load_te_state(checkpoint.load_extra(resume))
-        assert trainer.epoch == start, 'the checkpoint was not written at an epoch boundary'
-    for _ in range(start):             # the host streams of the epochs already run
-        data.begin_epoch()
-    eng = None
-    series = Series(os.path.join(out_dir, 'log.jsonl') if out_dir else None, echo=None)
-    series.iteration = start
-    for epoch in range(start, cfg.EPOCHS if epochs is None else epochs):
-        begin = time.time()
-        n = data.begin_epoch()
-        n = n if max_batches is None else min(n, max_batches)
-        if epoch == 0:
-            idx = torch.from_numpy(np.ascontiguousarray(data.init_indices())).to(dev)
-            trainer.init_params(trainer.gather_fixed(idx, cfg.IMG + 2 * cfg.PAD, (0, 0)))
-        if eng is None:
-            eng = GraphedCifarTETrainer(trainer, use_graphs=use_graphs)
-        outs, gen_loss = [], []
-        for t in range(n):
-            i_lab, y, i_unl, i_unl2 = data.batch(t)
-            out = eng.train_iteration(torch.from_numpy(i_lab), torch.from_numpy(y), torch.from_numpy(i_unl), torch.from_numpy(i_unl2))
-            outs.append(torch.stack([out['loss_lab'], out['loss_unl'], out['train_err'], out['train_err2']]))
-            gen_loss.append(out['loss_gen'].clone())
-        trainer.end_epoch()
-        m = torch.stack(outs).cpu().numpy().mean(0)
-        gl = float(torch.stack(gen_loss).sum().item())
-        test_err = trainer.test_error(data.test_x, data.test_y)
-        log("Epoch %d, time = %ds, loss_lab = %.4f, loss_unl = %.4f, train err = %.4f, train err2 = %.4f,gen loss = %.4f,test err = %.4f"
-            % (epoch, time.time() - begin, m[0], m[1], m[2], m[3], gl, test_err))
-        for k, v in (('loss_lab', m[0]), ('loss_unl', m[1]), ('train err', m[2]), ('train err2', m[3]), ('gen loss', gl),
-                     ('test err', test_err), ('time', time.time() - begin)):
-            series.add(k, v)
-        series.tick()
-        series.flush()
-        if out_dir and checkpoint_every and (epoch + 1) % checkpoint_every == 0:
-            checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, epoch + 1, extra=trainer.te_state())
-    return trainer
+    return ct_common.train_loop(CifarTETrainer(seed=seed, data=data.train_x), data, GraphedCifarTETrainer, C.init_from_stream, epochs, use_graphs,
+                                out_dir, resume, checkpoint_every, log, max_batches)

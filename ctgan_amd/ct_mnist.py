@@ -37,15 +37,14 @@ import os
 import numpy as np
 import torch
 
+from . import ct_common
 from . import functional as F
 from . import tflib as lib
-from .optim import FlatAdamTheano
-from .rng import DeviceRNG
 from .tflib.ops import linear as _linear
 from .tflib.ops import wn_dense as _wn
 
 
-class Config:
+class Config(ct_common.Config):
     """The literals of TH/CT_MNIST.py:14-22, 33-53, 103-105, 140-141 (tests shrink the five shape entries)."""
     Factor_M = 0.0
     LAMBDA_2 = 0.1
@@ -67,12 +66,6 @@ class Config:
     N_CLASSES = 10
     Z_DIM = 100
     G_HIDDEN = (500, 500)
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            if not hasattr(Config, k):
-                raise AttributeError('unknown hyper-parameter %s' % k)
-            setattr(self, k, v)
 
 
 cfg = Config()
@@ -125,25 +118,19 @@ def build_params():
         Classifier(Generator(2, noise=torch.zeros(2, cfg.Z_DIM, device=lib._dev())), deterministic=True)
 
 
-class SSLTrainer:
-    """The two Theano functions train_batch_disc / train_batch_gen (:110-111), init_param (:109) and test_batch (:112)."""
+class SSLTrainer(ct_common.SSLTrainerBase):
+    """The two Theano functions train_batch_disc / train_batch_gen (:110-111), init_param (:109) and test_batch (:112); a classifier
+    batch is (x_lab, labels, x_unl), train_iteration (:161-166) takes it followed by x_unl2."""
+    cfg = property(lambda self: cfg)
+    D_KEYS = ('out4', 'loss_lab', 'loss_unl', 'ct', 'train_err', 'ct_i')
+    REPORT = ('Iteration', (('loss_lab', 'loss_lab'), ('loss_unl', 'loss_unl'), ('train err', 'train_err')), ())
 
     def __init__(self, seed=None):
-        self.dev = lib._dev()
-        self.rng = DeviceRNG(cfg.SEED if seed is None else seed, 0, self.dev)
-        build_params()
-        self.d_named = lib.named_params_with_name('Classifier', trainable_only=True)
-        self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
-        self.d_params = [p for _, p in self.d_named]
-        self.g_params = [p for _, p in self.g_named]
-        self.d_opt = FlatAdamTheano(self.d_named, cfg.BETA1, cfg.BETA2, avg_rate=cfg.AVG_RATE)
-        self.g_opt = FlatAdamTheano(self.g_named, cfg.BETA1, cfg.BETA2, avg_rate=0.0)
-        # cotangent of the loss head's {loss_lab, loss_unl, CT, train_err}: cost = loss_lab + UNLABELED_WEIGHT loss_unl (:103)
-        self.d_seed = torch.tensor([1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0], dtype=torch.float32, device=self.dev)
-        self.iteration = 0
+        super().__init__(build_params, seed)
 
-    def lr(self):
-        return cfg.LR
+    def d_cotangents(self):
+        """out4 = {loss_lab, loss_unl, CT, train_err}: cost = loss_lab + UNLABELED_WEIGHT loss_unl (:103)"""
+        return {'out4': [1.0, cfg.UNLABELED_WEIGHT, 0.0, 0.0]}
 
     # ---- data-dependent init (:60-62, :137)
     def init_params(self, x):
@@ -163,21 +150,6 @@ class SSLTrainer:
         out4, ct_i = F.ssl_head(logits, labels, B, cfg.LAMBDA_2, cfg.Factor_M)
         return {'out4': out4, 'loss_lab': out4[0], 'loss_unl': out4[1], 'ct': out4[2], 'train_err': out4[3], 'ct_i': ct_i, 'logits': logits}
 
-    def d_grads(self, x_lab, labels, x_unl):
-        out = self.d_losses(x_lab, labels, x_unl)
-        grads = torch.autograd.grad(out['out4'], self.d_params, grad_outputs=self.d_seed, allow_unused=True)
-        return out, grads
-
-    def d_body(self, x_lab, labels, x_unl):
-        """Losses, gradients, Adam + average, end of step - everything a replayed graph holds (the learning rate is device state)."""
-        out, grads = self.d_grads(x_lab, labels, x_unl)
-        self.d_opt.update(grads, rng=self.rng)
-        return {k: out[k].detach() for k in ('out4', 'loss_lab', 'loss_unl', 'ct', 'train_err', 'ct_i')}
-
-    def d_step(self, x_lab, labels, x_unl):
-        self.d_opt.set_lr(self.lr())
-        return self.d_body(x_lab, labels, x_unl)
-
     # ---- generator step
     def g_losses(self, x_unl):
         B = x_unl.shape[0]
@@ -186,39 +158,11 @@ class SSLTrainer:
         feats = Classifier(torch.cat([fake, x_unl], 0), rng=self.rng, features=True, frozen=True)
         return {'loss_gen': F.feature_matching(feats, B)}
 
-    def g_grads(self, x_unl):
-        out = self.g_losses(x_unl)
-        grads = torch.autograd.grad(out['loss_gen'], self.g_params, allow_unused=True)
-        return out, grads
-
-    def g_body(self, x_unl):
-        out, grads = self.g_grads(x_unl)
-        self.g_opt.update(grads, rng=self.rng)
-        return {'loss_gen': out['loss_gen'].detach()}
-
-    def g_step(self, x_unl):
-        self.g_opt.set_lr(self.lr())
-        return self.g_body(x_unl)
-
-    def train_iteration(self, x_lab, labels, x_unl, x_unl2):
-        """One classifier step and one generator step (:161-166)."""
-        out = self.d_step(x_lab, labels, x_unl)
-        out.update(self.g_step(x_unl2))
-        self.iteration += 1
-        return out
-
     # ---- evaluation on the averaged parameters (:97-98, :106, :112)
     def predict(self, x, averaged=True):
         """Logits of the deterministic pass; averaged: every trained classifier parameter replaced by its average (`givens`, :106) -
         the weight scales of layers 1-5 are not trained, have no average and stay live."""
-        if averaged:
-            lib.alias_params({p: a for p, (_, a) in zip(self.d_opt.params, self.d_opt.avg_views())})
-        try:
-            with torch.no_grad():
-                return Classifier(x, deterministic=True)
-        finally:
-            if averaged:
-                lib.delete_param_aliases()
+        return self._averaged(lambda: Classifier(x, deterministic=True), averaged)
 
     def test_error(self, x, y, averaged=True, batch_size=None):
         """Mean over whole batches of the per-batch argmax error (:173-176)."""
@@ -278,6 +222,9 @@ class SSLData:
         s = slice(t * self.batch_size, (t + 1) * self.batch_size)
         return self.lab_x[s], self.lab_y[s], self.unl[s], self.unl2[s]
 
+    def test_set(self):
+        return self.testx, self.testy
+
 
 def train(data_path, epochs=None, seed=None, seed_data=None, use_graphs=True, out_dir=None, resume=None, checkpoint_every=1, log=print,
           max_batches=None):
@@ -287,42 +234,8 @@ def train(data_path, epochs=None, seed=None, seed_data=None, use_graphs=True, ou
     (checkpoint.py: parameters, both Adam states with the averages, the random-stream counters) is written to `out_dir` every
     `checkpoint_every` epochs; `resume` continues from one at the epoch it was written.  max_batches: shorten the epochs (smoke runs).
     Returns the trainer."""
-    import time
-
-    from . import checkpoint
     from .engine import GraphedSSLTrainer
-    from .train_log import Series
     data = SSLData(data_path, seed=seed, seed_data=seed_data)
     lib.delete_all_params()
-    trainer = SSLTrainer(seed=seed)
-    dev = trainer.dev
-    start = 0
-    if resume:
-        start = checkpoint.load(resume, trainer)
-    else:
-        trainer.init_params(torch.from_numpy(data.init_batch).to(dev))
-    eng = GraphedSSLTrainer(trainer, use_graphs=use_graphs)
-    series = Series(os.path.join(out_dir, 'log.jsonl') if out_dir else None, echo=None)
-    for _ in range(start):             # the host streams of the epochs already run
-        data.begin_epoch()
-    series.iteration = start
-    for epoch in range(start, cfg.EPOCHS if epochs is None else epochs):
-        begin = time.time()
-        n = data.begin_epoch()
-        n = n if max_batches is None else min(n, max_batches)
-        outs = []
-        for t in range(n):
-            x_lab, y, x_unl, x_unl2 = data.batch(t)
-            out = eng.train_iteration(torch.from_numpy(x_lab), torch.from_numpy(y), torch.from_numpy(x_unl), torch.from_numpy(x_unl2))
-            outs.append(out['out4'].clone())
-        m = torch.stack(outs).cpu().numpy().mean(0)
-        test_err = trainer.test_error(data.testx, data.testy)
-        log("Iteration %d, time = %ds, loss_lab = %.4f, loss_unl = %.4f, train err = %.4f, test err = %.4f"
-            % (epoch, time.time() - begin, m[0], m[1], m[3], test_err))
-        for k, v in (('loss_lab', m[0]), ('loss_unl', m[1]), ('train err', m[3]), ('test err', test_err), ('time', time.time() - begin)):
-            series.add(k, v)
-        series.tick()
-        series.flush()
-        if out_dir and checkpoint_every and (epoch + 1) % checkpoint_every == 0:
-            checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, epoch + 1)
-    return trainer
+    return ct_common.train_loop(SSLTrainer(seed=seed), data, GraphedSSLTrainer, lambda tr, d: tr.init_params(torch.from_numpy(d.init_batch).to(tr.dev)),
+                                epochs, use_graphs, out_dir, resume, checkpoint_every, log, max_batches)

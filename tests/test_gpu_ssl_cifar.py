@@ -118,7 +118,7 @@ def test_map_init_on_a_channels_last_map(K):
         K.wn_init_map(dev(y), sd, bd, 'lrelu', 0.2, 1.0)           # an NCHW map is not what the kernel indexes
 
 
-@pytest.mark.parametrize('B,Fd', [(100, 128), (3, 5), (4, 32)])
+@pytest.mark.parametrize('B,Fd', [(100, 128), (3, 5), (4, 32), (7, 67)])      # (7, 67): a ragged second column tile, rows < row slices
 def test_loss_pieces_fwd_bwd(K, B, Fd):
     g = torch.Generator().manual_seed(B + Fd)
     f = torch.randn(4 * B, Fd, generator=g)
