@@ -64,7 +64,8 @@ struct LReluB { float a; __device__ float operator()(float g, float r) const { r
 struct LReluBS { float a, sc; __device__ float operator()(float g, float r) const { return (r > 0.f ? g : a * g) * sc; } };
 struct MulF { __device__ float operator()(float x, float y) const { return x * y; } };
 struct RsqrtF { float eps; __device__ float operator()(float x) const { return 1.f / sqrtf(x + eps); } };
-struct DropF { float keep, inv; __device__ float operator()(float x, float u) const { return x * inv * floorf(keep + u); } };
+// keep = 1 keeps every element: floorf(1.0f + u) is 2 for u = 1 - 2^-24 (csrc/philox.h keep_mask)
+struct DropF { float keep, inv; __device__ float operator()(float x, float u) const { return x * inv * (keep < 1.f ? floorf(keep + u) : 1.f); } };
 struct TanhF { __device__ float operator()(float x) const { return tanhf(x); } };
 struct TanhB { __device__ float operator()(float g, float y) const { return g * (1.f - y * y); } };
 struct SigF { __device__ float operator()(float x) const { return 1.f / (1.f + expf(-x)); } };

@@ -192,13 +192,13 @@ __global__ void dropout_rng_kernel(const float* __restrict__ x, float* __restric
         if (vec && i + 3 < n) {
             const float4 v = *reinterpret_cast<const float4*>(x + i);
             float4 o;
-            o.x = v.x * inv * floorf(keep + u01(c[0])); o.y = v.y * inv * floorf(keep + u01(c[1]));
-            o.z = v.z * inv * floorf(keep + u01(c[2])); o.w = v.w * inv * floorf(keep + u01(c[3]));
+            o.x = v.x * inv * keep_mask(keep, u01(c[0])); o.y = v.y * inv * keep_mask(keep, u01(c[1]));
+            o.z = v.z * inv * keep_mask(keep, u01(c[2])); o.w = v.w * inv * keep_mask(keep, u01(c[3]));
             *reinterpret_cast<float4*>(y + i) = o;
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (i + k < n) y[i + k] = x[i + k] * inv * floorf(keep + u01(c[k]));
+                if (i + k < n) y[i + k] = x[i + k] * inv * keep_mask(keep, u01(c[k]));
         }
     }
 }
@@ -223,13 +223,13 @@ __global__ void lrelu_dropout_rng_kernel(const float* __restrict__ x, const floa
             const float4 v = *reinterpret_cast<const float4*>(x + i);
             const float4 r = *reinterpret_cast<const float4*>(ref + i);
             float4 o;
-            o.x = v.x * (r.x > 0.f ? 1.f : alpha) * inv * floorf(keep + u01(c[0])); o.y = v.y * (r.y > 0.f ? 1.f : alpha) * inv * floorf(keep + u01(c[1]));
-            o.z = v.z * (r.z > 0.f ? 1.f : alpha) * inv * floorf(keep + u01(c[2])); o.w = v.w * (r.w > 0.f ? 1.f : alpha) * inv * floorf(keep + u01(c[3]));
+            o.x = v.x * (r.x > 0.f ? 1.f : alpha) * inv * keep_mask(keep, u01(c[0])); o.y = v.y * (r.y > 0.f ? 1.f : alpha) * inv * keep_mask(keep, u01(c[1]));
+            o.z = v.z * (r.z > 0.f ? 1.f : alpha) * inv * keep_mask(keep, u01(c[2])); o.w = v.w * (r.w > 0.f ? 1.f : alpha) * inv * keep_mask(keep, u01(c[3]));
             *reinterpret_cast<float4*>(y + i) = o;
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (i + k < n) y[i + k] = x[i + k] * (ref[i + k] > 0.f ? 1.f : alpha) * inv * floorf(keep + u01(c[k]));
+                if (i + k < n) y[i + k] = x[i + k] * (ref[i + k] > 0.f ? 1.f : alpha) * inv * keep_mask(keep, u01(c[k]));
         }
     }
 }
@@ -251,8 +251,8 @@ __global__ void dropout_rng_mask_kernel(const float* __restrict__ x, const float
             const float4 v = *reinterpret_cast<const float4*>(x + i);
             const float4 r = *reinterpret_cast<const float4*>(ref + i);
             float4 o;
-            o.x = v.x * inv * floorf(keep + u01(c[0])); o.y = v.y * inv * floorf(keep + u01(c[1]));
-            o.z = v.z * inv * floorf(keep + u01(c[2])); o.w = v.w * inv * floorf(keep + u01(c[3]));
+            o.x = v.x * inv * keep_mask(keep, u01(c[0])); o.y = v.y * inv * keep_mask(keep, u01(c[1]));
+            o.z = v.z * inv * keep_mask(keep, u01(c[2])); o.w = v.w * inv * keep_mask(keep, u01(c[3]));
             if (y) *reinterpret_cast<float4*>(y + i) = o;
             o.x = r.x > 0.f ? o.x : 0.f; o.y = r.y > 0.f ? o.y : 0.f; o.z = r.z > 0.f ? o.z : 0.f; o.w = r.w > 0.f ? o.w : 0.f;
             *reinterpret_cast<float4*>(ym + i) = o;
@@ -260,7 +260,7 @@ __global__ void dropout_rng_mask_kernel(const float* __restrict__ x, const float
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (i + k < n) {
-                    const float o = x[i + k] * inv * floorf(keep + u01(c[k]));
+                    const float o = x[i + k] * inv * keep_mask(keep, u01(c[k]));
                     if (y) y[i + k] = o;
                     ym[i + k] = ref[i + k] > 0.f ? o : 0.f;
                 }
@@ -556,7 +556,7 @@ int ctgan_rng_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, c
 }
 int ctgan_rng_labels(int32_t* out, int64_t n, int32_t nlab, uint64_t seed, uint64_t stream_id, const uint64_t* ctr,
                      ctgan_stream_t s) {
-    if (!out || n < 0 || nlab <= 0) return ctgan_fail(CTGAN_E_BADARG, "rng_labels: bad argument");
+    if (!out || n < 0 || n >= (1LL << 34) || nlab <= 0) return ctgan_fail(CTGAN_E_BADARG, "rng_labels: bad argument");
     if (n == 0) return CTGAN_OK;
     hipLaunchKernelGGL(rng_labels_kernel, dim3(ctgan_blocks((n + 3) / 4, 256, 2048)), dim3(256), 0,
                        static_cast<hipStream_t>(s), out, (long long)n, nlab, seed, (uint32_t)stream_id, ctr);

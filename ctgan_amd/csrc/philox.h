@@ -25,4 +25,7 @@ __device__ __forceinline__ void draw4(uint64_t seed, uint32_t sid, uint64_t step
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }   // [0,1), 24 bits
+// tf.nn.dropout's keep mask floor(keep + u) for keep in (0,1].  keep = 1 keeps every element: 1.0f + (1 - 2^-24), the largest u01, rounds
+// to 2.0f and would double it.  Below 1 the sum stays under 2 and this is floorf(keep + u) unchanged.
+__device__ __forceinline__ float keep_mask(float keep, float u) { return keep < 1.f ? floorf(keep + u) : 1.f; }
 }  // namespace ctgan_philox

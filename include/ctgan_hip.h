@@ -309,7 +309,9 @@ int ctgan_lrelu_bwd(const float* gy, const float* ref, float* gx, int64_t n, flo
 int ctgan_lrelu_bwd_scaled(const float* gy, const float* ref, float* gx, int64_t n, float alpha, float scale,
                            ctgan_stream_t stream);
 /* tf.nn.dropout: y = x/keep * floor(keep + u)  (TF/CT_gan_cifar_resnet.py:173-177); the
- * backward is the same call on the gradient.                                                  */
+ * backward is the same call on the gradient.  keep in (0,1]; keep = 1 returns x itself
+ * (floor(1 + u) would be 2 in float for u = 1 - 2^-24, the largest uniform draw) - here and
+ * in the ctgan_*dropout_rng* entry points.                                                    */
 int ctgan_dropout(const float* x, const float* u, float* y, int64_t n, float keep,
                   ctgan_stream_t stream);
 int ctgan_tanh_fwd(const float* x, float* y, int64_t n, ctgan_stream_t stream);

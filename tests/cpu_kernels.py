@@ -269,6 +269,8 @@ def lrelu_bwd(gy, ref, alpha, scale=1.0):
 
 @_export
 def dropout(x, u, keep):
+    if keep >= 1.0:                      # floor(1.0f + u) is 2 for u = 1 - 2^-24: keep = 1 keeps every element as it is
+        return _like(x, x)
     return _like(x / keep * torch.floor(keep + u), x)
 
 
@@ -863,20 +865,22 @@ def rows_cat_dropout(x, n_extra, keep, seed, stream_id, ctr):
 
 @_export
 def rows_gather_dropout(src, segs, seed, ctr):
-    parts, groups = [], {}
-    row = 0
+    from oracle import philox
+    parts, row = [], 0
+    row_elems = src.numel() // src.shape[0]
     for r0, rows, keep, sid, idx0 in segs:
-        parts.append(src[r0:r0 + rows])
-        groups.setdefault((idx0, keep, sid), []).append((row, rows))
+        part = src[r0:r0 + rows]
+        if src.dim() == 4:
+            part = part.contiguous(memory_format=torch.channels_last)
+        if keep < 1.0:                   # the stream index of an element is its index in the result relative to result row idx0
+            u = torch.empty_strided(part.shape, part.stride(), dtype=part.dtype)
+            _storage_order(u).copy_(torch.from_numpy(philox.uniform(int(seed), int(sid), _step_of(ctr), part.numel(),
+                                                                    first=(row - idx0) * row_elems)))
+            part = dropout(part, u, keep)
+        parts.append(part)
         row += rows
     y = torch.cat(parts, 0)
-    if src.dim() == 4:
-        y = y.contiguous(memory_format=torch.channels_last)
-    for (idx0, keep, sid), rs in groups.items():
-        if keep < 1.0:
-            end = max(a + b for a, b in rs)
-            y[idx0:end] = dropout_rng(y[idx0:end], keep, seed, sid, ctr)     # segments of a group are adjacent
-    return y
+    return y.contiguous(memory_format=torch.channels_last) if src.dim() == 4 else y
 
 
 @_export

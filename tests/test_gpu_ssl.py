@@ -67,7 +67,13 @@ def test_weight_norm_fwd_bwd(K, n_in, n_out, eps):
 
 @pytest.mark.parametrize('rows,cols,row_offset', [(401, 1000, 0), (37, 10, 0), (37, 10, 5), (13, 3, 7), (100, 784, 300), (5, 7, 1)])
 def test_dense_epilogue_draws_the_documented_stream(K, rows, cols, row_offset):
-    seed, sid, step, sigma = 1234567891011, 6, 3, 0.5
+    # the second stream is corner B of tests/philox_spec.py: high key word, rank bits of the stream id and counter word 3 all non-zero
+    for seed, sid, step in ((1234567891011, 6, 3), (0x9E3779B97F4A7C15, (513 << 16) | 7, (1 << 32) + 5)):
+        _dense_epilogue_on_stream(K, rows, cols, row_offset, seed, sid, step)
+
+
+def _dense_epilogue_on_stream(K, rows, cols, row_offset, seed, sid, step):
+    sigma = 0.5
     g = torch.Generator().manual_seed(rows + cols)
     y = torch.randn(rows, cols, generator=g)
     b = torch.randn(cols, generator=g)

@@ -226,10 +226,15 @@ def test_gather_fixed_windows_equal_numpy(K, win, flip):
 
 
 def test_gather_draws_are_the_documented_stream(K):
+    # the second stream is corner B of tests/philox_spec.py: high key word, rank bits of the stream id and counter word 3 all non-zero
+    for seed, sid, step in ((1234567891011, 17, 6), (0x9E3779B97F4A7C15, (513 << 16) | 7, (1 << 32) + 5)):
+        _gather_draws_on_stream(K, seed, sid, step)
+
+
+def _gather_draws_on_stream(K, seed, sid, step):
     data, idx = _gather_data()
     lut = dev(torch.from_numpy(O.byte_table()))
     dd, di = dev(torch.from_numpy(data)), dev(torch.from_numpy(idx))
-    seed, sid, step = 1234567891011, 17, 6
     ctr = torch.tensor([step], dtype=torch.int64, device='cuda')
     u = philox.uniform(seed, sid, step, 3 * B_G).reshape(B_G, 3)
     draws = (u[:, 0] > 0.5, np.minimum((5 * u[:, 1]).astype(int), 4), np.minimum((5 * u[:, 2]).astype(int), 4))
