@@ -162,6 +162,16 @@ SIGNATURES = {
     'ctgan_bn_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32,
                              c_int32, _p, c_size_t, _p]),
     'ctgan_bn_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    # score classifier (csrc/bn.hip, csrc/score.hip)
+    'ctgan_bn_stats_moving': (c_int, [_p, c_int32, c_int32, c_int32, c_float, _p, _p, _p, _p, _p, _p, c_size_t, _p]),
+    'ctgan_bn_blend_stats': (c_int, [_p, c_int32, c_int32, c_int32, c_float, _p, _p, _p, _p, _p, c_size_t, _p]),
+    'ctgan_bn_apply_ex': (c_int, [_p, _p, _p, c_int32, _p, _p, _p, c_float, _p, _p, c_int32, c_int32, c_int32, c_int32, _p]),
+    'ctgan_bn_bwd_scaled': (c_int, [_p, _p, _p, _p, _p, _p, c_float, _p, _p, _p, c_int32, c_int32, c_int32, _p, c_size_t, _p]),
+    'ctgan_elu_fwd': (c_int, [_p, _p, c_int64, _p]),
+    'ctgan_elu_bwd': (c_int, [_p, _p, _p, _p, c_int64, _p]),
+    'ctgan_global_norm_workspace_bytes': (c_size_t, [c_int64]),
+    'ctgan_global_norm': (c_int, [_p, c_int64, _p, _p, c_size_t, _p]),
+    'ctgan_clip_by_norm': (c_int, [_p, c_int64, _p, c_float, _p]),
     'ctgan_gp_fwd': (c_int, [_p, c_int32, c_int32, c_float, _p, _p, _p]),
     'ctgan_gp_bwd': (c_int, [_p, _p, _p, c_int32, c_int32, c_float, _p, _p]),
     'ctgan_ct_fwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_float, c_float, _p, _p, _p]),

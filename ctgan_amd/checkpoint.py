@@ -19,9 +19,9 @@ def save(path, trainer, iteration, extra=None):
         'iteration': int(iteration),
         'params': lib.state_dict(),
         'd_opt': trainer.d_opt.state_dict(),
-        'g_opt': trainer.g_opt.state_dict(),
+        'g_opt': trainer.g_opt.state_dict() if trainer.g_opt is not None else None,        # (score_mnist: one optimizer, no stream)
         'rng': {'seed': trainer.rng.seed, 'rank': trainer.rng.rank, 'ctr': int(trainer.rng.ctr.item()),
-                'eval_ctr': int(eval_stream(trainer).ctr.item())},
+                'eval_ctr': int(eval_stream(trainer).ctr.item())} if trainer.rng is not None else None,
         'extra': extra or {},
     }, path)
 
@@ -34,10 +34,12 @@ def load(path, trainer):
         raise ValueError('unknown checkpoint format')
     lib.load_state_dict(ck['params'], strict=True)
     trainer.d_opt.load_state_dict(ck['d_opt'])
-    trainer.g_opt.load_state_dict(ck['g_opt'])
-    trainer.rng.seed = ck['rng']['seed']
-    trainer.rng.ctr.fill_(ck['rng']['ctr'])
-    eval_stream(trainer).ctr.fill_(ck['rng'].get('eval_ctr', 0))
+    if trainer.g_opt is not None:
+        trainer.g_opt.load_state_dict(ck['g_opt'])
+    if trainer.rng is not None:
+        trainer.rng.seed = ck['rng']['seed']
+        trainer.rng.ctr.fill_(ck['rng']['ctr'])
+        eval_stream(trainer).ctr.fill_(ck['rng'].get('eval_ctr', 0))
     return ck['iteration']
 
 

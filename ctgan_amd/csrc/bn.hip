@@ -169,7 +169,7 @@ __global__ __launch_bounds__(CB * RL) void bn_bwd_sample_kernel(const double* __
 __global__ __launch_bounds__(64 * 16) void bn_bwd_final_kernel(const double* __restrict__ tot, const float* __restrict__ scale,
                                                              const int32_t* __restrict__ labels, BnShape s, int n_labels,
                                                              float* __restrict__ gscale, float* __restrict__ goffset,
-                                                             float* __restrict__ s12) {
+                                                             float* __restrict__ s12, double gys, float* __restrict__ sga) {
     __shared__ double red[2][16][64];
     const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -204,12 +204,16 @@ __global__ __launch_bounds__(64 * 16) void bn_bwd_final_kernel(const double* __r
     a = 0.; b = 0.;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { a += red[0][r][cl]; b += red[1][r][cl]; }
+    // gys: the incoming gradient is gys * gy (ctgan_bn_bwd_scaled; 1 elsewhere - exact).  Every sum is linear in gy, so the factor
+    // goes on the totals, and the apply pass reads the gain from sga = gys * scale instead of scaling gy per element.
+    a *= gys; b *= gys;
     if (job < n_labels) {
         goffset[job * s.c + c] = (float)a; gscale[job * s.c + c] = (float)b;
     } else {
         const int g = job - n_labels;
         const double cnt = (double)per * s.hw;
         s12[(g * 2 + 0) * s.c + c] = (float)(a / cnt); s12[(g * 2 + 1) * s.c + c] = (float)(b / cnt);
+        if (sga) sga[c] = (float)gys * scale[c];
     }
 }
 
@@ -385,6 +389,135 @@ size_t part_bytes(const BnShape& s) { return (size_t)s.n * s.hc * 2 * s.c * size
 size_t tot_bytes(const BnShape& s) { return (size_t)s.n * 2 * s.c * sizeof(double); }
 size_t bins_bytes(const BnShape& s, int n_labels) { return (size_t)n_labels * 2 * s.c * sizeof(double); }
 
+// ---- the score classifier's batch norm (LS/tflib/ops/batchnorm.py:30-69; LS/ = tensorflow_generative_model/LSUN_bedrooms) ----------
+// Finalisation of the training statistics (one group) that also moves the moving statistics (:62-65):
+//   moving <- (it/(it+1)) moving + (1/(it+1)) batch     in fp32, `it` read from device memory (a replayed graph sees the current value)
+// batch_var is what tf.nn.fused_batch_norm returns in training: the biased variance * cnt/max(cnt-1, 1), taken from the fp64 sums.
+// Same summation order as bn_stats_final_kernel.  moving_mean == NULL: no update.
+__global__ __launch_bounds__(CB * FL) void bn_stats_final_moving_kernel(const double* __restrict__ part, BnShape s, float eps,
+                                                                       float* __restrict__ mean, float* __restrict__ rstd,
+                                                                       float* __restrict__ moving_mean, float* __restrict__ moving_var,
+                                                                       const float* __restrict__ it) {
+    __shared__ double red[2][FL][CB];
+    const int cl = threadIdx.x % CB, fl = threadIdx.x / CB;
+    const int c = blockIdx.x * CB + cl;
+    double a = 0., b = 0.;
+    if (c < s.c) {
+        const int i1 = s.n * s.hc;
+        for (int i = fl; i < i1; i += FL) {
+            a += part[(long long)i * 2 * s.c + c];
+            b += part[(long long)i * 2 * s.c + s.c + c];
+        }
+    }
+    red[0][fl][cl] = a; red[1][fl][cl] = b;
+    __syncthreads();
+    if (fl != 0 || c >= s.c) return;
+    a = 0.; b = 0.;
+#pragma unroll
+    for (int r = 0; r < FL; ++r) { a += red[0][r][cl]; b += red[1][r][cl]; }
+    const double cnt = (double)s.n * s.hw;
+    const double m = a / cnt;
+    double var = b / cnt - m * m;
+    if (var < 0.) var = 0.;
+    mean[c] = (float)m;
+    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (moving_mean) {
+        const float bm = (float)m, bv = (float)(var * (cnt / fmax(cnt - 1., 1.)));
+        const float fi = it[0];
+        const float wa = fi / (fi + 1.f), wb = 1.f / (fi + 1.f);
+        moving_mean[c] = wa * moving_mean[c] + wb * bm;
+        moving_var[c] = wa * moving_var[c] + wb * bv;
+    }
+}
+
+// Per-sample finalisation of the inference-mode "blend" (:32-38): the biased moments of sample n's plane c over h*w, from that sample's
+// rows of `part`, blended in fp32 with the moving statistics by the row count B = n of the call:
+//   mean = m/B + ((B-1)/B) moving_mean[c]   (the variance alike)  ->  mean[n][c], rstd[n][c] = 1/sqrt(var + eps)
+// workgroup = 64 channels x 4 samples.
+__global__ __launch_bounds__(CB * RL) void bn_blend_final_kernel(const double* __restrict__ part, BnShape s, float eps,
+                                                                const float* __restrict__ moving_mean, const float* __restrict__ moving_var,
+                                                                float* __restrict__ mean, float* __restrict__ rstd) {
+    const int cl = threadIdx.x % CB, sl = threadIdx.x / CB;
+    const int c = blockIdx.y * CB + cl, sample = blockIdx.x * RL + sl;
+    if (c >= s.c || sample >= s.n) return;
+    double a = 0., b = 0.;
+    for (int k = 0; k < s.hc; ++k) {
+        const long long i = ((long long)sample * s.hc + k) * 2 * s.c;
+        a += part[i + c]; b += part[i + s.c + c];
+    }
+    const double m = a / s.hw;
+    double var = b / s.hw - m * m;
+    if (var < 0.) var = 0.;
+    const float B = (float)s.n;
+    const float wa = 1.f / B, wb = (B - 1.f) / B;
+    const float mu = wa * (float)m + wb * moving_mean[c];
+    const float v = wa * (float)var + wb * moving_var[c];
+    mean[(long long)sample * s.c + c] = mu;
+    rstd[(long long)sample * s.c + c] = (float)(1.0 / sqrt((double)v + (double)eps));
+}
+
+__device__ __forceinline__ float bn_elu(float x) { return x > 0.f ? x : expm1f(x); }
+
+// y = [shortcut +] alpha * [relu]( (x - mean) * rstd * scale + offset ),  elu_out = elu(y)   in one pass.
+// sstride: 0 = mean / rstd per channel (training statistics), c = per (sample, channel) (the blend).  shortcut / elu_out may be NULL.
+__global__ void bn_apply_ex_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd, int sstride,
+                                   const float* __restrict__ scale, const float* __restrict__ offset, const float* __restrict__ shortcut,
+                                   float alpha, float* __restrict__ y, float* __restrict__ elu_out, BnShape s, int relu) {
+    const long long total = (long long)s.n * s.hw * s.c;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long hwc = (long long)s.hw * s.c;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int c = i % s.c;
+        const long long st = (i / hwc) * sstride + c;
+        float v = (x[i] - mean[st]) * rstd[st] * scale[c] + offset[c];
+        if (relu) v = fmaxf(v, 0.f);
+        v = shortcut ? shortcut[i] + alpha * v : alpha * v;
+        y[i] = v;
+        if (elu_out) elu_out[i] = bn_elu(v);
+    }
+}
+// vector form, as bn_apply_vec_kernel: a thread owns 4 consecutive channels of one sample and keeps their coefficients in registers
+__global__ __launch_bounds__(256) void bn_apply_ex_vec_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                              const float* __restrict__ rstd, int sstride, const float* __restrict__ scale,
+                                                              const float* __restrict__ offset, const float* __restrict__ shortcut, float alpha,
+                                                              float* __restrict__ y, float* __restrict__ elu_out, BnShape s, int relu) {
+    const int c4n = s.c >> 2, c4 = threadIdx.x % c4n, pl = threadIdx.x / c4n, pstep = 256 / c4n;
+    const int sample = blockIdx.x, p0 = blockIdx.y * APOS, p1 = min(s.hw, p0 + APOS);
+    const long long st = (long long)sample * sstride + c4 * 4;
+    const float4 mu = *reinterpret_cast<const float4*>(mean + st), rs = *reinterpret_cast<const float4*>(rstd + st);
+    const float4 ga = *reinterpret_cast<const float4*>(scale + c4 * 4), be = *reinterpret_cast<const float4*>(offset + c4 * 4);
+    const long long base = ((long long)sample * s.hw) * s.c + c4 * 4;
+    for (int p = p0 + pl; p < p1; p += pstep) {
+        const long long o = base + (long long)p * s.c;
+        const float4 v = *reinterpret_cast<const float4*>(x + o);
+        float4 r;     // the operation order of bn_apply_kernel, then the residual sum
+        r.x = (v.x - mu.x) * rs.x * ga.x + be.x; r.y = (v.y - mu.y) * rs.y * ga.y + be.y;
+        r.z = (v.z - mu.z) * rs.z * ga.z + be.z; r.w = (v.w - mu.w) * rs.w * ga.w + be.w;
+        if (relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+        if (shortcut) {
+            const float4 sc = *reinterpret_cast<const float4*>(shortcut + o);
+            r.x = sc.x + alpha * r.x; r.y = sc.y + alpha * r.y; r.z = sc.z + alpha * r.z; r.w = sc.w + alpha * r.w;
+        } else {
+            r.x *= alpha; r.y *= alpha; r.z *= alpha; r.w *= alpha;
+        }
+        *reinterpret_cast<float4*>(y + o) = r;
+        if (elu_out) {
+            float4 e;
+            e.x = bn_elu(r.x); e.y = bn_elu(r.y); e.z = bn_elu(r.z); e.w = bn_elu(r.w);
+            *reinterpret_cast<float4*>(elu_out + o) = e;
+        }
+    }
+}
+
+// the fp64 partial sums of the two entry points above (rows per (sample, chunk): what the blend needs per sample)
+int launch_partial_f64(const float* x, const BnShape& s, double* part, hipStream_t st) {
+    if (bn_vec_ok(s, x, x, x))
+        hipLaunchKernelGGL(bn_stats_partial_vec_kernel<double>, dim3(s.n * s.hc), dim3(256), 0, st, x, s, part);
+    else
+        hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(s.n * s.hc, (s.c + CB - 1) / CB), dim3(CB * RL), 0, st, x, s, part);
+    return ctgan_check_launch("bn_stats_partial");
+}
+
 }  // namespace
 
 extern "C" {
@@ -445,10 +578,11 @@ int ctgan_bn_apply(const float* x, const float* mean, const float* rstd, const f
     return ctgan_check_launch("bn_apply");
 }
 
-int ctgan_bn_bwd(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale,
-                 const float* offset, const int32_t* labels, float* gx, float* gscale, float* goffset, int32_t n,
-                 int32_t hw, int32_t c, int32_t groups, int32_t n_labels, int32_t relu, void* ws, size_t ws_bytes,
-                 ctgan_stream_t stream) {
+// scaled: the gradient is gys * gy (no labels, one group, no ReLU); the gain of the apply pass is then sga, written by the finalisation
+static int bn_bwd_impl(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale,
+                       const float* offset, const int32_t* labels, float* gx, float* gscale, float* goffset, int32_t n,
+                       int32_t hw, int32_t c, int32_t groups, int32_t n_labels, int32_t relu, void* ws, size_t ws_bytes,
+                       bool scaled, double gys, ctgan_stream_t stream) {
     int rc = check_shape(n, hw, c, groups, "bn_bwd");
     if (rc) return rc;
     if (!gy || !x || !mean || !rstd || !scale || !offset || !gx || !gscale || !goffset || !ws || n_labels <= 0)
@@ -469,12 +603,14 @@ int ctgan_bn_bwd(const float* gy, const float* x, const float* mean, const float
                            scale, offset, labels, s, relu, part);
     rc = ctgan_check_launch("bn_bwd_partial");
     if (rc) return rc;
-    (void)bins; (void)tot;
+    (void)tot;
+    float* sga = scaled ? reinterpret_cast<float*>(bins) : nullptr;      // c floats of the (otherwise unused) label-bin region
     // the finalisation sums the (<= 4) chunk partials of a sample itself: no per-sample totals pass
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((c + 63) / 64, n_labels + groups), dim3(64 * 16), 0, st, part, scale, labels, s,
-                       n_labels, gscale, goffset, s12);
+                       n_labels, gscale, goffset, s12, gys, sga);
     rc = ctgan_check_launch("bn_bwd_final");
     if (rc) return rc;
+    if (scaled) scale = sga;
     if (bn_vec_ok(s, gy, x, gx) && bn_vec_ok(s, mean, rstd, scale) && bn_vec_ok(s, offset, s12, s12)) {
         hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3(n, (hw + APOS - 1) / APOS), dim3(256), 0, st, gy, x, mean, rstd, scale, offset, labels,
                            s12, gx, s, relu);
@@ -483,6 +619,72 @@ int ctgan_bn_bwd(const float* gy, const float* x, const float* mean, const float
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ctgan_blocks((long long)n * hw * c, 256)), dim3(256), 0, st, gy, x, mean,
                        rstd, scale, offset, labels, s12, gx, s, relu);
     return ctgan_check_launch("bn_bwd_apply");
+}
+
+int ctgan_bn_bwd(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale,
+                 const float* offset, const int32_t* labels, float* gx, float* gscale, float* goffset, int32_t n,
+                 int32_t hw, int32_t c, int32_t groups, int32_t n_labels, int32_t relu, void* ws, size_t ws_bytes,
+                 ctgan_stream_t stream) {
+    return bn_bwd_impl(gy, x, mean, rstd, scale, offset, labels, gx, gscale, goffset, n, hw, c, groups, n_labels, relu, ws, ws_bytes,
+                       false, 1.0, stream);
+}
+
+int ctgan_bn_bwd_scaled(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale,
+                        const float* offset, float gy_scale, float* gx, float* gscale, float* goffset, int32_t n, int32_t hw,
+                        int32_t c, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    return bn_bwd_impl(gy, x, mean, rstd, scale, offset, nullptr, gx, gscale, goffset, n, hw, c, 1, 1, 0, ws, ws_bytes, true,
+                       (double)gy_scale, stream);
+}
+
+int ctgan_bn_stats_moving(const float* x, int32_t n, int32_t hw, int32_t c, float eps, float* mean, float* rstd, float* moving_mean,
+                          float* moving_var, const float* it, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    int rc = check_shape(n, hw, c, 1, "bn_stats_moving");
+    if (rc) return rc;
+    if (!x || !mean || !rstd || !ws) return ctgan_fail(CTGAN_E_BADARG, "bn_stats_moving: null");
+    if ((moving_mean != nullptr) != (moving_var != nullptr) || (moving_mean && !it))
+        return ctgan_fail(CTGAN_E_BADARG, "bn_stats_moving: the update needs moving_mean, moving_var and it");
+    const BnShape s = mk(n, hw, c, 1);
+    if (ws_bytes < part_bytes(s)) return ctgan_fail(CTGAN_E_BADARG, "bn_stats_moving: workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = launch_partial_f64(x, s, static_cast<double*>(ws), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_stats_final_moving_kernel, dim3((c + CB - 1) / CB), dim3(CB * FL), 0, st, static_cast<const double*>(ws), s, eps,
+                       mean, rstd, moving_mean, moving_var, it);
+    return ctgan_check_launch("bn_stats_final_moving");
+}
+
+int ctgan_bn_blend_stats(const float* x, int32_t n, int32_t hw, int32_t c, float eps, const float* moving_mean, const float* moving_var,
+                         float* mean, float* rstd, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    int rc = check_shape(n, hw, c, 1, "bn_blend_stats");
+    if (rc) return rc;
+    if (!x || !mean || !rstd || !moving_mean || !moving_var || !ws) return ctgan_fail(CTGAN_E_BADARG, "bn_blend_stats: null");
+    const BnShape s = mk(n, hw, c, 1);
+    if (ws_bytes < part_bytes(s)) return ctgan_fail(CTGAN_E_BADARG, "bn_blend_stats: workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = launch_partial_f64(x, s, static_cast<double*>(ws), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_blend_final_kernel, dim3((n + RL - 1) / RL, (c + CB - 1) / CB), dim3(CB * RL), 0, st,
+                       static_cast<const double*>(ws), s, eps, moving_mean, moving_var, mean, rstd);
+    return ctgan_check_launch("bn_blend_final");
+}
+
+int ctgan_bn_apply_ex(const float* x, const float* mean, const float* rstd, int32_t per_sample, const float* scale, const float* offset,
+                      const float* shortcut, float alpha, float* y, float* elu_out, int32_t relu, int32_t n, int32_t hw, int32_t c,
+                      ctgan_stream_t stream) {
+    int rc = check_shape(n, hw, c, 1, "bn_apply_ex");
+    if (rc) return rc;
+    if (!x || !mean || !rstd || !scale || !offset || !y) return ctgan_fail(CTGAN_E_BADARG, "bn_apply_ex: null");
+    const BnShape s = mk(n, hw, c, 1);
+    const int sstride = per_sample ? c : 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (bn_vec_ok(s, x, y, mean) && bn_vec_ok(s, rstd, scale, offset) && bn_vec_ok(s, shortcut, elu_out, x)) {
+        hipLaunchKernelGGL(bn_apply_ex_vec_kernel, dim3(n, (hw + APOS - 1) / APOS), dim3(256), 0, st, x, mean, rstd, sstride, scale, offset,
+                           shortcut, alpha, y, elu_out, s, relu);
+        return ctgan_check_launch("bn_apply_ex_vec");
+    }
+    hipLaunchKernelGGL(bn_apply_ex_kernel, dim3(ctgan_blocks((long long)n * hw * c, 256)), dim3(256), 0, st, x, mean, rstd, sstride, scale,
+                       offset, shortcut, alpha, y, elu_out, s, relu);
+    return ctgan_check_launch("bn_apply_ex");
 }
 
 }  // extern "C"

@@ -708,3 +708,97 @@ class GraphedCifarTETrainer(GraphedCifarSSLTrainer):
         t = self.t
         assert t.epoch_pred is not None, 'bind the uint8 training set first (CifarTETrainer.bind_data allocates the tables)'
         return [t.epoch_pred, t.epoch_pred2]
+
+
+class GraphedScoreTrainer:
+    """hipGraph replay of score_mnist.ScoreTrainer's train step (forward, backward, gradient packing, global-norm clip, Adam) and of its
+    statistics pass (the training-mode forward that moves the moving statistics), on the pattern of GraphedSSLTrainer: one stream, no
+    parallel branches, the batch staged into fixed buffers; the learning rate, Adam's beta powers and `stats_iter` live in device
+    memory, so both graphs replay with the values current at replay.  The warm-up runs at learning rate 0 and every buffer it writes
+    (Adam's slots, the moving statistics, stats_iter) is restored afterwards: a graphed run equals an eager one bit for bit."""
+
+    def __init__(self, trainer, use_graphs=True, warmup=2):
+        from . import score_mnist as M
+        self.t = trainer
+        B, dev = M.cfg.BATCH_SIZE, trainer.dev
+        self.x = torch.zeros(B, 784, dtype=torch.float32, device=dev)
+        self.y = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.step_graph = self.stats_graph = None
+        self.step_out = None
+        self.graph_error = None
+        if use_graphs:
+            try:
+                self._capture(warmup)
+            except Exception as e:
+                self.graph_error = '%s: %s' % (type(e).__name__, e)
+                self.step_graph = self.stats_graph = None
+                torch.cuda.synchronize()
+
+    def _step_body(self):
+        lib.bump_epoch('InceptionScore')      # weights changed since the last replay: derived / packed filters are rebuilt in-graph
+        F.prepare_filters()
+        return self.t.body(self.x, self.y)
+
+    def _stats_body(self):
+        lib.bump_epoch('InceptionScore')
+        F.prepare_filters()
+        self.t.stats_body(self.x)
+
+    def _capture(self, warmup):
+        t = self.t
+        K.reset_capture_workspaces()
+        bufs = t.opt.slots() + [p.data for _, p in t.moving_stats()] + [t.stats_iter]
+        snap = [b.clone() for b in bufs]
+        steps = t.opt.t
+        t.opt.set_lr(0.0)
+        try:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(warmup):
+                    self._step_body()
+                    self._stats_body()
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            quiesce_collectives()
+            self.step_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.step_graph, **_capture_kw()):
+                self.step_out = self._step_body()
+            self.stats_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.stats_graph, **_capture_kw()):
+                self._stats_body()
+        finally:
+            torch.cuda.synchronize()
+            for b, sn in zip(bufs, snap):
+                b.copy_(sn)
+            t.opt.t, t.opt._lr_last = steps, None
+            torch.cuda.synchronize()
+
+    @property
+    def graphed(self):
+        return self.step_graph is not None
+
+    def step(self, x, y):
+        """-> cost, acc, gradnorm of one train step on (x [B,784] float32, y [B] int32), host or device tensors."""
+        t = self.t
+        if not self.graphed:
+            return t.step(x, y)
+        self.x.copy_(x, non_blocking=True)
+        self.y.copy_(y, non_blocking=True)
+        t.opt.set_lr(t.lr())
+        t.stats_iter.fill_(0)
+        self.step_graph.replay()
+        t.opt.t += 1
+        t.iteration += 1
+        lib.bump_epoch('InceptionScore')
+        out = self.step_out
+        return out['cost'], out['acc'], out['gradnorm']
+
+    def bn_stats_pass(self, x, i):
+        t = self.t
+        if not self.graphed:
+            return t.bn_stats_pass(x, i)
+        self.x.copy_(x, non_blocking=True)
+        t.stats_iter.fill_(i)
+        self.stats_graph.replay()
+        lib.bump_epoch('InceptionScore')

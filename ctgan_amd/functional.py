@@ -1377,6 +1377,99 @@ def batch_norm(x, scale, offset, labels=None, groups=1, relu=False, eps=1e-5, f6
     return BatchNormFn.apply(x, scale, offset, labels, groups, relu, float(eps), bool(f64_stats))
 
 
+# --------------------------------------------------------------------------------- score classifier: ELU, BN with moving statistics
+# CTGAN_SCORE_FUSED=0: the residual block's  shortcut + alpha bn(x)  [and the ELU of it]  as bn_apply, F.add and ELU launches instead
+# of the one-pass epilogue (kernels.bn_apply_ex) - the A/B switch of that fusion.
+SCORE_FUSED = _os.environ.get('CTGAN_SCORE_FUSED', '1') != '0'
+
+
+class EluFn(Function):
+    """ELU, alpha 1; the backward reads the forward output only."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = K.elu_fwd(x if K.is_dense(x) else x.contiguous())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        return K.elu_bwd(gy.contiguous() if not K.is_dense(gy) else gy, y)
+
+
+def elu(x):
+    return EluFn.apply(x)
+
+
+class ScoreBNFn(Function):
+    """Training-mode BN (one group, fp64 statistics) -> (y, elu(y) or None) with y = [shortcut +] alpha [relu](bn(x)) in one pass.
+    moving: None, or (moving_mean, moving_var, it) - moved in place by the statistics' own finalisation (kernels.bn_stats_moving).
+    The backward takes both cotangents: elu'(.) g_e + g_y in one launch, then the BN backward with alpha folded into its totals."""
+
+    @staticmethod
+    def forward(ctx, x, scale, offset, shortcut, alpha, want_elu, relu, moving, eps):
+        mm, mv, it = moving if moving is not None else (None, None, None)
+        mean, rstd, x4 = K.bn_stats_moving(x, eps, mm, mv, it)
+        fused = shortcut is not None or alpha != 1.0
+        assert not (fused and relu)
+        y, e = K.bn_apply_ex(x4, mean, rstd, scale, offset, shortcut, alpha, relu, want_elu)
+        ctx.alpha, ctx.relu, ctx.fused, ctx.in_shape, ctx.has_shortcut = alpha, relu, fused, x.shape, shortcut is not None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x4, mean, rstd, scale, offset, e)
+        if x.dim() == 2:
+            y = y.view(x.shape)
+            e = e.view(x.shape) if e is not None else None
+        return y, e
+
+    @staticmethod
+    def backward(ctx, gy, ge):
+        x4, mean, rstd, scale, offset, e = ctx.saved_tensors
+        if gy is not None and gy.dim() == 2:
+            gy = gy.reshape(x4.shape)
+        if ge is not None:
+            gy = K.elu_bwd(ge.reshape(x4.shape) if ge.dim() == 2 else ge, e, gy)
+        if gy is None:
+            return (None,) * 9
+        if ctx.fused:
+            gx, gs, go = K.bn_bwd_scaled(gy, x4, mean, rstd, scale, offset, ctx.alpha)
+        else:
+            gx, gs, go = K.bn_bwd(gy, x4, mean, rstd, scale.view(1, -1), offset.view(1, -1), None, 1, ctx.relu)
+        if len(ctx.in_shape) == 2:
+            gx = gx.reshape(ctx.in_shape)
+        return gx, gs.view(scale.shape), go.view(offset.shape), (gy if ctx.has_shortcut else None), None, None, None, None, None
+
+
+def batch_norm_moving(x, scale, offset, moving=None, shortcut=None, alpha=1.0, relu=False, want_elu=False, eps=1e-5):
+    """Training-mode BN of the score classifier -> y, or (y, elu(y)) with want_elu.  moving = (moving_mean, moving_var, it): the
+    moving statistics move in place, it a float32 device scalar (kernels.device_scalar)."""
+    if SCORE_FUSED or (shortcut is None and alpha == 1.0 and not want_elu):
+        y, e = ScoreBNFn.apply(x, scale, offset, shortcut, float(alpha), bool(want_elu), bool(relu), moving, float(eps))
+    else:
+        y, _ = ScoreBNFn.apply(x, scale, offset, None, 1.0, False, bool(relu), moving, float(eps))
+        y = AddFn.apply(shortcut, y, 1.0, float(alpha)) if shortcut is not None else ScaleFn.apply(y, float(alpha))
+        e = elu(y) if want_elu else None
+    return (y, e) if want_elu else y
+
+
+def batch_norm_blend(x, scale, offset, moving_mean, moving_var, shortcut=None, alpha=1.0, relu=False, want_elu=False, eps=1e-5):
+    """Inference-mode BN of the score classifier (LS/tflib/ops/batchnorm.py:32-38): every sample is normalised by its own moments
+    over h*w blended with the moving statistics, weights 1/B and (B-1)/B, B = the rows of the call.  Forward only."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, scale, offset, shortcut)):
+        raise RuntimeError('batch_norm_blend is forward only: call it under torch.no_grad()')
+    mean, rstd, x4 = K.bn_blend_stats(x, moving_mean, moving_var, eps)
+    if SCORE_FUSED or (shortcut is None and alpha == 1.0 and not want_elu):
+        y, e = K.bn_apply_ex(x4, mean, rstd, scale, offset, shortcut, float(alpha), relu, want_elu)
+    else:
+        y, _ = K.bn_apply_ex(x4, mean, rstd, scale, offset, None, 1.0, relu, False)
+        y = K.axpby(shortcut, y, 1.0, float(alpha)) if shortcut is not None else K.axpby(y, None, float(alpha), 0.0)
+        e = K.elu_fwd(y) if want_elu else None
+    if x.dim() == 2:
+        y = y.view(x.shape)
+        e = e.view(x.shape) if e is not None else None
+    return (y, e) if want_elu else y
+
+
 # --------------------------------------------------------------------------------- layer norm (config[4] critic)
 # TF/tflib/ops/layernorm.py:6-20 = tf.nn.moments over (C,H,W) per sample + tf.nn.batch_normalization with a per-channel
 # scale / offset.  The critic is differentiated TWICE through it (gradient penalty), so the operator is a composition

@@ -1516,6 +1516,123 @@ def bn_bwd(gy, x4, mean, rstd, scale, offset, labels, groups, relu):
     return gx, gscale, goffset
 
 
+# ------------------------------------------------------------------------------- score classifier (csrc/bn.hip, csrc/score.hip)
+def _bn_x4(x):
+    x4 = x if x.dim() == 4 else x.view(x.shape[0], x.shape[1], 1, 1)
+    return to_channels_last(x4)
+
+
+def device_scalar(value, device):
+    """`value` (a number, or a one-element int / float tensor) as a float32 device scalar [1]: what the kernels read a step-dependent
+    quantity from, so that a captured step replays with the value current at replay."""
+    if torch.is_tensor(value):
+        if value.numel() != 1:
+            raise ValueError('expected a scalar tensor')
+        return value.reshape(1).to(device=device, dtype=torch.float32)
+    return torch.full((1,), float(value), dtype=torch.float32, device=device)
+
+
+def bn_stats_moving(x, eps=1e-5, moving_mean=None, moving_var=None, it=None):
+    """Training-mode moments of x (channels-last [N,C,H,W] or [N,C]) over (n,h,w), all sums in fp64 -> mean [1,C], rstd [1,C], x4.  With
+    moving_mean / moving_var [C]: both are moved IN PLACE by moving <- (it/(it+1)) moving + (1/(it+1)) batch (fp32; batch variance with
+    the n/(n-1) factor), `it` a float32 device scalar (device_scalar)."""
+    _need_dev(x, moving_mean, moving_var, it)
+    x4 = _bn_x4(x)
+    N, C, H, W = x4.shape
+    if moving_mean is not None:
+        assert moving_mean.is_contiguous() and moving_var.is_contiguous() and moving_mean.numel() == C and moving_var.numel() == C
+        assert it is not None and it.dtype == torch.float32 and it.numel() == 1
+    mean = torch.empty((1, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((1, C), dtype=torch.float32, device=x.device)
+    ws = workspace(lib.ctgan_bn_workspace_bytes(N, H * W, C, 1, 1), x.device)
+    check(lib.ctgan_bn_stats_moving(_ptr(x4), N, H * W, C, eps, _ptr(mean), _ptr(rstd), _ptr(moving_mean), _ptr(moving_var), _ptr(it),
+                                    _ptr(ws), ws.numel(), _stream()), 'bn_stats_moving')
+    return mean, rstd, x4
+
+
+def bn_blend_stats(x, moving_mean, moving_var, eps=1e-5):
+    """Statistics of the inference-mode blend -> mean [N,C], rstd [N,C], x4 (ctgan_bn_blend_stats)."""
+    _need_dev(x, moving_mean, moving_var)
+    x4 = _bn_x4(x)
+    N, C, H, W = x4.shape
+    assert moving_mean.is_contiguous() and moving_var.is_contiguous() and moving_mean.numel() == C and moving_var.numel() == C
+    mean = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    ws = workspace(lib.ctgan_bn_workspace_bytes(N, H * W, C, 1, 1), x.device)
+    check(lib.ctgan_bn_blend_stats(_ptr(x4), N, H * W, C, eps, _ptr(moving_mean), _ptr(moving_var), _ptr(mean), _ptr(rstd), _ptr(ws),
+                                   ws.numel(), _stream()), 'bn_blend_stats')
+    return mean, rstd, x4
+
+
+def bn_apply_ex(x4, mean, rstd, scale, offset, shortcut=None, alpha=1.0, relu=False, want_elu=False):
+    """-> (y, elu(y) or None), y = [shortcut +] alpha [relu]((x4 - mean) rstd scale + offset) in one pass; mean / rstd [1,C] (training
+    statistics) or [N,C] (bn_blend_stats).  x4 channels-last; shortcut in x4's layout."""
+    _need_dev(x4, mean, rstd, scale, offset, shortcut)
+    N, C, H, W = x4.shape
+    assert x4.permute(0, 2, 3, 1).is_contiguous() and mean.shape == rstd.shape and mean.shape[0] in (1, N) and mean.shape[1] == C
+    assert scale.numel() == C and offset.numel() == C
+    per_sample = 1 if (mean.shape[0] == N and N > 1) else 0
+    if shortcut is not None:
+        assert tuple(shortcut.shape) == tuple(x4.shape)
+        shortcut = to_channels_last(shortcut)
+    y = empty_cl(N, C, H, W, x4.device)
+    e = empty_cl(N, C, H, W, x4.device) if want_elu else None
+    check(lib.ctgan_bn_apply_ex(_ptr(x4), _ptr(mean), _ptr(rstd), per_sample, _ptr(scale), _ptr(offset), _ptr(shortcut), alpha, _ptr(y),
+                                _ptr(e), 1 if relu else 0, N, H * W, C, _stream()), 'bn_apply_ex')
+    return y, e
+
+
+def bn_bwd_scaled(gy, x4, mean, rstd, scale, offset, gy_scale):
+    """bn_bwd (one group, no labels, no ReLU) of gy_scale * gy without a pass that scales gy -> gx, gscale [1,C], goffset [1,C]."""
+    _need_dev(gy, x4, mean, rstd, scale, offset)
+    N, C, H, W = x4.shape
+    gy4 = to_channels_last(gy if gy.dim() == 4 else gy.reshape(N, C, 1, 1))
+    gx = empty_cl(N, C, H, W, gy.device)
+    gscale = torch.empty((1, C), dtype=torch.float32, device=gy.device)
+    goffset = torch.empty((1, C), dtype=torch.float32, device=gy.device)
+    ws = workspace(lib.ctgan_bn_workspace_bytes(N, H * W, C, 1, 1), gy.device)
+    check(lib.ctgan_bn_bwd_scaled(_ptr(gy4), _ptr(x4), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(offset), gy_scale, _ptr(gx), _ptr(gscale),
+                                  _ptr(goffset), N, H * W, C, _ptr(ws), ws.numel(), _stream()), 'bn_bwd_scaled')
+    return gx, gscale, goffset
+
+
+def elu_fwd(x):
+    _need_dev(x)
+    y = _ew_out(x)
+    check(lib.ctgan_elu_fwd(_ptr(x), _ptr(y), x.numel(), _stream()), 'elu_fwd')
+    return y
+
+
+def elu_bwd(gy, y, add=None):
+    """[add +] elu'(.) gy from the forward output y; gy / add are brought to y's layout."""
+    _need_dev(gy, y, add)
+    gy = match_layout(gy, y)
+    if add is not None:
+        add = match_layout(add, y)
+    gx = _ew_out(y)
+    check(lib.ctgan_elu_bwd(_ptr(gy), _ptr(y), _ptr(add), _ptr(gx), y.numel(), _stream()), 'elu_bwd')
+    return gx
+
+
+def global_norm(flat, out=None):
+    """sqrt(sum flat^2) of a contiguous fp32 buffer into a float32 device scalar [1] (`out`, or a new one): deterministic, no host read."""
+    _need_dev(flat, out)
+    assert flat.is_contiguous()
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=flat.device)
+    ws = workspace(lib.ctgan_global_norm_workspace_bytes(flat.numel()), flat.device)
+    check(lib.ctgan_global_norm(_ptr(flat), flat.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream()), 'global_norm')
+    return out
+
+
+def clip_by_norm_(flat, norm, clip):
+    """flat *= clip / max(norm, clip) in place, norm a float32 device scalar (global_norm)."""
+    _need_dev(flat, norm)
+    assert flat.is_contiguous() and norm.numel() == 1 and norm.dtype == torch.float32
+    check(lib.ctgan_clip_by_norm(_ptr(flat), flat.numel(), _ptr(norm), float(clip), _stream()), 'clip_by_norm')
+    return flat
+
+
 # ------------------------------------------------------------------------------- loss heads
 def gp_fwd(g, lam, defer_mean=False):
     """-> (gp, slopes).  defer_mean: only the slopes are computed here; gp is an UNWRITTEN slot that tail_critic_heads_fwd(slopes=...,

@@ -118,6 +118,15 @@ class FlatAdam:
         self._keepalive = srcs
         self._end(rng)
 
+    def update_clipped(self, grads, clip_norm, rng=None):
+        """gather_grads, tf.clip_by_global_norm over the whole bucket (LS/tflib/train_loop_2.py:76-79), step.  Returns the norm BEFORE
+        the clip as a float32 device scalar [1]; nothing crosses to the host (kernels.global_norm / clip_by_norm_)."""
+        self.gather_grads(grads)
+        norm = K.global_norm(self.grad)
+        K.clip_by_norm_(self.grad, norm, clip_norm)
+        self.step(1.0, rng)
+        return norm
+
     def slots(self):
         """The device tensors a step writes besides the weights: what a graph capture's warm-up steps must leave as they found them."""
         return [self.m, self.v, self.state]

@@ -112,6 +112,16 @@ def delete_all_params():
         fn()
 
 
+def delete_params_with_name(name):
+    """Forget the parameters whose name contains `name` (one network of several in the registry); the others stay."""
+    for n in [n for n in _params if name in n]:
+        del _params[n]
+        _non_trainable.discard(n)
+    bump_epoch()
+    for fn in _delete_hooks:              # derived-weight caches are keyed by parameter addresses
+        fn()
+
+
 def alias_params(replace_dict):
     for old, new in replace_dict.items():
         _param_aliases[old] = new

@@ -434,6 +434,41 @@ int ctgan_bn_bwd(const float* gy, const float* x, const float* mean, const float
                  ctgan_stream_t stream);
 size_t ctgan_bn_workspace_bytes(int32_t n, int32_t hw, int32_t c, int32_t groups, int32_t n_labels);
 
+/* ---- batch norm of the self-trained MNIST score classifier (LS/tflib/ops/batchnorm.py:30-69) ---- */
+/* ctgan_bn_stats_f64 for one statistic group that also moves the moving statistics in place (:62-65):
+ *   moving <- (it/(it+1)) moving + (1/(it+1)) batch,  in fp32, it = *it read on the DEVICE (a float scalar), no special case at 0;
+ * batch_var = biased variance * cnt/max(cnt-1, 1), cnt = n*hw (what tf.nn.fused_batch_norm returns in training), from the fp64 sums.
+ * moving_mean == moving_var == NULL: statistics only.  ws as ctgan_bn_stats.                                                        */
+int ctgan_bn_stats_moving(const float* x, int32_t n, int32_t hw, int32_t c, float eps, float* mean /*[c]*/, float* rstd /*[c]*/,
+                          float* moving_mean /*[c]*/, float* moving_var /*[c]*/, const float* it, void* ws, size_t ws_bytes,
+                          ctgan_stream_t stream);
+/* Statistics of the inference-mode "blend" (:32-38): per sample and channel the biased moments m, v over hw, then in fp32
+ *   mean[n][c] = m/B + ((B-1)/B) moving_mean[c],  var alike,  rstd[n][c] = 1/sqrt(var + eps),  B = n (the rows of the call).       */
+int ctgan_bn_blend_stats(const float* x, int32_t n, int32_t hw, int32_t c, float eps, const float* moving_mean,
+                         const float* moving_var, float* mean /*[n,c]*/, float* rstd /*[n,c]*/, void* ws, size_t ws_bytes,
+                         ctgan_stream_t stream);
+/* y = [shortcut +] alpha * [relu]((x - mean) * rstd * scale + offset) and, with elu_out, elu_out = elu(y), in one pass.
+ * per_sample: mean / rstd are [n,c] (ctgan_bn_blend_stats), else [c].  shortcut and elu_out may be NULL.                            */
+int ctgan_bn_apply_ex(const float* x, const float* mean, const float* rstd, int32_t per_sample, const float* scale,
+                      const float* offset, const float* shortcut, float alpha, float* y, float* elu_out, int32_t relu, int32_t n,
+                      int32_t hw, int32_t c, ctgan_stream_t stream);
+/* ctgan_bn_bwd (one group, no labels, no ReLU) of the gradient gy_scale * gy: the factor rides on the reduced totals and the gain,
+ * not on a pass over gy.  ws: ctgan_bn_workspace_bytes(n, hw, c, 1, 1).                                                            */
+int ctgan_bn_bwd_scaled(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale,
+                        const float* offset, float gy_scale, float* gx, float* gscale, float* goffset, int32_t n, int32_t hw,
+                        int32_t c, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+
+/* ---- ELU and the global-norm clip of the score classifier (csrc/score.hip) ---- */
+/* y = x > 0 ? x : expm1(x)                                                                      */
+int ctgan_elu_fwd(const float* x, float* y, int64_t n, ctgan_stream_t stream);
+/* gx = [add +] (y > 0 ? gy : gy * (y + 1)),  y the forward OUTPUT; add may be NULL             */
+int ctgan_elu_bwd(const float* gy, const float* y, const float* add, float* gx, int64_t n, ctgan_stream_t stream);
+/* norm[0] = sqrt(sum g^2): two-stage, fp64 partials in a fixed order (the same bits on every run) */
+size_t ctgan_global_norm_workspace_bytes(int64_t n);
+int ctgan_global_norm(const float* g, int64_t n, float* norm, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+/* g *= clip / max(norm[0], clip) in place, norm read on the device (tf.clip_by_global_norm with use_norm) */
+int ctgan_clip_by_norm(float* g, int64_t n, const float* norm, float clip, ctgan_stream_t stream);
+
 /* ---- fused loss heads (K16-K20) ------------------------------------------------------------- */
 /* slopes[b] = ||g[b,:]||_2 ; gp = lambda*mean((slopes-1)^2)   (TF/CT_gan_cifar_resnet.py:285-286); gp == NULL: slopes only */
 int ctgan_gp_fwd(const float* g, int32_t b, int32_t d, float lambda, float* slopes, float* gp,
