@@ -126,6 +126,11 @@ SIGNATURES = {
     'ctgan_layernorm_fwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int64, c_int32, c_float, c_int32, _p, c_size_t, _p]),
     'ctgan_layernorm_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, c_int32, c_int64, c_int32, _p, c_size_t, _p]),
     'ctgan_layernorm_bwd2': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, c_int32, c_int64, c_int32, _p, c_size_t, _p]),
+    'ctgan_layernorm_cond_fwd': (c_int, [_p, _p, _p, _p, c_int32, _p, _p, _p, c_int32, c_int64, c_int32, c_float, c_int32, _p, c_size_t, _p]),
+    'ctgan_layernorm_cond_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, _p, _p, _p, c_int32, c_int64, c_int32, _p, c_size_t, _p]),
+    'ctgan_layernorm_cond_bwd2': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, c_int32, _p, _p, _p, c_int32, c_int64, c_int32, _p, c_size_t, _p]),
+    'ctgan_layernorm_rows_gather': (c_int, [_p, _p, c_int32, _p, c_int32, c_int32, _p]),
+    'ctgan_layernorm_rows_sum_by_label': (c_int, [_p, _p, c_int32, _p, c_int32, c_int32, _p]),
     'ctgan_im2col': (c_int, [_D, _p, c_int32, _p, _p]),
     'ctgan_col2im': (c_int, [_D, _p, c_int32, _p, _p]),
     'ctgan_colsum': (c_int, [_p, c_int64, c_int32, c_int64, _p, _p, c_size_t, _p]),

@@ -18,6 +18,16 @@
 // channels: 1024 % C == 0) as per-workgroup partial rows + one small column reduction.  The composition of ~9 elementwise /
 // reduction kernels this replaces (functional.layer_norm_composed) stays as the fallback for other channel counts.
 // x / gy / u / outputs: dense, channel fastest ([N,H,W,C] or [N,C]); D = elements per sample.
+//
+// Label-conditioned twins (ctgan_layernorm_cond_{fwd,bwd,bwd2}; LS/tflib/ops/layernorm.py:21-30, the critic of
+// TF/CT_gan_cifar_resnet.py with CONDITIONAL, not ACGAN, NORMALIZATION_D): scale / offset are [n_labels, C] tables and sample n
+// reads row labels[n].  The same kernels, instantiated with COND = true: the only difference in the partial-sum and elementwise
+// passes is the table row a sample reads, so tables whose rows all equal one vector give the unconditional results bit for bit.
+// A label is CLAMPED to [0, n_labels) where it is read (table_row / ln_rows_reduce_by_label_kernel): a bad label can never index
+// outside the table.  The parameter gradients keep the per-workgroup partial rows [N*chunks][C]; the column reduction becomes a
+// by-label one: for every (label, channel) the rows whose sample (row / chunks) carries that label, each row lane in ascending
+// row order, fp64, lanes folded in fixed order - no float atomics, identical bits run to run, a written zero row for an absent
+// label.
 #include "common.h"
 
 namespace {
@@ -34,14 +44,22 @@ __device__ __forceinline__ double block_sum(double v, double* red /* [NT/64] */)
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// offset of sample n's row in the [n_labels, C] tables (0 for the unconditional vectors); the label is clamped to the table
+template <bool COND>
+__device__ __forceinline__ long long table_row(const int* __restrict__ labels, int n_labels, int n, int C) {
+    if (!COND) return 0;
+    const int l = min(max(labels[n], 0), n_labels - 1);
+    return (long long)l * C;
+}
+
 // mode 0: sums of x, x^2                               -> part[n][chunk][2]
 // mode 1: sums of g, g*xh               (g = gy*scale) -> part[n][chunk][2]
 // mode 2: sums of u, u*xh, g, g*xh, u*g                -> part[n][chunk][5]
-template <int MODE>
+template <int MODE, bool COND>
 __global__ __launch_bounds__(NT) void ln_partial_kernel(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ u,
                                                         const float* __restrict__ scale, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, const float* __restrict__ ymask, long long D, int C,
-                                                        double* __restrict__ part) {
+                                                        const int* __restrict__ labels, int n_labels, double* __restrict__ part) {
     constexpr int NS = MODE == 2 ? 5 : 2;
     __shared__ double red[NT / 64];
     const int n = blockIdx.y, chunk = blockIdx.x;
@@ -50,6 +68,7 @@ __global__ __launch_bounds__(NT) void ln_partial_kernel(const float* __restrict_
     const float* gs = MODE ? gy + (long long)n * D : nullptr;
     const float* us = MODE == 2 ? u + (long long)n * D : nullptr;
     const float mu = MODE ? mean[n] : 0.f, r = MODE ? rstd[n] : 0.f;
+    const float* sc = MODE ? scale + table_row<COND>(labels, n_labels, n, C) : nullptr;
     float s[NS];
     double d0 = 0., d1 = 0.;          // mode 0: E[x^2] - E[x]^2 cancels when |mean| >> std - carry the moments in fp64 throughout
 #pragma unroll
@@ -62,7 +81,7 @@ __global__ __launch_bounds__(NT) void ln_partial_kernel(const float* __restrict_
             for (int j = 0; j < 4; ++j) { d0 += (double)xa[j]; d1 += (double)xa[j] * (double)xa[j]; }
         } else {
             const float4 gv = *reinterpret_cast<const float4*>(gs + e);
-            const float4 sv = *reinterpret_cast<const float4*>(scale + (int)(e % C));
+            const float4 sv = *reinterpret_cast<const float4*>(sc + (int)(e % C));
             float ga[4] = {gv.x * sv.x, gv.y * sv.y, gv.z * sv.z, gv.w * sv.w};
             if (ymask) {                      // fused ReLU: the gradient only passes where the forward result is positive
                 const float4 yv = *reinterpret_cast<const float4*>(ymask + (long long)n * D + e);
@@ -100,10 +119,14 @@ __device__ __forceinline__ void fold_partials(const double* __restrict__ part, i
         for (int k = 0; k < NS; ++k) tot[k] += p[c * NS + k];
 }
 
+template <bool COND>
 __global__ __launch_bounds__(NT) void ln_fwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
                                                           const double* __restrict__ part, long long D, int C, float eps, int relu,
+                                                          const int* __restrict__ labels, int n_labels,
                                                           float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
     const int n = blockIdx.y, chunk = blockIdx.x;
+    const long long trow = table_row<COND>(labels, n_labels, n, C);
+    scale += trow; offset += trow;
     double t[2];
     fold_partials<2>(part, n, gridDim.x, t);
     const double m = t[0] / (double)D;
@@ -149,12 +172,15 @@ __device__ __forceinline__ void channel_rows(const float (&acc)[NV][4], int C, f
     }
 }
 
+template <bool COND>
 __global__ __launch_bounds__(NT) void ln_bwd_apply_kernel(const float* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ scale,
                                                           const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ ymask,
-                                                          const double* __restrict__ part, long long D, int C, float* __restrict__ gx,
+                                                          const double* __restrict__ part, long long D, int C,
+                                                          const int* __restrict__ labels, int n_labels, float* __restrict__ gx,
                                                           float* __restrict__ rows /* [2][N*chunks][C] or null */) {
     __shared__ float lds[2 * NT * 4];
     const int n = blockIdx.y, chunk = blockIdx.x;
+    scale += table_row<COND>(labels, n_labels, n, C);
     double t[2];
     fold_partials<2>(part, n, gridDim.x, t);
     const float a = (float)(t[0] / (double)D), b = (float)(t[1] / (double)D);
@@ -186,14 +212,17 @@ __global__ __launch_bounds__(NT) void ln_bwd_apply_kernel(const float* __restric
     if (rows) channel_rows<2>(acc, C, lds, rows, (long long)n * gridDim.x + chunk, gridDim.x * gridDim.y);
 }
 
+template <bool COND>
 __global__ __launch_bounds__(NT) void ln_bwd2_apply_kernel(const float* __restrict__ u, const float* __restrict__ gy, const float* __restrict__ x,
                                                            const float* __restrict__ scale, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ ymask,
                                                            const double* __restrict__ part, long long D, int C,
+                                                           const int* __restrict__ labels, int n_labels,
                                                            float* __restrict__ cot_gy, float* __restrict__ cot_x,
                                                            float* __restrict__ rows /* [1][N*chunks][C] or null */) {
     __shared__ float lds[NT * 4];
     const int n = blockIdx.y, chunk = blockIdx.x;
+    scale += table_row<COND>(labels, n_labels, n, C);
     double t[5];
     fold_partials<5>(part, n, gridDim.x, t);
     const double inv = 1.0 / (double)D;
@@ -264,9 +293,109 @@ __global__ __launch_bounds__(RC * RLN) void ln_rows_reduce_kernel(const float* _
     }
 }
 
+// out[v][label][c] = sum of rows[v][row][c] over the rows whose sample (row / chunks) carries `label` (clamped as in table_row):
+// one workgroup per (64 channels, v, label), 16 row lanes that each walk their rows in ascending order, fp64, lanes folded in
+// fixed order => deterministic, no atomics; a label that no sample carries gets a written row of zeros.
+__global__ __launch_bounds__(RC * RLN) void ln_rows_reduce_by_label_kernel(const float* __restrict__ rows, long long nrows, int chunks, int C,
+                                                                           const int* __restrict__ labels, int n_labels,
+                                                                           float* __restrict__ out0, float* __restrict__ out1) {
+    __shared__ double red[RLN][RC];
+    const int cl = threadIdx.x % RC, rl = threadIdx.x / RC;
+    const int c = blockIdx.x * RC + cl, v = blockIdx.y, label = blockIdx.z;
+    double s = 0.;
+    if (c < C) {
+        const float* base = rows + (long long)v * nrows * C + c;
+        for (long long r = rl; r < nrows; r += RLN) {
+            const int l = min(max(labels[r / chunks], 0), n_labels - 1);       // wave-uniform: a wave is one row lane
+            if (l == label) s += (double)base[r * C];
+        }
+    }
+    red[rl][cl] = s;
+    __syncthreads();
+    if (rl == 0 && c < C) {
+        double t = 0.;
+#pragma unroll
+        for (int k = 0; k < RLN; ++k) t += red[k][cl];
+        (v == 0 ? out0 : out1)[(long long)label * C + c] = (float)t;
+    }
+}
+
+// out[n][c] = table[label(n)][c]: the row gather of the composed (any channel count) conditional operator; its adjoint is
+// ln_rows_reduce_by_label_kernel over the [N][C] rows (chunks = 1)
+__global__ __launch_bounds__(NT) void ln_rows_gather_kernel(const float* __restrict__ table, const int* __restrict__ labels, int n_labels, long long total,
+                                                            int C, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= total) return;
+    const int l = min(max(labels[i / C], 0), n_labels - 1);
+    out[i] = table[(long long)l * C + (int)(i % C)];
+}
+
 int chunks_of(long long D) { return (int)((D + CHUNK - 1) / CHUNK); }
 
 bool ln_ok(long long D, int C) { return C > 0 && C % 4 == 0 && (NT * 4) % C == 0 && D % C == 0; }
+
+size_t ln_ws_bytes(int N, long long D, int C) {
+    const size_t ch = (size_t)chunks_of(D);
+    return (size_t)N * ch * 5 * sizeof(double) + (size_t)2 * N * ch * C * sizeof(float);
+}
+
+// the parameter-gradient reduction of the partial rows: per column, or per (label, column)
+void reduce_rows(const float* rows, int N, int ch, int C, int nv, const int* labels, int n_labels, float* out0, float* out1, hipStream_t st) {
+    if (labels)
+        hipLaunchKernelGGL(ln_rows_reduce_by_label_kernel, dim3((C + RC - 1) / RC, nv, n_labels), dim3(RC * RLN), 0, st, rows, (long long)N * ch, ch, C,
+                           labels, n_labels, out0, out1);
+    else
+        hipLaunchKernelGGL(ln_rows_reduce_kernel, dim3((C + RC - 1) / RC, nv), dim3(RC * RLN), 0, st, rows, (long long)N * ch, C, out0, out1);
+}
+
+// labels == nullptr: the unconditional operator (scale / offset [C]); else the [n_labels, C] tables
+template <bool COND>
+int ln_fwd(const char* what, const float* x, const float* scale, const float* offset, const int* labels, int n_labels, float* y, float* mean,
+           float* rstd, int N, long long D, int C, float eps, int relu, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!x || !scale || !offset || !y || !mean || !rstd || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
+    const dim3 grid(chunks_of(D), N);
+    double* part = (double*)ws;
+    hipLaunchKernelGGL((ln_partial_kernel<0, false>), grid, dim3(NT), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, D, C, nullptr, 0, part);
+    hipLaunchKernelGGL(ln_fwd_apply_kernel<COND>, grid, dim3(NT), 0, st, x, scale, offset, part, D, C, eps, relu, labels, n_labels, y, mean, rstd);
+    return ctgan_check_launch(what);
+}
+
+template <bool COND>
+int ln_bwd(const char* what, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd, const float* ymask,
+           const int* labels, int n_labels, float* gx, float* gscale, float* goffset, int N, long long D, int C, void* ws, size_t ws_bytes,
+           hipStream_t st) {
+    if (!gy || !x || !scale || !mean || !rstd || !gx || N <= 0 || (!gscale) != (!goffset) || (COND && (!labels || n_labels <= 0)))
+        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
+    const int ch = chunks_of(D);
+    const dim3 grid(ch, N);
+    double* part = (double*)ws;
+    float* rows = gscale ? (float*)(part + (size_t)N * ch * 5) : nullptr;
+    hipLaunchKernelGGL((ln_partial_kernel<1, COND>), grid, dim3(NT), 0, st, x, gy, nullptr, scale, mean, rstd, ymask, D, C, labels, n_labels, part);
+    hipLaunchKernelGGL(ln_bwd_apply_kernel<COND>, grid, dim3(NT), 0, st, gy, x, scale, mean, rstd, ymask, part, D, C, labels, n_labels, gx, rows);
+    if (rows) reduce_rows(rows, N, ch, C, 2, labels, n_labels, gscale, goffset, st);
+    return ctgan_check_launch(what);
+}
+
+template <bool COND>
+int ln_bwd2(const char* what, const float* u, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd,
+            const float* ymask, const int* labels, int n_labels, float* cot_gy, float* cot_x, float* cot_scale, int N, long long D, int C,
+            void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!u || !gy || !x || !scale || !mean || !rstd || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
+    const int ch = chunks_of(D);
+    const dim3 grid(ch, N);
+    double* part = (double*)ws;
+    float* rows = cot_scale ? (float*)(part + (size_t)N * ch * 5) : nullptr;
+    hipLaunchKernelGGL((ln_partial_kernel<2, COND>), grid, dim3(NT), 0, st, x, gy, u, scale, mean, rstd, ymask, D, C, labels, n_labels, part);
+    hipLaunchKernelGGL(ln_bwd2_apply_kernel<COND>, grid, dim3(NT), 0, st, u, gy, x, scale, mean, rstd, ymask, part, D, C, labels, n_labels, cot_gy, cot_x, rows);
+    if (rows) reduce_rows(rows, N, ch, C, 1, labels, n_labels, cot_scale, cot_scale, st);
+    return ctgan_check_launch(what);
+}
 
 }  // namespace
 
@@ -274,56 +403,60 @@ extern "C" {
 
 int ctgan_layernorm_supported(int64_t D, int32_t C) { return ln_ok(D, C) ? 1 : 0; }
 
-size_t ctgan_layernorm_workspace_bytes(int32_t N, int64_t D, int32_t C) {
-    const size_t ch = (size_t)chunks_of(D);
-    return (size_t)N * ch * 5 * sizeof(double) + (size_t)2 * N * ch * C * sizeof(float);
-}
+size_t ctgan_layernorm_workspace_bytes(int32_t N, int64_t D, int32_t C) { return ln_ws_bytes(N, D, C); }
 
 int ctgan_layernorm_fwd(const float* x, const float* scale, const float* offset, float* y, float* mean, float* rstd, int32_t N,
                         int64_t D, int32_t C, float eps, int32_t relu, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
-    if (!x || !scale || !offset || !y || !mean || !rstd || N <= 0) return ctgan_fail(CTGAN_E_BADARG, "layernorm_fwd: bad argument");
-    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "layernorm_fwd: D=%lld C=%d outside the fused kernels", (long long)D, C);
-    if (ws_bytes < ctgan_layernorm_workspace_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "layernorm_fwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(chunks_of(D), N);
-    double* part = (double*)ws;
-    hipLaunchKernelGGL(ln_partial_kernel<0>, grid, dim3(NT), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (long long)D, C, part);
-    hipLaunchKernelGGL(ln_fwd_apply_kernel, grid, dim3(NT), 0, st, x, scale, offset, part, (long long)D, C, eps, (int)relu, y, mean, rstd);
-    return ctgan_check_launch("layernorm_fwd");
+    return ln_fwd<false>("layernorm_fwd", x, scale, offset, nullptr, 0, y, mean, rstd, N, (long long)D, C, eps, (int)relu, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ctgan_layernorm_bwd(const float* gy, const float* x, const float* scale, const float* mean, const float* rstd, const float* ymask,
                         float* gx, float* gscale, float* goffset, int32_t N, int64_t D, int32_t C, void* ws, size_t ws_bytes,
                         ctgan_stream_t stream) {
-    if (!gy || !x || !scale || !mean || !rstd || !gx || N <= 0 || (!gscale) != (!goffset)) return ctgan_fail(CTGAN_E_BADARG, "layernorm_bwd: bad argument");
-    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "layernorm_bwd: D=%lld C=%d outside the fused kernels", (long long)D, C);
-    if (ws_bytes < ctgan_layernorm_workspace_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "layernorm_bwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_of(D);
-    const dim3 grid(ch, N);
-    double* part = (double*)ws;
-    float* rows = gscale ? (float*)(part + (size_t)N * ch * 5) : nullptr;
-    hipLaunchKernelGGL(ln_partial_kernel<1>, grid, dim3(NT), 0, st, x, gy, nullptr, scale, mean, rstd, ymask, (long long)D, C, part);
-    hipLaunchKernelGGL(ln_bwd_apply_kernel, grid, dim3(NT), 0, st, gy, x, scale, mean, rstd, ymask, part, (long long)D, C, gx, rows);
-    if (rows) hipLaunchKernelGGL(ln_rows_reduce_kernel, dim3((C + RC - 1) / RC, 2), dim3(RC * RLN), 0, st, rows, (long long)N * ch, C, gscale, goffset);
-    return ctgan_check_launch("layernorm_bwd");
+    return ln_bwd<false>("layernorm_bwd", gy, x, scale, mean, rstd, ymask, nullptr, 0, gx, gscale, goffset, N, (long long)D, C, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ctgan_layernorm_bwd2(const float* u, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd,
                          const float* ymask, float* cot_gy, float* cot_x, float* cot_scale, int32_t N, int64_t D, int32_t C, void* ws,
                          size_t ws_bytes, ctgan_stream_t stream) {
-    if (!u || !gy || !x || !scale || !mean || !rstd || N <= 0) return ctgan_fail(CTGAN_E_BADARG, "layernorm_bwd2: bad argument");
-    if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "layernorm_bwd2: D=%lld C=%d outside the fused kernels", (long long)D, C);
-    if (ws_bytes < ctgan_layernorm_workspace_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "layernorm_bwd2: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_of(D);
-    const dim3 grid(ch, N);
-    double* part = (double*)ws;
-    float* rows = cot_scale ? (float*)(part + (size_t)N * ch * 5) : nullptr;
-    hipLaunchKernelGGL(ln_partial_kernel<2>, grid, dim3(NT), 0, st, x, gy, u, scale, mean, rstd, ymask, (long long)D, C, part);
-    hipLaunchKernelGGL(ln_bwd2_apply_kernel, grid, dim3(NT), 0, st, u, gy, x, scale, mean, rstd, ymask, part, (long long)D, C, cot_gy, cot_x, rows);
-    if (rows) hipLaunchKernelGGL(ln_rows_reduce_kernel, dim3((C + RC - 1) / RC, 1), dim3(RC * RLN), 0, st, rows, (long long)N * ch, C, cot_scale, cot_scale);
-    return ctgan_check_launch("layernorm_bwd2");
+    return ln_bwd2<false>("layernorm_bwd2", u, gy, x, scale, mean, rstd, ymask, nullptr, 0, cot_gy, cot_x, cot_scale, N, (long long)D, C, ws, ws_bytes,
+                          (hipStream_t)stream);
+}
+
+int ctgan_layernorm_cond_fwd(const float* x, const float* scale, const float* offset, const int32_t* labels, int32_t n_labels, float* y,
+                             float* mean, float* rstd, int32_t N, int64_t D, int32_t C, float eps, int32_t relu, void* ws, size_t ws_bytes,
+                             ctgan_stream_t stream) {
+    return ln_fwd<true>("layernorm_cond_fwd", x, scale, offset, labels, n_labels, y, mean, rstd, N, (long long)D, C, eps, (int)relu, ws, ws_bytes,
+                        (hipStream_t)stream);
+}
+
+int ctgan_layernorm_cond_bwd(const float* gy, const float* x, const float* scale, const float* mean, const float* rstd, const float* ymask,
+                             const int32_t* labels, int32_t n_labels, float* gx, float* gscale, float* goffset, int32_t N, int64_t D, int32_t C,
+                             void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    return ln_bwd<true>("layernorm_cond_bwd", gy, x, scale, mean, rstd, ymask, labels, n_labels, gx, gscale, goffset, N, (long long)D, C, ws, ws_bytes,
+                        (hipStream_t)stream);
+}
+
+int ctgan_layernorm_cond_bwd2(const float* u, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd,
+                              const float* ymask, const int32_t* labels, int32_t n_labels, float* cot_gy, float* cot_x, float* cot_scale,
+                              int32_t N, int64_t D, int32_t C, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+    return ln_bwd2<true>("layernorm_cond_bwd2", u, gy, x, scale, mean, rstd, ymask, labels, n_labels, cot_gy, cot_x, cot_scale, N, (long long)D, C, ws,
+                         ws_bytes, (hipStream_t)stream);
+}
+
+int ctgan_layernorm_rows_gather(const float* table, const int32_t* labels, int32_t n_labels, float* out, int32_t N, int32_t C,
+                                ctgan_stream_t stream) {
+    if (!table || !labels || !out || N <= 0 || C <= 0 || n_labels <= 0) return ctgan_fail(CTGAN_E_BADARG, "layernorm_rows_gather: bad argument");
+    const long long total = (long long)N * C;
+    hipLaunchKernelGGL(ln_rows_gather_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, table, labels, n_labels, total, C, out);
+    return ctgan_check_launch("layernorm_rows_gather");
+}
+
+int ctgan_layernorm_rows_sum_by_label(const float* rows, const int32_t* labels, int32_t n_labels, float* out, int32_t N, int32_t C,
+                                      ctgan_stream_t stream) {
+    if (!rows || !labels || !out || N <= 0 || C <= 0 || n_labels <= 0) return ctgan_fail(CTGAN_E_BADARG, "layernorm_rows_sum_by_label: bad argument");
+    reduce_rows(rows, N, 1, C, 1, labels, n_labels, out, out, (hipStream_t)stream);
+    return ctgan_check_launch("layernorm_rows_sum_by_label");
 }
 
 }  // extern "C"

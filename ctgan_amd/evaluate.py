@@ -196,7 +196,8 @@ class Evaluator:
         with torch.no_grad():
             gp, _ = F.gradient_penalty(grads.detach(), cfg.GP_LAMBDA)
             # dropout passes 1 and 2 share the trunk; pass 2 is needed on the real rows only
-            h = R.DiscriminatorTrunk(rf)
+            lab_c = R.critic_labels(labels)          # the label-conditioned Layernorm critic: one label per row of every stacked pass
+            h = R.DiscriminatorTrunk(rf, torch.cat([lab_c, lab_c], 0) if lab_c is not None else None)
             if fuse_heads:
                 y = R.DiscriminatorTailBody(h, 0.8, 0.5, 0.5, rng=rng, mask_done=True, cat_extra=n)
                 return F.critic_tail_heads(y, P('Discriminator.Output.W'), P('Discriminator.Output.b'),
@@ -207,7 +208,8 @@ class Evaluator:
                 p1r, p1f, p2r = (_cat_masks(rnds, 'u_pass1', slice(0, B)), _cat_masks(rnds, 'u_pass1', slice(B, 2 * B)),
                                  _cat_masks(rnds, 'u_pass2', slice(0, B)))
                 u = [torch.cat([a, b, c], 0) for a, b, c in zip(p1r, p1f, p2r)]
-            d_all, f_all, a_all = R.DiscriminatorTail(torch.cat([h, h[:n]], 0), 0.8, 0.5, 0.5, u=u, rng=rng)
+            d_all, f_all, a_all = R.DiscriminatorTail(torch.cat([h, h[:n]], 0), 0.8, 0.5, 0.5, u=u, rng=rng,
+                                                      labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None)
             return F.critic_heads(d_all, f_all, a_all if use_ac else None, labels, n, cfg.LAMBDA_2, cfg.Factor_M,
                                   cfg.ACGAN_SCALE if use_ac else 0.0, gp)[0]
 

@@ -1622,28 +1622,134 @@ class LayerNormBwdFn(Function):
         return cg, cx, cs, None, None, None, None
 
 
-def layer_norm(x, scale, offset, eps=1e-5, relu=False):
+class CondLayerNormFn(Function):
+    """LayerNormFn with [n_labels, C] scale / offset tables, sample n reading row labels[n] (LS/tflib/ops/layernorm.py:21-30): the
+    same fused kernels reading another table row per sample; the table gradients are by-label reductions of the same partial rows."""
+
+    @staticmethod
+    def forward(ctx, x, scale, offset, labels, eps, relu):
+        y, mean, rstd = K.layernorm_cond_fwd(x, scale, offset, labels, eps, relu)
+        ctx.relu = bool(relu)
+        if relu:
+            ctx.save_for_backward(x, scale, labels, mean, rstd, y)
+        else:
+            ctx.save_for_backward(x, scale, labels, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, scale, labels, mean, rstd = ctx.saved_tensors[:5]
+        ymask = ctx.saved_tensors[5].detach() if ctx.relu else None       # a constant of every derivative order
+        want_params = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if want_params:
+            gx, gs, go = CondLayerNormBwdFn.apply(gy, x, scale, labels, mean, rstd, ymask, True)
+            return gx, gs, go, None, None, None
+        return CondLayerNormBwdFn.apply(gy, x, scale, labels, mean, rstd, ymask, False), None, None, None, None, None
+
+
+class CondLayerNormBwdFn(Function):
+    """(gy, x, scale table) -> gx [, gscale, goffset tables]; the label-conditioned LayerNormBwdFn."""
+
+    @staticmethod
+    def forward(ctx, gy, x, scale, labels, mean, rstd, ymask, want_params):
+        gx, gs, go = K.layernorm_cond_bwd(gy, x, scale, labels, mean, rstd, want_params, ymask)
+        ctx.has_mask = ymask is not None
+        if ymask is not None:
+            ctx.save_for_backward(gy, x, scale, labels, mean, rstd, ymask)
+        else:
+            ctx.save_for_backward(gy, x, scale, labels, mean, rstd)
+        ctx.set_materialize_grads(False)
+        if want_params:
+            return gx, gs, go
+        return gx
+
+    @staticmethod
+    def backward(ctx, u, u_s=None, u_o=None):
+        if u_s is not None or u_o is not None:
+            raise NotImplementedError('derivatives of the Layernorm parameter gradients (third order) are not used by any loss')
+        if u is None:
+            return None, None, None, None, None, None, None, None
+        if torch.is_grad_enabled():
+            raise NotImplementedError('third-order derivatives through Layernorm')
+        gy, x, scale, labels, mean, rstd = ctx.saved_tensors[:6]
+        ymask = ctx.saved_tensors[6] if ctx.has_mask else None
+        cg, cx, cs = K.layernorm_cond_bwd2(u, gy, x, scale, labels, mean, rstd, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                           ctx.needs_input_grad[2], ymask)
+        return cg, cx, cs, None, None, None, None, None
+
+
+class RowsGatherFn(Function):
+    """[n_labels, C] table -> its rows labels[n], [N, C]; linear, adjoint = RowsSumByLabelFn."""
+
+    @staticmethod
+    def forward(ctx, table, labels):
+        ctx.n_labels = table.shape[0]
+        ctx.save_for_backward(labels)
+        return K.rows_gather(table, labels)
+
+    @staticmethod
+    def backward(ctx, g):
+        (labels,) = ctx.saved_tensors
+        return RowsSumByLabelFn.apply(g.contiguous(), labels, ctx.n_labels), None
+
+
+class RowsSumByLabelFn(Function):
+    @staticmethod
+    def forward(ctx, rows, labels, n_labels):
+        ctx.save_for_backward(labels)
+        return K.rows_sum_by_label(rows, labels, n_labels)
+
+    @staticmethod
+    def backward(ctx, g):
+        (labels,) = ctx.saved_tensors
+        return RowsGatherFn.apply(g.contiguous(), labels), None, None
+
+
+def layer_norm(x, scale, offset, eps=1e-5, relu=False, labels=None):
     """Per-sample normalisation over all non-batch axes, then per-channel scale / offset (TF/tflib/ops/layernorm.py);
-    relu=True also applies the nonlinearity that follows it in the critics' blocks (fused kernels: same pass)."""
+    relu=True also applies the nonlinearity that follows it in the critics' blocks (fused kernels: same pass).  With `labels`
+    (int32 [N]) scale / offset are [n_labels, C] tables and sample n uses row labels[n] (LS/tflib/ops/layernorm.py:21-30)."""
     if x.dim() == 4 and not x.permute(0, 2, 3, 1).is_contiguous():
         x = to_channels_last(x)
     elif x.dim() == 2:
         x = x.contiguous()
+    if labels is not None:
+        if scale.dim() != 2 or tuple(scale.shape) != tuple(offset.shape) or labels.shape[0] != x.shape[0]:
+            raise ValueError('layer_norm with labels: scale / offset are [n_labels, C] tables, labels one per sample')
+        labels = labels.to(torch.int32).contiguous()
+        if LN_FUSED and K.layernorm_supported(x):
+            return CondLayerNormFn.apply(x, scale, offset, labels, float(eps), bool(relu))
+        y = layer_norm_cond_composed(x, scale, offset, labels, eps)
+        return globals()['relu'](y) if relu else y
     if LN_FUSED and K.layernorm_supported(x):
         return LayerNormFn.apply(x, scale, offset, float(eps), bool(relu))
     y = layer_norm_composed(x, scale, offset, eps)
     return globals()['relu'](y) if relu else y
 
 
-def layer_norm_composed(x, scale, offset, eps=1e-5):
-    """The same operator from five kernel-backed maps that are closed under differentiation (any channel count)."""
+def _normalised(x, eps):
     inv = 1.0 / x[0].numel()
     m = SampleSumFn.apply(x, inv)
     xc = AddFn.apply(x, SampleBcastFn.apply(m, x, 1.0), 1.0, -1.0)
     v = SampleSumFn.apply(MulFn.apply(xc, xc), inv)               # biased variance (tf.nn.moments)
     r = RsqrtFn.apply(v, float(eps))
-    xh = MulFn.apply(xc, SampleBcastFn.apply(r, x, 1.0))
-    return ChannelAffineFn.apply(xh, scale, offset)
+    return MulFn.apply(xc, SampleBcastFn.apply(r, x, 1.0))
+
+
+def layer_norm_cond_composed(x, scale, offset, labels, eps=1e-5):
+    """The label-conditioned operator from the closed maps of layer_norm_composed plus a row gather of the tables (any channel count):
+    y = xh * scale[labels[n], c] + offset[labels[n], c]."""
+    xh = _normalised(x, eps)
+    s, o = RowsGatherFn.apply(scale, labels), RowsGatherFn.apply(offset, labels)
+    if x.dim() == 4:
+        H, W = x.shape[2], x.shape[3]
+        s, o = SpatialBcastFn.apply(s, H, W, 1.0), SpatialBcastFn.apply(o, H, W, 1.0)
+    return AddFn.apply(MulFn.apply(xh, s), o, 1.0, 1.0)
+
+
+def layer_norm_composed(x, scale, offset, eps=1e-5):
+    """The same operator from five kernel-backed maps that are closed under differentiation (any channel count)."""
+    return ChannelAffineFn.apply(_normalised(x, eps), scale, offset)
 
 
 # --------------------------------------------------------------------------------- loss heads

@@ -71,6 +71,8 @@ FUSE_RELU = _os.environ.get('CTGAN_FUSE_RELU', '1') != '0'
 def configure(**kw):
     global cfg
     cfg = Config(**kw)
+    if cfg.CONDITIONAL and (not cfg.ACGAN) and (not cfg.NORMALIZATION_D):
+        print("WARNING! Conditional model without normalization in D might be effectively unconditional!")      # :58-59
     return cfg
 
 
@@ -98,7 +100,10 @@ def Normalize(name, inputs, labels=None, groups=1, relu=False):
     if cfg.CONDITIONAL and cfg.ACGAN and ('Discriminator' in name):
         labels = None
     if ('Discriminator' in name) and cfg.NORMALIZATION_D:
-        return _ln.Layernorm(name, [1, 2, 3], inputs)        # :76-77 (the main-tree op takes no labels, layernorm.py:6)
+        # :76-77.  The script passes labels / n_labels, which the main tree's operator (TF/tflib/ops/layernorm.py:6) would reject:
+        # the LSUN tree's operator (LS/tflib/ops/layernorm.py:6-34) is followed - per-label [10, C] scale / offset tables when the
+        # labels survive the two filters above (CONDITIONAL and not ACGAN)
+        return _ln.Layernorm(name, [1, 2, 3], inputs, labels=labels, n_labels=10 if labels is not None else None)
     elif ('Generator' in name) and cfg.NORMALIZATION_G:
         if labels is not None:
             return _cbn.Batchnorm(name, [0, 2, 3], inputs, labels=labels, n_labels=10, groups=groups, relu=relu)
@@ -263,12 +268,18 @@ def _fused_output_stage(h, G, groups):
         return None
 
 
-def DiscriminatorTrunk(inputs):
-    """Blocks 1-2 of the critic: everything before the first dropout (:170-172)."""
+def critic_labels(labels):
+    """The labels the critic's blocks consume: only the label-conditioned Layernorm (CONDITIONAL, not ACGAN, NORMALIZATION_D: Normalize)
+    reads them, so every other configuration passes None and takes exactly the label-free launches."""
+    return labels if (cfg.CONDITIONAL and not cfg.ACGAN and cfg.NORMALIZATION_D) else None
+
+
+def DiscriminatorTrunk(inputs, labels=None):
+    """Blocks 1-2 of the critic: everything before the first dropout (:170-172).  `labels`: one per row of `inputs`."""
     D = cfg.DIM_D
     out = inputs.reshape(-1, 3, 32, 32)
     out = OptimizedResBlockDisc1(out)
-    return ResidualBlock('Discriminator.2', D, D, 3, out, resample='down')
+    return ResidualBlock('Discriminator.2', D, D, 3, out, resample='down', labels=labels)
 
 
 def _tail_fusable(kp1, kp2, kp3, u, rng):
@@ -276,7 +287,7 @@ def _tail_fusable(kp1, kp2, kp3, u, rng):
             and max(kp1, kp2, kp3) < 1.0)
 
 
-def DiscriminatorTailBody(h, kp1, kp2, kp3, u=None, rng=None, mask_done=False, cat_extra=0, specs=None):
+def DiscriminatorTailBody(h, kp1, kp2, kp3, u=None, rng=None, mask_done=False, cat_extra=0, specs=None, labels=None):
     """dropout -> block 3 -> dropout -> block 4 -> dropout -> relu (:173-179).  mask_done (fused path only): the consumer
     of the result returns the gradient w.r.t. the last conv's result, relu/dropout mask included (F.critic_tail_heads,
     F.gp_head_grad)."""
@@ -301,18 +312,18 @@ def DiscriminatorTailBody(h, kp1, kp2, kp3, u=None, rng=None, mask_done=False, c
         return F.dropout(x, kp, u[i]) if u is not None else F.dropout(x, kp, rng=rng)
 
     out = drop(0, h, kp1)
-    out = ResidualBlock('Discriminator.3', D, D, 3, out, resample=None)
+    out = ResidualBlock('Discriminator.3', D, D, 3, out, resample=None, labels=labels)
     out = drop(1, out, kp2)
-    out = ResidualBlock('Discriminator.4', D, D, 3, out, resample=None)
+    out = ResidualBlock('Discriminator.4', D, D, 3, out, resample=None, labels=labels)
     out = drop(2, out, kp3)
     return nonlinearity(out)
 
 
-def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan')):
+def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan'), labels=None):
     """dropout -> block 3 -> dropout -> block 4 -> dropout -> relu -> mean -> heads (:173-186).
     `heads`: which of the two linear heads the caller consumes (the other one is not launched)."""
     D = cfg.DIM_D
-    out = DiscriminatorTailBody(h, kp1, kp2, kp3, u=u, rng=rng)
+    out = DiscriminatorTailBody(h, kp1, kp2, kp3, u=u, rng=rng, labels=labels)
     output2 = F.spatial_mean(out)
     output_wgan = _linear.Linear('Discriminator.Output', D, 1, output2).reshape(-1) if 'wgan' in heads else None
     if cfg.CONDITIONAL and cfg.ACGAN and 'acgan' in heads:
@@ -324,7 +335,8 @@ def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan'
 def Discriminator(inputs, labels, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan')):
     """:169-186 - returns (D [n], D_ [n,DIM_D], acgan logits [n,10] or None).
     `u` = the three dropout uniforms [n,DIM_D,8,8] (explicit draws); else drawn from `rng`."""
-    return DiscriminatorTail(DiscriminatorTrunk(inputs), kp1, kp2, kp3, u=u, rng=rng, heads=heads)
+    labels = critic_labels(labels)
+    return DiscriminatorTail(DiscriminatorTrunk(inputs, labels), kp1, kp2, kp3, u=u, rng=rng, heads=heads, labels=labels)
 
 
 def build_params(device=None):
@@ -519,7 +531,8 @@ class Trainer:
             with F.tape_replay(tape, 0, 2 * B):
                 h = DiscriminatorTrunk(rf)
         else:
-            h = DiscriminatorTrunk(rf)
+            lab_c = critic_labels(labels)           # (the stacked [real ; fake] pass reads [labels ; labels], :220-225)
+            h = DiscriminatorTrunk(rf, _cat_rows(lab_c, lab_c) if lab_c is not None else None)
         if rnd is not None:
             u = [_cat_rows(a, b[:B]) for a, b in zip(rnd['u_pass1'], rnd['u_pass2'])]
         else:
@@ -549,7 +562,9 @@ class Trainer:
                 slopes if HEADS_FOLD else None, cfg.GP_LAMBDA, y_clean, False)
         else:
             tail_in = _cat_rows(h, h[:B])
-            d_all, f_all, a_all = DiscriminatorTail(tail_in, 0.8, 0.5, 0.5, u=u, rng=rng)
+            lab_c = critic_labels(labels)           # rows: real, fake (pass 1), real (pass 2)
+            d_all, f_all, a_all = DiscriminatorTail(tail_in, 0.8, 0.5, 0.5, u=u, rng=rng,
+                                                    labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None)
             # every loss head of the two dropout passes in one kernel (fwd) / one kernel (bwd): wgan :244, CT :288-291, ACGAN :246-248
             cost, wgan, ct, acgan, disc_wgan = F.critic_heads(d_all, f_all, a_all if use_ac else None, labels, B, cfg.LAMBDA_2,
                                                               cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, gp)

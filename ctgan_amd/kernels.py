@@ -1351,6 +1351,78 @@ def layernorm_bwd2(u, gy, x, scale, mean, rstd, want_gy=True, want_x=True, want_
     return cg, cx, cs
 
 
+def _ln_tables(x, labels, *tables):
+    """(N, D, C, n_labels) of a label-conditioned call: labels int32 [N] on the device, tables contiguous [n_labels, C]."""
+    N, D, C = _ln_dims(x)
+    n_labels = tables[0].shape[0]
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (N,), 'labels: int32 [N]'
+    for t in tables:
+        assert tuple(t.shape) == (n_labels, C) and t.is_contiguous(), 'scale / offset tables: contiguous [n_labels, C]'
+    return N, D, C, n_labels
+
+
+def layernorm_cond_fwd(x, scale, offset, labels, eps, relu=False):
+    """layernorm_fwd with [n_labels, C] scale / offset tables, sample n reading row labels[n] (LS/tflib/ops/layernorm.py:21-30)
+    -> (y, mean [N], rstd [N])"""
+    _need_dev(x, scale, offset, labels)
+    N, D, C, L = _ln_tables(x, labels, scale, offset)
+    y = _ew_out(x)
+    mean = torch.empty(N, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(N, dtype=torch.float32, device=x.device)
+    ws = _ln_ws(N, D, C, x.device)
+    check(lib.ctgan_layernorm_cond_fwd(_ptr(x), _ptr(scale), _ptr(offset), _ptr(labels), L, _ptr(y), _ptr(mean), _ptr(rstd), N, D, C, float(eps),
+                                       1 if relu else 0, _ptr(ws), ws.numel(), _stream()), 'layernorm_cond_fwd')
+    return y, mean, rstd
+
+
+def layernorm_cond_bwd(gy, x, scale, labels, mean, rstd, want_params, ymask=None):
+    """-> (gx, gscale | None, goffset | None), the parameter gradients [n_labels, C] (a zero row for a label absent from the batch)"""
+    _need_dev(gy, x, scale, labels, mean, rstd, ymask)
+    N, D, C, L = _ln_tables(x, labels, scale)
+    gy = match_layout(gy, x)
+    gx = _ew_out(x)
+    gs = torch.empty((L, C), dtype=torch.float32, device=x.device) if want_params else None
+    go = torch.empty((L, C), dtype=torch.float32, device=x.device) if want_params else None
+    ws = _ln_ws(N, D, C, x.device)
+    check(lib.ctgan_layernorm_cond_bwd(_ptr(gy), _ptr(x), _ptr(scale), _ptr(mean), _ptr(rstd), _ptr(ymask), _ptr(labels), L, _ptr(gx), _ptr(gs), _ptr(go),
+                                       N, D, C, _ptr(ws), ws.numel(), _stream()), 'layernorm_cond_bwd')
+    return gx, gs, go
+
+
+def layernorm_cond_bwd2(u, gy, x, scale, labels, mean, rstd, want_gy=True, want_x=True, want_scale=True, ymask=None):
+    """Adjoint of layernorm_cond_bwd: cotangent u of gx -> (cot_gy, cot_x, cot_scale [n_labels, C]), None where not wanted."""
+    _need_dev(u, gy, x, scale, labels, mean, rstd, ymask)
+    N, D, C, L = _ln_tables(x, labels, scale)
+    u, gy = match_layout(u, x), match_layout(gy, x)
+    cg = _ew_out(x) if want_gy else None
+    cx = _ew_out(x) if want_x else None
+    cs = torch.empty((L, C), dtype=torch.float32, device=x.device) if want_scale else None
+    ws = _ln_ws(N, D, C, x.device)
+    check(lib.ctgan_layernorm_cond_bwd2(_ptr(u), _ptr(gy), _ptr(x), _ptr(scale), _ptr(mean), _ptr(rstd), _ptr(ymask), _ptr(labels), L, _ptr(cg), _ptr(cx),
+                                        _ptr(cs), N, D, C, _ptr(ws), ws.numel(), _stream()), 'layernorm_cond_bwd2')
+    return cg, cx, cs
+
+
+def rows_gather(table, labels):
+    """[n_labels, C] table, int32 labels [N] -> [N, C] rows (labels clamped to the table)."""
+    _need_dev(table, labels)
+    assert table.dim() == 2 and table.is_contiguous() and labels.dtype == torch.int32 and labels.is_contiguous()
+    N, (L, C) = labels.shape[0], table.shape
+    out = torch.empty((N, C), dtype=torch.float32, device=table.device)
+    check(lib.ctgan_layernorm_rows_gather(_ptr(table), _ptr(labels), L, _ptr(out), N, C, _stream()), 'layernorm_rows_gather')
+    return out
+
+
+def rows_sum_by_label(rows, labels, n_labels):
+    """Adjoint of rows_gather: rows [N, C] -> [n_labels, C], the fixed-order sum of the rows that carry each label."""
+    _need_dev(rows, labels)
+    assert rows.dim() == 2 and rows.is_contiguous() and labels.dtype == torch.int32 and labels.is_contiguous()
+    N, C = rows.shape
+    out = torch.empty((n_labels, C), dtype=torch.float32, device=rows.device)
+    check(lib.ctgan_layernorm_rows_sum_by_label(_ptr(rows), _ptr(labels), n_labels, _ptr(out), N, C, _stream()), 'layernorm_rows_sum_by_label')
+    return out
+
+
 def spatial_sum(x, scale):
     """[N,C,H,W] channels-last -> [N,C], scale * sum over (h,w)."""
     _need_dev(x)

@@ -221,6 +221,29 @@ int ctgan_layernorm_bwd(const float* gy, const float* x, const float* scale, con
 int ctgan_layernorm_bwd2(const float* u, const float* gy, const float* x, const float* scale, const float* mean,
                          const float* rstd, const float* ymask, float* cot_gy, float* cot_x, float* cot_scale, int32_t N,
                          int64_t D, int32_t C, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+/* Label-conditioned twins (LS/tflib/ops/layernorm.py:21-30; the "vanilla" conditional critic of TF/CT_gan_cifar_resnet.py:70-87):
+ * scale / offset are row-major [n_labels, C] tables and sample n uses row labels[n] (int32 [N], device memory).  A label is
+ * clamped to [0, n_labels) inside the kernels, so no label can index outside the tables.  gscale / goffset / cot_scale are
+ * [n_labels, C]: per (label, channel) the fixed-order fp64 sum over the samples that carry the label (no float atomics, identical
+ * bits run to run), a written zero row for a label absent from the batch.  Same support predicate (ctgan_layernorm_supported) and
+ * workspace (ctgan_layernorm_workspace_bytes) as the unconditional maps; tables whose rows all equal one vector give y, gx,
+ * cot_gy and cot_x equal to the unconditional results bit for bit.                                                        */
+int ctgan_layernorm_cond_fwd(const float* x, const float* scale, const float* offset, const int32_t* labels, int32_t n_labels,
+                             float* y, float* mean, float* rstd, int32_t N, int64_t D, int32_t C, float eps, int32_t relu, void* ws,
+                             size_t ws_bytes, ctgan_stream_t stream);
+int ctgan_layernorm_cond_bwd(const float* gy, const float* x, const float* scale, const float* mean, const float* rstd,
+                             const float* ymask, const int32_t* labels, int32_t n_labels, float* gx, float* gscale, float* goffset,
+                             int32_t N, int64_t D, int32_t C, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+int ctgan_layernorm_cond_bwd2(const float* u, const float* gy, const float* x, const float* scale, const float* mean,
+                              const float* rstd, const float* ymask, const int32_t* labels, int32_t n_labels, float* cot_gy,
+                              float* cot_x, float* cot_scale, int32_t N, int64_t D, int32_t C, void* ws, size_t ws_bytes,
+                              ctgan_stream_t stream);
+/* The table side of the composed conditional operator (channel counts outside the fused kernels): out [N, C] = table[labels[n]]
+ * and its adjoint out [n_labels, C] = the by-label sum of rows [N, C] (same fixed-order fp64 reduction as above, labels clamped). */
+int ctgan_layernorm_rows_gather(const float* table, const int32_t* labels, int32_t n_labels, float* out, int32_t N, int32_t C,
+                                ctgan_stream_t stream);
+int ctgan_layernorm_rows_sum_by_label(const float* rows, const int32_t* labels, int32_t n_labels, float* out, int32_t N, int32_t C,
+                                      ctgan_stream_t stream);
 /* ---- 16-bit matrix-core family (csrc/igemm16.hip): BASELINE.json configs[1] "bf16" and configs[4] "fp16 MFMA conv" ----
  * The same three operators (tf.nn.conv2d TF/tflib/ops/conv2d.py:106-112, tf.nn.conv2d_transpose / the data gradient
  * TF/tflib/ops/deconv2d.py:91-103, the filter gradient tf.gradients derives) computed as mixed precision: operands rounded
