@@ -82,6 +82,7 @@ DEBUG_SIGNATURES = {
     'ctgan_debug_last_wgrad_group_kinds': (c_int, []),
     'ctgan_debug_last_wgrad_group_col_mask': (ctypes.c_uint, []),
     'ctgan_debug_x3_hk': (None, [c_int, c_int]),
+    'ctgan_debug_x3_halo_always': (None, [c_int]),
     'ctgan_debug_clock_probe': (c_int, [c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
 }
 
@@ -109,6 +110,7 @@ SIGNATURES = {
     'ctgan_conv2d_wgrad': (c_int, [_D, _p, _p, _p, _p, _p, c_size_t, c_int, _p]),
     'ctgan_conv2d16_supported': (c_int, [_D, c_int, c_int]),
     'ctgan_conv2d16_x3_prefers': (c_int, [_D, c_int]),
+    'ctgan_conv2d16_bn_in_takes': (c_int, [_D]),
     'ctgan_conv2d16_wgrad_col_takes': (c_int, [_D, c_int, c_int32]),
     'ctgan_conv2d16_filter_elems': (c_size_t, [_D, c_int, c_int]),
     'ctgan_conv2d16_pack_filter': (c_int, [_D, c_int, c_int, _p, _p, _p]),

@@ -2012,6 +2012,7 @@ int launch_conv16x3hf_t(const P16& p, const PatchGeom& pg, hipStream_t st) {
 // and the reduction, which more rounds do not amortise.  g_hk: 0 = never (tests / A-B: ctgan_debug_x3_hk), 1 = by the rule, 2 = every launch
 // that qualifies whatever its size.
 int g_hk = 1;
+int g_halo_always = 0;      // tests: ctgan_debug_x3_halo_always(1) = every launch the halo-patch kernels take rides them, whatever its size
 int g_hk_max_wgs = 256;      // one round of one workgroup per CU: beyond it the pixel-tiled kernels are level or ahead (profiles/r06_hk_prof.txt)
 bool conv16x3hk_takes(const P16& p, PatchGeom* out) {
     if (!g_hk || p.nph != 1 || p.stride != 1 || !p.Wf || p.bn_mean || p.act || p.C != 128 || p.Ng % 128 || p.M % 64) return false;
@@ -2110,6 +2111,17 @@ int launch_conv16x3sf(const P16& p, int bmp, hipStream_t st) {
     return bmp == 128 ? launch_conv16x3sf_t<false, 4>(p, st) : (bmp == 64 ? launch_conv16x3sf_t<false, 2>(p, st) : launch_conv16x3sf_t<false, 1>(p, st));
 }
 
+// Batch norm of the input on load (conv16x3hf_kernel<true, TN, true>): the tile of the fragment-streaming kernel whose tiles lie inside one
+// image (a tile's BN coefficients are those of ONE sample), 0 when the launch has none.  The launcher and the routing query
+// (ctgan_conv2d16_bn_in_takes) both ask here.
+int conv16x3hf_bn_tile(const P16& p, PatchGeom* pg) {
+    const int bmp = conv16x3hf_usable(p) ? conv16x3hf_tile(p) : 0;
+    PatchGeom g;
+    if (!bmp || !conv16x3h_ok(p, &g, bmp) || g.IMGS != 1) return 0;
+    if (pg) *pg = g;
+    return bmp;
+}
+
 int launch_conv16x3h(const P16& p, hipStream_t st) {
     {
         PatchGeom pk;                 // launches that cannot fill the chip with pixel tiles: one channel chunk per wave (conv16x3hk_kernel)
@@ -2119,8 +2131,8 @@ int launch_conv16x3h(const P16& p, hipStream_t st) {
     const bool prefer_v1 = !g_halo_version_override && x3_8x8_mode() == 0 && p.P * p.Q < 128 && conv16x3h_ok(p, nullptr) && (long long)(p.M / 128) * (p.Ng / 128) >= 192;
     if (p.bn_mean) {                  // batch norm of the input on load: the fragment-streaming kernel, tiles inside one image, ReLU behind the norm
         PatchGeom pg;
-        const int bmp = conv16x3hf_usable(p) ? conv16x3hf_tile(p) : 0;
-        if (!bmp || !conv16x3h_ok(p, &pg, bmp) || pg.IMGS != 1 || !p.relu_in)
+        const int bmp = conv16x3hf_bn_tile(p, &pg);
+        if (!bmp || !p.relu_in)
             return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv16x3hf: input batch norm needs the fragment-streaming halo kernel, tiles inside one image and relu_in");
         if (bmp == 128) return launch_conv16x3hf_t<true, 4, true>(p, pg, st);
         if (bmp == 64) return launch_conv16x3hf_t<true, 2, true>(p, pg, st);
@@ -2197,7 +2209,7 @@ int dispatch_conv16_tiles(const P16& p, bool small, hipStream_t st) {
     if constexpr (planes<MMA>() == 3) {
         // split mode: stride-1 whole-row tiles go to the halo-patch kernel; everything else to the slice kernels with three planes per
         // operand in LDS - 32-deep slices, the 128x128 tile with ONE 60 KB stage (two workgroups per CU)
-        const int halo = 1;
+        const int halo = g_halo_always ? 2 : 1;
         if (halo_takes(p)) {
             const int bmp = conv16x3hf_usable(p) ? conv16x3hf_tile(p) : 128;
             if (!small || halo == 2 || (bmp < 128 && (long long)(p.M / bmp) * (p.Ng / 128) >= 96)) return launch_conv16x3h(p, st);
@@ -2316,6 +2328,7 @@ void ctgan_debug_x3_halo_version(int version) { g_halo_version_override = versio
 void ctgan_debug_x3_s2halo(int on) { g_s2halo = on ? 1 : 0; }
 void ctgan_debug_x3_s2fwd(int on) { g_s2fwd = on ? 1 : 0; g_sf_ksplit = on == 2 ? 0 : 1; }
 void ctgan_debug_x3_s2dgrad_sf(int on) { g_s2dgrad_sf = on; }
+void ctgan_debug_x3_halo_always(int on) { g_halo_always = on ? 1 : 0; }
 void ctgan_debug_x3_hk(int mode, int max_wgs) { g_hk = mode; if (max_wgs > 0) g_hk_max_wgs = max_wgs; }
 static thread_local int g_last_group_kinds = 0;
 static thread_local unsigned g_last_group_col_mask = 0;
@@ -2384,6 +2397,17 @@ int ctgan_conv2d16_x3_prefers(const ctgan_conv_desc* d, int op) {
     }
     if (!conv16x3h_ok(p, nullptr)) return 0;
     return (long long)(p.M / 128) * (p.Ng / 128) >= 192 ? 1 : 0;
+}
+
+int ctgan_conv2d16_bn_in_takes(const ctgan_conv_desc* d) {
+    // the checks of conv2d16_fwd_impl and launch_conv16x3h for a forward launch with ctgan_epilogue_ext::in_bn_*, without the operands
+    if (!d || d->stride != 1 || !shape_ok_fwd(d) || !extents_ok(d, CTGAN_CONV_FWD, CTGAN_MMA_F32X3) || !frag_image_shape(d, CTGAN_CONV_FWD)) return 0;
+    P16 p{};
+    p.nph = 1; p.stride = d->stride;
+    p.ph_T[0] = d->R; p.ph_U[0] = d->S;
+    p.Ng = d->K; p.C = d->C; p.P = d->P; p.Q = d->Q; p.M = d->N * d->P * d->Q;
+    p.Wf = reinterpret_cast<const unsigned short*>(d);      // (any non-null value: the packed image of these shapes carries the FRAG copy)
+    return conv16x3hf_bn_tile(p, nullptr) ? 1 : 0;
 }
 
 static bool frag_image(const ctgan_conv_desc* d, int op, int mma) { return mma == CTGAN_MMA_F32X3 && frag_image_shape(d, op); }

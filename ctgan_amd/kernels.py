@@ -913,6 +913,12 @@ def debug_x3_hk(mode, max_wgs=0):
     lib.ctgan_debug_x3_hk(int(mode), int(max_wgs))
 
 
+def debug_x3_halo_always(on):
+    """Tests: True = the split mode runs every stride-1 launch its halo-patch kernels take on them, whatever its size (default: small launches
+    stay on the slice kernels) - a small launch then rides the kernel conv_fwd_bn_in uses."""
+    lib.ctgan_debug_x3_halo_always(1 if on else 0)
+
+
 if os.environ.get('CTGAN_X3_HK') is not None:      # (bench A/B: "0", "2", or "1:<max workgroups>")
     _hk = os.environ['CTGAN_X3_HK'].split(':')
     debug_x3_hk(int(_hk[0]), int(_hk[1]) if len(_hk) > 1 else 0)
@@ -1496,13 +1502,14 @@ def conv_fwd_bn_in_supported(x, g, tanh=False, labels=None, resid=None):
         return labels is None and resid is None
     if tanh:
         return False
-    if MMA_DTYPE == 'f32x3':
-        return True
-    if MMA_DTYPE is None and X3_HYBRID:
-        y_strides = (g.K * g.P * g.Q, 1, g.Q * g.K, g.K)          # channels-last result (empty_cl)
-        d = g.desc(x.shape[0], x.stride(), y_strides)
-        return bool(lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0))
-    return False
+    if not (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID)):
+        return False
+    y_strides = (g.K * g.P * g.Q, 1, g.Q * g.K, g.K)          # channels-last result (empty_cl)
+    d = g.desc(x.shape[0], x.stride(), y_strides)
+    # the launcher's own question (tiles of the fragment-streaming halo kernel inside one image); the fp32 mode also asks its routing
+    if not lib.ctgan_conv2d16_bn_in_takes(ctypes.byref(d)):
+        return False
+    return MMA_DTYPE == 'f32x3' or bool(lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0))
 
 
 def conv_fwd_bn_in(x, w, bias, g, mean, rstd, scale, offset, groups, relu_in=True, tanh=False, out_strides=None, labels=None, resid=None,

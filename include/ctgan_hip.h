@@ -268,6 +268,10 @@ int ctgan_conv2d16_supported(const ctgan_conv_desc* d, int op, int mma);        
  * on the fp32 MFMA entry points - the results carry fp32 accuracy either way.  A forward launch with prefers = 1 and stride 1 also
  * accepts CTGAN_RESID_UP.                                                                                                    */
 int ctgan_conv2d16_x3_prefers(const ctgan_conv_desc* d, int op);
+/* 1 when ctgan_conv2d16_fwd_ex (mma = CTGAN_MMA_F32X3, CTGAN_IN_RELU) takes this forward launch with the input batch norm on load
+ * (ctgan_epilogue_ext::in_bn_*): stride 1 on the fragment-streaming halo kernel with every tile inside one image.  The launcher asks
+ * the same function, so a caller that gets 1 here never computes the moments for a launch that is then refused.                   */
+int ctgan_conv2d16_bn_in_takes(const ctgan_conv_desc* d);
 /* 1 when the filter-column weight-gradient kernel (csrc/wgrad16c.hip) takes this problem over `rows` samples in mode mma - geometry, the
  * strides of x in d->xs (images dense in memory) and the 32-bit offset limits; callers that queue weight gradients for
  * ctgan_conv2d16_wgrad_group use it to tell the problems the grouped launch runs on that kernel from those it would run on the slice tiles. */

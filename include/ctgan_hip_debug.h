@@ -42,6 +42,9 @@ unsigned ctgan_debug_last_wgrad_group_col_mask(void);
    round 6) instead of the pixel-tiled kernels (or, at 64 rows, the fp32 pipe): mode 0 none, 1 (default) launches of at most max_wgs workgroups (default
    768; max_wgs <= 0 keeps the current value), 2 every launch that qualifies */
 void ctgan_debug_x3_hk(int mode, int max_wgs);
+/* tests only: 1 = the split mode sends every stride-1 launch its halo-patch kernels take to them, also the launches whose few tiles the
+   routing leaves on the slice kernels (0, default) - so that a small launch can be compared bit for bit with another route to the same kernel */
+void ctgan_debug_x3_halo_always(int on);
 /* bench.py's roofline leg: a one-wave kernel that reads s_memrealtime (constant 100 MHz) and s_memtime (shader cycles) when it starts, polls
    `*flag` (device int32; may be NULL) and reads both again when the flag is non-zero or after max_real_ticks (100 MHz ticks, <= 2 s): launched on a
    SIDE stream next to a measured launch, out[0..3] = real0, shader0, real1, shader1 give the shader clock sustained over that launch
