@@ -174,6 +174,11 @@ SIGNATURES = {
     'ctgan_bn_blend_stats': (c_int, [_p, c_int32, c_int32, c_int32, c_float, _p, _p, _p, _p, _p, c_size_t, _p]),
     'ctgan_bn_apply_ex': (c_int, [_p, _p, _p, c_int32, _p, _p, _p, c_float, _p, _p, c_int32, c_int32, c_int32, c_int32, _p]),
     'ctgan_bn_bwd_scaled': (c_int, [_p, _p, _p, _p, _p, _p, c_float, _p, _p, _p, c_int32, c_int32, c_int32, _p, c_size_t, _p]),
+    # batch norm with a folded LeakyReLU / tanh / gate, the gate alone (csrc/bn_act.hip)
+    'ctgan_bn_act_apply': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _p]),
+    'ctgan_bn_act_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _p, c_size_t, _p]),
+    'ctgan_gate_fwd': (c_int, [_p, _p, c_int64, _p]),
+    'ctgan_gate_bwd': (c_int, [_p, _p, _p, c_int64, _p]),
     'ctgan_elu_fwd': (c_int, [_p, _p, c_int64, _p]),
     'ctgan_elu_bwd': (c_int, [_p, _p, _p, _p, c_int64, _p]),
     'ctgan_global_norm_workspace_bytes': (c_size_t, [c_int64]),

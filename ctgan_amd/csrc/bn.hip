@@ -520,6 +520,19 @@ int launch_partial_f64(const float* x, const BnShape& s, double* part, hipStream
 
 }  // namespace
 
+void ctgan_bn_plan(int n, int hw, int* hc, int* pos) {
+    const BnShape s = mk(n, hw, 1, 1);
+    *hc = s.hc; *pos = s.pos;
+}
+
+int ctgan_bn_bwd_finalize(const double* part, const float* scale, int n, int hw, int c, int groups, float* gscale, float* goffset,
+                          float* s12, hipStream_t st) {
+    const BnShape s = mk(n, hw, c, groups);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((c + 63) / 64, 1 + groups), dim3(64 * 16), 0, st, part, scale,
+                       static_cast<const int32_t*>(nullptr), s, 1, gscale, goffset, s12, 1.0, static_cast<float*>(nullptr));
+    return ctgan_check_launch("bn_bwd_final");
+}
+
 extern "C" {
 
 size_t ctgan_bn_workspace_bytes(int32_t n, int32_t hw, int32_t c, int32_t groups, int32_t n_labels) {

@@ -21,6 +21,12 @@ static inline unsigned ctgan_blocks(long long n, int per_block, int cap = 4096) 
     return (unsigned)b;
 }
 
+// bn.hip, for bn_act.hip: the chunk plan of the partial reductions (part[(sample*hc + chunk)][2][c], `pos` positions per chunk) and the
+// finalisation of the backward's sums (no labels): part -> gscale, goffset [c] and s12 [groups][2][c] = mean(g scale), mean(g scale xhat)
+void ctgan_bn_plan(int n, int hw, int* hc, int* pos);
+int ctgan_bn_bwd_finalize(const double* part, const float* scale, int n, int hw, int c, int groups, float* gscale, float* goffset,
+                          float* s12, hipStream_t st);
+
 // skinny.hip: small-N linear layers (critic heads)
 bool ctgan_is_small_linear(const ctgan_conv_desc* d);
 int ctgan_small_linear_fwd(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,

@@ -1377,6 +1377,96 @@ def batch_norm(x, scale, offset, labels=None, groups=1, relu=False, eps=1e-5, f6
     return BatchNormFn.apply(x, scale, offset, labels, groups, relu, float(eps), bool(f64_stats))
 
 
+# --------------------------------------------------------------------------------- batch norm + LeakyReLU / tanh / gate, the gate alone
+# CTGAN_BN_ACT_FUSED=0: each such layer as batch_norm plus the separate activation launches (the gate: two strided channel views, sigmoid,
+# tanh and a product) instead of the folded kernels of csrc/bn_act.hip - the A/B switch of that fusion.
+BN_ACT_FUSED = _os.environ.get('CTGAN_BN_ACT_FUSED', '1') != '0'
+
+
+def _first_order_only(what):
+    raise RuntimeError('%s is first order only: its backward is not differentiable (the objectives that use it have no gradient penalty); '
+                       'set CTGAN_BN_ACT_FUSED=0 for the composed, twice-differentiable layer' % what)
+
+
+class BatchNormActFn(Function):
+    """Training-mode BN with the following LeakyReLU / tanh / gate folded into the apply launch and into both launches of the backward."""
+
+    @staticmethod
+    def forward(ctx, x, scale, offset, act, alpha, groups, eps):
+        y, mean, rstd, x4 = K.bn_act_fwd(x, scale, offset, act, alpha, groups, eps)
+        ctx.act, ctx.alpha, ctx.groups, ctx.in_shape = act, alpha, groups, x.shape
+        ctx.save_for_backward(x4, mean, rstd, scale, offset)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if torch.is_grad_enabled():
+            _first_order_only('batch_norm_act')
+        x4, mean, rstd, scale, offset = ctx.saved_tensors
+        gx, gs, go = K.bn_act_bwd(gy, x4, mean, rstd, scale, offset, ctx.act, ctx.alpha, ctx.groups)
+        if len(ctx.in_shape) == 2:
+            gx = gx.reshape(ctx.in_shape)
+        return gx, gs.view(scale.shape), go.view(offset.shape), None, None, None, None
+
+
+class GateFn(Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return K.gate_fwd(x)
+
+    @staticmethod
+    def backward(ctx, gy):
+        if torch.is_grad_enabled():
+            _first_order_only('gate')
+        (x,) = ctx.saved_tensors
+        return K.gate_bwd(gy, x).reshape(x.shape)
+
+
+class ChannelSplitFn(Function):
+    """(x[:, ::2], x[:, 1::2]) as two dense channels-last tensors (copy launches); the adjoint writes both halves back into one buffer."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.shape = x.shape
+        ev, od = x[:, ::2], x[:, 1::2]
+        return K.copy4d(ev, K.empty_cl(*ev.shape, device=x.device)), K.copy4d(od, K.empty_cl(*od.shape, device=x.device))
+
+    @staticmethod
+    def backward(ctx, ge, go):
+        full = K.empty_cl(*ctx.shape, device=ge.device)
+        K.copy4d(ge, full[:, ::2])
+        K.copy4d(go, full[:, 1::2])
+        return full
+
+
+def gate_composed(x):
+    """The gate from the existing launches: two strided channel views, sigmoid, tanh and a product (TF/CT_gan_64x64.py:95-96, :333)."""
+    two_d = x.dim() == 2
+    a, b = ChannelSplitFn.apply(x.reshape(x.shape[0], x.shape[1], 1, 1) if two_d else x)
+    y = MulFn.apply(sigmoid(a), tanh(b))
+    return y.reshape(y.shape[0], y.shape[1]) if two_d else y
+
+
+def gate(x):
+    """sigmoid(x[:, ::2]) * tanh(x[:, 1::2]): one launch each way (first order only), or gate_composed with CTGAN_BN_ACT_FUSED=0."""
+    return GateFn.apply(x) if BN_ACT_FUSED else gate_composed(x)
+
+
+def batch_norm_act(x, scale, offset, act, alpha=0.2, groups=1, eps=1e-5):
+    """act(batch_norm(x)) with act 'lrelu' (slope alpha) / 'tanh' / 'gate'; scale / offset [C].  The activation rides the normalisation's
+    apply launch and both launches of its backward (first order only); CTGAN_BN_ACT_FUSED=0 composes today's launches instead."""
+    if act not in K.BN_ACTS:
+        raise ValueError('activation %r: one of %s' % (act, ', '.join(sorted(K.BN_ACTS))))
+    C = x.shape[1]
+    if BN_ACT_FUSED:
+        return BatchNormActFn.apply(x, scale.reshape(C), offset.reshape(C), act, float(alpha), int(groups), float(eps))
+    y = batch_norm(x, scale.reshape(1, C), offset.reshape(1, C), None, groups, False, eps)
+    if act == 'lrelu':
+        return leaky_relu(y, alpha)
+    return tanh(y) if act == 'tanh' else gate_composed(y)
+
+
 # --------------------------------------------------------------------------------- score classifier: ELU, BN with moving statistics
 # CTGAN_SCORE_FUSED=0: the residual block's  shortcut + alpha bn(x)  [and the ELU of it]  as bn_apply, F.add and ELU launches instead
 # of the one-pass epilogue (kernels.bn_apply_ex) - the A/B switch of that fusion (INTEGRATION.md 4).

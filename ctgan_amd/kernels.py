@@ -1595,6 +1595,97 @@ def bn_bwd(gy, x4, mean, rstd, scale, offset, labels, groups, relu):
     return gx, gscale, goffset
 
 
+# ------------------------------------------------------------------------------- batch norm + LeakyReLU / tanh / gate (csrc/bn_act.hip)
+BN_ACTS = {'lrelu': 0, 'tanh': 1, 'gate': 2}       # CTGAN_ACT_*
+
+
+def _act_code(act, C):
+    if act not in BN_ACTS:
+        raise ValueError('activation %r: one of %s' % (act, ', '.join(sorted(BN_ACTS))))
+    if act == 'gate' and C % 2:
+        raise ValueError('the gate pairs channels: %d is odd' % C)
+    return BN_ACTS[act]
+
+
+def bn_act_fwd(x, scale, offset, act, alpha, groups, eps=1e-5):
+    """act((x - mean) rstd scale + offset) of a channels-last [N,C,H,W] (or [N,C]) tensor: the statistics of bn_fwd (ctgan_bn_stats), then
+    one apply launch with the activation folded in.  act 'lrelu' (slope alpha) / 'tanh' / 'gate' (sigmoid of the even channels times tanh of
+    the odd ones: C/2 channels out).  scale / offset [C].  Returns y, mean[groups,C], rstd[groups,C], x4."""
+    _need_dev(x, scale, offset)
+    x4 = to_channels_last(x if x.dim() == 4 else x.view(x.shape[0], x.shape[1], 1, 1))
+    N, C, H, W = x4.shape
+    code = _act_code(act, C)
+    assert scale.numel() == C and offset.numel() == C and scale.is_contiguous() and offset.is_contiguous()
+    hw = H * W
+    mean = torch.empty((groups, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((groups, C), dtype=torch.float32, device=x.device)
+    ws = workspace(lib.ctgan_bn_workspace_bytes(N, hw, C, groups, 1), x.device)
+    check(lib.ctgan_bn_stats(_ptr(x4), N, hw, C, groups, eps, _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(), _stream()), 'bn_stats')
+    Co = C // 2 if act == 'gate' else C
+    y = empty_cl(N, Co, H, W, x.device)
+    check(lib.ctgan_bn_act_apply(_ptr(x4), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(offset), _ptr(y), N, hw, C, groups, code, float(alpha),
+                                 _stream()), 'bn_act_apply')
+    if x.dim() == 2:
+        y = y.view(N, Co)
+    return y, mean, rstd, x4
+
+
+def bn_act_bwd(gy, x4, mean, rstd, scale, offset, act, alpha, groups):
+    """Backward of bn_act_fwd from x4, mean, rstd alone: the activation's derivative is recomputed in the reduction and in the apply launch
+    (three launches, as bn_bwd).  gy has the forward result's shape (C/2 channels for the gate).  -> gx (x4's shape), gscale [C], goffset [C]."""
+    _need_dev(gy, x4, mean, rstd, scale, offset)
+    N, C, H, W = x4.shape
+    code = _act_code(act, C)
+    Co = C // 2 if act == 'gate' else C
+    gy4 = to_channels_last(gy if gy.dim() == 4 else gy.reshape(N, Co, 1, 1))
+    assert tuple(gy4.shape) == (N, Co, H, W)
+    hw = H * W
+    gx = empty_cl(N, C, H, W, gy.device)
+    gscale = torch.empty(C, dtype=torch.float32, device=gy.device)
+    goffset = torch.empty(C, dtype=torch.float32, device=gy.device)
+    ws = workspace(lib.ctgan_bn_workspace_bytes(N, hw, C, groups, 1), gy.device)
+    check(lib.ctgan_bn_act_bwd(_ptr(gy4), _ptr(x4), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(offset), _ptr(gx), _ptr(gscale), _ptr(goffset),
+                               N, hw, C, groups, code, float(alpha), _ptr(ws), ws.numel(), _stream()), 'bn_act_bwd')
+    return gx, gscale, goffset
+
+
+def _gate_x(x):
+    """x as the flat pair list the gate kernels read: channels-last [N,C,H,W] or contiguous rows [N,C], C even."""
+    if x.dim() == 4:
+        x = to_channels_last(x)
+    elif not (x.dim() == 2 and x.is_contiguous()):
+        raise ValueError('gate: a 4-D tensor or contiguous rows [N, C]')
+    if x.shape[1] % 2:
+        raise ValueError('the gate pairs channels: %d is odd' % x.shape[1])
+    return x
+
+
+def gate_fwd(x):
+    """sigmoid(x[:, ::2]) * tanh(x[:, 1::2]) in one launch -> half the channels, channels-last."""
+    _need_dev(x)
+    x = _gate_x(x)
+    N, C = x.shape[:2]
+    y = empty_cl(N, C // 2, x.shape[2], x.shape[3], x.device) if x.dim() == 4 else torch.empty((N, C // 2), dtype=torch.float32, device=x.device)
+    check(lib.ctgan_gate_fwd(_ptr(x), _ptr(y), y.numel(), _stream()), 'gate_fwd')
+    return y
+
+
+def gate_bwd(gy, x):
+    """Backward of gate_fwd: gy (half the channels) and the forward input -> the gradient of both channels of each pair, one launch."""
+    _need_dev(gy, x)
+    x = _gate_x(x)
+    N, C = x.shape[:2]
+    if x.dim() == 4:
+        gy = to_channels_last(gy)
+        gx = empty_cl(N, C, x.shape[2], x.shape[3], x.device)
+    else:
+        gy = gy.contiguous()
+        gx = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    assert gy.numel() * 2 == x.numel()
+    check(lib.ctgan_gate_bwd(_ptr(gy), _ptr(x), _ptr(gx), gy.numel(), _stream()), 'gate_bwd')
+    return gx
+
+
 # ------------------------------------------------------------------------------- score classifier (csrc/bn.hip, csrc/score.hip)
 def _bn_x4(x):
     x4 = x if x.dim() == 4 else x.view(x.shape[0], x.shape[1], 1, 1)

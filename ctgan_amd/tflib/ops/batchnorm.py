@@ -6,7 +6,8 @@ host - a Python bool, not a tensor.  True: batch statistics and, with update_mov
 or a device scalar tensor (read on the device, so a captured step replays with the current value).  False: the blend of :32-38, forward
 only, no update.
 Build-only kwargs: `groups` (independent statistic groups = the reference's per-tower batches; is_training=None only),
-`relu` (fuse the ReLU that always follows in the generators), `resid` / `resid_scale` / `want_elu` (is_training True / False only):
+`relu` (fuse the ReLU that always follows in the generators), `act` = 'lrelu' | 'tanh' | 'gate' with `alpha` (is_training=None, axes
+[0,2,3] only: the LeakyReLU / tanh / gated nonlinearity that follows in the DCGAN-style 64x64 nets, functional.batch_norm_act), `resid` / `resid_scale` / `want_elu` (is_training True / False only):
 the result is resid + resid_scale * Batchnorm(inputs) and, with want_elu, the pair (result, elu(result)) - the epilogue of
 LS/inception_score.py's residual block in the normalisation's own apply pass.
 """
@@ -19,7 +20,9 @@ from .. import param as _param
 
 
 def Batchnorm(name, axes, inputs, is_training=None, stats_iter=None, update_moving_stats=True, fused=True,
-              groups=1, relu=False, resid=None, resid_scale=1.0, want_elu=False):
+              groups=1, relu=False, resid=None, resid_scale=1.0, want_elu=False, act=None, alpha=0.2):
+    if act is not None and (is_training is not None or axes != [0, 2, 3] or not fused or relu or resid is not None or want_elu):
+        raise ValueError('Batchnorm: act needs is_training=None on the fused [0,2,3] path, without relu / resid / want_elu')
     fuse = dict(shortcut=resid, alpha=resid_scale, want_elu=want_elu)
     if (resid is not None or resid_scale != 1.0 or want_elu) and (is_training is None or axes != [0, 2, 3] or not fused or relu):
         raise ValueError('Batchnorm: resid / resid_scale / want_elu need is_training True or False on the fused [0,2,3] path, without relu')
@@ -37,6 +40,8 @@ def Batchnorm(name, axes, inputs, is_training=None, stats_iter=None, update_movi
         scale = _param(name + '.scale', lambda rng: np.ones(C, dtype='float32'))
         moving_mean = _param(name + '.moving_mean', lambda rng: np.zeros(C, dtype='float32'), trainable=False)
         moving_variance = _param(name + '.moving_variance', lambda rng: np.ones(C, dtype='float32'), trainable=False)
+        if act is not None:
+            return F.batch_norm_act(x, scale, offset, act, alpha, groups)
         if is_training is None:
             out = F.batch_norm(x, scale.view(1, C), offset.view(1, C), None, groups, relu)
         elif is_training:

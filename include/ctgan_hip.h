@@ -485,6 +485,26 @@ int ctgan_bn_bwd_scaled(const float* gy, const float* x, const float* mean, cons
                         const float* offset, float gy_scale, float* gx, float* gscale, float* goffset, int32_t n, int32_t hw,
                         int32_t c, void* ws, size_t ws_bytes, ctgan_stream_t stream);
 
+/* ---- batch norm with the following activation folded in, and the gate on its own (csrc/bn_act.hip): the hidden layers of the DCGAN-style
+ *      64x64 nets, conv -> Batchnorm -> LeakyReLU | tanh | gate (TF/CT_gan_64x64.py:237-273, :325-353, :375-399, :435-467).
+ *      z = (x - mean) rstd scale + offset with mean / rstd [groups, c] from ctgan_bn_stats and scale / offset [c];
+ *      LRELU: y = z > 0 ? z : alpha z;  TANH: y = tanh(z);  GATE: y[.., j] = sigmoid(z[.., 2j]) tanh(z[.., 2j+1]), y and gy [n, hw, c/2]
+ *      (c even; :95-96, :333).  ReLU stays with ctgan_bn_apply / ctgan_bn_bwd.  ---------- */
+#define CTGAN_ACT_LRELU 0
+#define CTGAN_ACT_TANH 1
+#define CTGAN_ACT_GATE 2
+int ctgan_bn_act_apply(const float* x, const float* mean, const float* rstd, const float* scale, const float* offset, float* y,
+                       int32_t n, int32_t hw, int32_t c, int32_t groups, int32_t act, float alpha, ctgan_stream_t stream);
+/* gy -> gx, gscale [c], goffset [c] with g = act'(z) gy recomputed from x and the coefficients in both passes (three launches, as
+ * ctgan_bn_bwd).  ws: ctgan_bn_workspace_bytes(n, hw, c, groups, 1).                                                             */
+int ctgan_bn_act_bwd(const float* gy, const float* x, const float* mean, const float* rstd, const float* scale, const float* offset,
+                     float* gx, float* gscale, float* goffset, int32_t n, int32_t hw, int32_t c, int32_t groups, int32_t act,
+                     float alpha, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+/* The gate without a normalisation, over flat pairs: y[j] = sigmoid(x[2j]) tanh(x[2j+1]), j < n_out - a dense channels-last tensor
+ * with an even channel count (or rows [n, c]) -> half the channels.  One launch each way.                                         */
+int ctgan_gate_fwd(const float* x, float* y, int64_t n_out, ctgan_stream_t stream);
+int ctgan_gate_bwd(const float* gy, const float* x, float* gx, int64_t n_out, ctgan_stream_t stream);
+
 /* ---- ELU and the global-norm clip of the score classifier (csrc/score.hip) ---- */
 /* y = x > 0 ? x : expm1(x)                                                                      */
 int ctgan_elu_fwd(const float* x, float* y, int64_t n, ctgan_stream_t stream);
