@@ -262,6 +262,10 @@ SIGNATURES = {
     'ctgan_te_head_fwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_te_head_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p]),
     'ctgan_te_ensemble_update': (c_int, [_p, _p, _p, c_int64, c_float, c_float, _p]),
+    # classifier score of CIFAR-10 samples (csrc/score_cifar.hip)
+    'ctgan_score_input': (c_int, [_p, c_int64, c_int32, c_int32, c_float, _p, _p, _p]),
+    'ctgan_score_accum': (c_int, [_p, c_int64, c_int32, c_int64, c_int64, c_int32, _p, _p, _p, _p]),
+    'ctgan_score_finish': (c_int, [_p, c_int64, c_int32, c_int32, _p, _p]),
 }
 
 

@@ -1,6 +1,7 @@
 // elementwise.hip - HBM-bound helpers of the CT-WGAN step.
 // All are grid-stride kernels; contiguous fp32 streams use 16-byte accesses when aligned.
 #include "common.h"
+#include "pixel_u8.h"
 
 namespace {
 
@@ -154,14 +155,7 @@ __global__ void real_prep_kernel(const int32_t* __restrict__ xi, const float* __
     }
 }
 
-// score-sample pixels: trunc((x + 1) * scale) clamped to [0, 255], NCHW fp32 -> NHWC uint8.  Add then multiply, each rounded on its
-// own (no fused multiply-add), so that finite inputs are bit-equal to ((x + 1.) * scale).to(int32).clamp(0, 255); a non-finite
-// input gives 0.
-__device__ __forceinline__ unsigned pixel_u8(float x, float scale) {
-    const float v = __fmul_rn(__fadd_rn(x, 1.0f), scale);
-    if (!isfinite(x) || !(v > 0.f)) return 0u;
-    return v >= 256.f ? 255u : (unsigned)(int)v;
-}
+// score-sample pixels: pixel_u8 (pixel_u8.h) of every element, NCHW fp32 -> NHWC uint8.
 
 // three channel planes, hw % 4 == 0: a lane reads 16 B from each plane (four pixels) and writes their 12 output bytes as three words
 __global__ void pixels_u8_c3_kernel(const float* __restrict__ x, uint32_t* __restrict__ out, long long quads, int hw4, float scale) {

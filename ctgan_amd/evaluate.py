@@ -280,16 +280,16 @@ class Evaluator:
             return slopes.max()
 
     # ------------------------------------------------------------------ score samples
-    def score_samples(self, n, labels=None, scale=255.99 / 2, chunk=None):
-        """Yields uint8 [m, H, W, 3] pixel tensors, trunc((sample + 1) * scale), until `n` samples are out.  Samples are drawn in statistic
-        groups of 100 (samples_100 = Generator(100, ...)); `chunk` samples (a multiple of 100; None: DEFAULT_SCORE_CHUNK) share one
-        generator call.  ResNet: `labels` [n] int32, or drawn uniformly in [0, 10) on the evaluation stream (:351)."""
+    def score_draws(self, n, labels=None, chunk=None):
+        """Yields (samples fp32 [m, OUTPUT_DIM] as the generator returns them, their labels int32 [m] - None for an unconditional
+        generator) until `n` samples are out.  Samples are drawn on the evaluation stream in statistic groups of 100
+        (samples_100 = Generator(100, ...)); `chunk` samples (a multiple of 100; None: DEFAULT_SCORE_CHUNK) share one generator call.
+        ResNet: `labels` [n] int32, or drawn uniformly in [0, 10) on the evaluation stream (:351)."""
         if self.name not in SCORE_SCALE:
             raise NotImplementedError('%s: the script scores no samples (no three-channel output)' % self.mod.__name__)
         chunk = DEFAULT_SCORE_CHUNK[self.name] if chunk is None else int(chunk)
         if chunk < SCORE_GROUP or chunk % SCORE_GROUP:
-            raise ValueError('score_samples: chunk must be a positive multiple of %d' % SCORE_GROUP)
-        side = int(round(math.sqrt(self.mod.cfg.OUTPUT_DIM // 3)))
+            raise ValueError('score samples: chunk must be a positive multiple of %d' % SCORE_GROUP)
         rng = self.rng
         F.prepare_filters()
         done = 0
@@ -297,6 +297,7 @@ class Evaluator:
             m = min(chunk, n - done)
             groups = (m + SCORE_GROUP - 1) // SCORE_GROUP
             drawn = groups * SCORE_GROUP            # whole statistic groups; a trailing partial group is cut after the draw
+            lab = None
             rng.begin_step()
             with torch.no_grad():
                 if self.resnet:
@@ -308,10 +309,15 @@ class Evaluator:
                     x = self.mod.Generator(drawn, rng=rng, groups=groups)
                 else:
                     x = self.mod.Generator(drawn, rng=rng)
-                px = K.pixels_u8(x.contiguous(), 3, scale)
             rng.end_step()
-            yield px.reshape(drawn, side, side, 3)[:m]
+            yield x.contiguous()[:m], (lab[:m] if lab is not None else None)
             done += m
+
+    def score_samples(self, n, labels=None, scale=255.99 / 2, chunk=None):
+        """Yields uint8 [m, H, W, 3] pixel tensors, trunc((sample + 1) * scale), of the samples of score_draws(n, labels, chunk)."""
+        side = int(round(math.sqrt(self.mod.cfg.OUTPUT_DIM // 3)))
+        for x, _ in self.score_draws(n, labels, chunk):
+            yield K.pixels_u8(x, 3, scale).reshape(x.shape[0], side, side, 3)
 
     def get_inception_score(self, n, classifier, splits=10, scale=None):
         """(mean, std) of the score over `n` samples: `classifier` (a host callable) gets float32 [m, H, W, 3] arrays in [0, 255] and
@@ -323,10 +329,24 @@ class Evaluator:
         preds = [np.asarray(classifier(px.cpu().numpy().astype(np.float32))) for px in self.score_samples(n, scale=scale)]
         return score_from_probabilities(np.concatenate(preds, 0), splits)
 
+    def get_classifier_score(self, n, scorer, splits=10):
+        """The score of `n` samples under `scorer` (a score_cifar.ClassifierScore), everything on the device: samples -> classifier
+        input (kernels.score_input) -> logits -> streaming statistic -> {'mean', 'std', 'splits', 'hist', 'acc'}, one host copy."""
+        return scorer.score_generator(self.t, n, splits=splits)
+
 
 def record_score(ev, series, classifier):
-    """One scoring of the loops: the script's sample count through `classifier`, recorded under the script's series names."""
+    """One scoring of the loops: the script's sample count through `classifier`, recorded under the script's series names.  A
+    score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels."""
     if ev.name not in SCORE_SERIES:
+        return
+    from .score_cifar import ClassifierScore
+    if isinstance(classifier, ClassifierScore):
+        res = ev.get_classifier_score(SCORE_SAMPLES[ev.name], classifier)
+        for name, value in zip(SCORE_SERIES[ev.name], (res['mean'], res['std'])):
+            series.add(name, value)
+        if res['acc'] is not None:
+            series.add('score_acc', res['acc'])
         return
     score = ev.get_inception_score(SCORE_SAMPLES[ev.name], classifier)
     for name, value in zip(SCORE_SERIES[ev.name], score):

@@ -2593,3 +2593,45 @@ def te_ensemble_update(ens, targets, pred, decay, epoch):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == ens.shape, 'three contiguous fp32 tables of one shape expected'
     inv_corr = 1.0 / (1.0 - float(decay) ** (int(epoch) + 1))
     check(lib.ctgan_te_ensemble_update(_ptr(ens), _ptr(targets), _ptr(pred), ens.numel(), float(decay), inv_corr, _stream()), 'te_ensemble_update')
+
+
+# ---------------------------------------------------------------- classifier score of CIFAR-10 samples (csrc/score_cifar.hip; score_cifar.py)
+def score_input(x, channels, scale, lut):
+    """Generator output x fp32 [n, C*S*S] (NCHW flat) -> the CT classifier's internal input: logical [n, C, S, S], channels-last,
+    rotated by 180 degrees, lut[pixels_u8 byte] per element - bit-equal to pixels_u8 -> [n, C, S, S] -> aug_gather's fixed mode."""
+    _need_dev(x, lut)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2 and x.shape[1] % channels == 0
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and lut.numel() == 256
+    n, size = x.shape[0], math.isqrt(x.shape[1] // channels)
+    assert size * size * channels == x.shape[1], 'square images expected'
+    out = empty_cl(n, channels, size, size, x.device)
+    check(lib.ctgan_score_input(_ptr(x), n, channels, size, float(scale), _ptr(lut), _ptr(out), _stream()), 'score_input')
+    return out
+
+
+def _score_state(acc, cnt, splits):
+    for t in (acc, cnt):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % t.device)
+    assert acc.dtype == torch.float64 and acc.dim() == 2 and acc.is_contiguous() and acc.shape[0] == splits
+    nc = acc.shape[1] - 1
+    assert cnt is None or (cnt.dtype == torch.int64 and cnt.is_contiguous() and cnt.numel() == 2 * nc)
+    return nc
+
+
+def score_accum(logits, r0, n, splits, acc, cnt, labels=None):
+    """Adds the chunk of global rows [r0, r0 + m) of n - logits fp32 [m, K] - to the score state acc fp64 [splits, K + 1],
+    cnt int64 [2 K] (both zeroed by the caller before the first chunk), in place; labels: int32 [m] or None.  K <= 32."""
+    _need_dev(logits, labels)
+    m, nc = _rows2d(logits)
+    assert _score_state(acc, cnt, splits) == nc, 'acc [splits, K + 1] expected'
+    assert labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == m)
+    check(lib.ctgan_score_accum(_ptr(logits), m, nc, int(r0), int(n), int(splits), _ptr(labels), _ptr(acc), _ptr(cnt), _stream()), 'score_accum')
+
+
+def score_finish(acc, n, splits):
+    """acc fp64 [splits, K + 1] -> fp64 [2 + splits] = {mean, population std, the per-split scores}."""
+    nc = _score_state(acc, None, splits)
+    out = torch.empty(2 + splits, dtype=torch.float64, device=acc.device)
+    check(lib.ctgan_score_finish(_ptr(acc), int(n), int(splits), nc, _ptr(out), _stream()), 'score_finish')
+    return out

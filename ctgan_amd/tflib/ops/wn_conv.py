@@ -26,6 +26,39 @@ WN_EPS = 1e-6           # TH/nn.py:81
 LRELU_SLOPE = 0.2       # TH/nn.py lrelu
 
 
+_CONST = None            # inside constant_filters(store): the store
+
+
+class constant_filters:
+    """with constant_filters(store): every WNConv2D / WNNIN / WNLinear layer outside its init pass takes its normalised filter from
+    the dict `store` (layer name -> tensor), made by the layer's own normalisation launch the first time and kept there - the same
+    values a pass outside the context computes, so its results are bit-equal.  For passes whose W and g do not change between calls
+    (score_cifar.ClassifierScore, which owns the store and empties it when the classifier's parameters move); no gradients."""
+
+    def __init__(self, store):
+        self.store = store
+
+    def __enter__(self):
+        global _CONST
+        self.old, _CONST = _CONST, self.store
+
+    def __exit__(self, *a):
+        global _CONST
+        _CONST = self.old
+        return False
+
+
+def _normalised(name, make):
+    if _CONST is None:
+        return make()
+    if torch.is_grad_enabled():
+        raise RuntimeError('wn_conv.constant_filters: %s is being built with gradients enabled - the stored filters are constants' % name)
+    if name not in _CONST:
+        with torch.no_grad():
+            _CONST[name] = make().detach()
+    return _CONST[name]
+
+
 def _normal(shape):
     return lambda r: r.normal(0.0, W_STD, shape).astype('float32')
 
@@ -80,7 +113,7 @@ def WNConv2D(name, input_dim, output_dim, filter_size, inputs, stride=1, pad='sa
             return F.dropout(y, 1.0 if deterministic else float(drop_keep), rng=rng)
     if frozen:
         W, g, b = W.detach(), g.detach(), b.detach()
-    y = valid(F.conv2d(inputs, F.weight_norm_filter(W, g, WN_EPS), b, stride=stride))
+    y = valid(F.conv2d(inputs, _normalised(name, lambda: F.weight_norm_filter(W, g, WN_EPS)), b, stride=stride))
     return _act(y, nonlinearity, drop_keep, deterministic, rng)
 
 
@@ -97,7 +130,7 @@ def WNNIN(name, input_dim, output_dim, inputs, nonlinearity='lrelu', drop_keep=1
             return F.dropout(y, 1.0 if deterministic else float(drop_keep), rng=rng)
     if frozen:
         W, g, b = W.detach(), g.detach(), b.detach()
-    y = F.conv2d(inputs, F.weight_norm(W, g, WN_EPS).view(1, 1, input_dim, output_dim), b)
+    y = F.conv2d(inputs, _normalised(name, lambda: F.weight_norm(W, g, WN_EPS).view(1, 1, input_dim, output_dim)), b)
     return _act(y, nonlinearity, drop_keep, deterministic, rng)
 
 
@@ -113,7 +146,7 @@ def WNLinear(name, input_dim, output_dim, inputs, nonlinearity=None, train_g=Fal
             return K.wn_init_map(y, g, b, nonlinearity, LRELU_SLOPE, init_stdv)
     if frozen:
         W, g, b = W.detach(), g.detach(), b.detach()
-    y = F.linear(inputs, F.weight_norm(W, g, WN_EPS), b)
+    y = F.linear(inputs, _normalised(name, lambda: F.weight_norm(W, g, WN_EPS)), b)
     return _act(y, nonlinearity, 1.0, deterministic, rng)
 
 

@@ -847,6 +847,29 @@ int ctgan_te_head_bwd(const float* logits, const float* feat, const int32_t* lab
 int ctgan_te_ensemble_update(float* ens, float* targets, float* pred, int64_t n, float decay, float inv_corr, ctgan_stream_t stream);
 
 
+/* ---- classifier score of CIFAR-10 samples (csrc/score_cifar.hip; score_cifar.py) ------------------------------------------------
+ * The path between a generator and the score of TF/tflib/inception_score.py:60-69 under the CT classifier (ct_cifar.py), kept on
+ * the device.
+ * Generator output x [n, channels size size] (NCHW flat) -> the classifier's internal input: out logical [n, channels, size, size],
+ * channels-last, rotated by 180 degrees, out = lut[byte] with byte what ctgan_pixels_u8 computes for that element - bit-equal to
+ * ctgan_pixels_u8 -> NHWC to NCHW -> ctgan_aug_gather(rows 0..n-1, win = size, offsets (pad, pad), no flip, rot180, channels_last). */
+int ctgan_score_input(const float* x, int64_t n, int32_t channels, int32_t size, float scale, const float* lut, float* out,
+                      ctgan_stream_t stream);
+/* Streaming score statistic over the logits [m, classes] of the chunk of global rows [r0, r0 + m) of n, n >= splits.  Row g
+ * belongs to split k with k n / splits <= g < (k + 1) n / splits (integer division: score_from_probabilities' slices).  Caller-owned,
+ * caller-zeroed state: acc double [splits, classes + 1], cnt int64 [2 classes].  Per row in fp64: lp = z - max - log sum exp(z - max),
+ * p = exp(lp); acc[k, j] += p_j; acc[k, classes] += sum_j p_j lp_j (a p that underflowed to 0 adds exactly 0; a non-finite logit
+ * makes the row's terms NaN); cnt[argmax] += 1 (first maximum, as numpy.argmax) and, with labels (int32 [m], may be NULL),
+ * cnt[classes + label] += 1 where argmax == label.  One workgroup per split; fp64 partials per thread, an LDS tree in a fixed
+ * order, one thread adds into acc with plain loads and stores; integer adds for cnt.  Successive chunks are ordered by the stream.
+ * classes > 32: CTGAN_E_UNSUPPORTED, nothing is launched.                                                                         */
+int ctgan_score_accum(const float* logits, int64_t m, int32_t classes, int64_t r0, int64_t n, int32_t splits, const int32_t* labels,
+                      double* acc, int64_t* cnt, ctgan_stream_t stream);
+/* acc -> out double [2 + splits]: out[2 + k] = exp(acc[k, classes] / n_k - sum_j m_j log m_j), m_j = acc[k, j] / n_k (a term with
+ * m_j = 0 is 0), n_k the split's length; out[0] their mean, out[1] their population standard deviation.  One workgroup.          */
+int ctgan_score_finish(const double* acc, int64_t n, int32_t splits, int32_t classes, double* out, ctgan_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif
