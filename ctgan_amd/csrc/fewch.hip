@@ -815,18 +815,31 @@ bool ctgan_fewch_handles(const ctgan_conv_desc* d) {
 }
 
 // launch helpers -------------------------------------------------------------------------------------------
+// few -> many: output rows per workgroup.  pick_band grows the band with the batch, up to the whole image, and the LDS tile [CS][TR][TW]
+// grows with it (N >= 512 at 64x64, 3x3x3: 3*66*66*4 = 52 272 B; at 128x128 more than a workgroup can have at all): the band is halved until
+// the tile is within the 48 KB that need no opt-in.  0: even the 4-row band is over the 150 KB the launches of this file allow themselves.
+static size_t f2m_tile_bytes(int band, int Q, int stride, int R, int S, int CS) {
+    return (size_t)CS * ((band - 1) * stride + R) * ((Q - 1) * stride + S) * sizeof(float);
+}
+static int f2m_band(int N, int P, int Q, int stride, int R, int S, int CS) {
+    int band = pick_band(N, P, 4);
+    while (band > 4 && f2m_tile_bytes(band, Q, stride, R, S, CS) > 48 * 1024) band >>= 1;
+    return f2m_tile_bytes(band, Q, stride, R, S, CS) > 150 * 1024 ? 0 : band;
+}
+
 static int launch_f2m(const F2MParams& p, int R, int S, int CS, hipStream_t st) {
     const int bands = (p.P + p.band - 1) / p.band;
-    const int TR = (p.band - 1) * p.stride + R, TW = (p.Q - 1) * p.stride + S;
-    const size_t smem = (size_t)CS * TR * TW * sizeof(float);
+    const size_t smem = f2m_tile_bytes(p.band, p.Q, p.stride, R, S, CS);
     const dim3 grid(p.N * bands), blk(NT);
+    int rc = 0;
     switch (tap_case(R, S, CS)) {
-        case 1: hipLaunchKernelGGL((f2m_kernel<3, 3, 3>), grid, blk, smem, st, p); break;
-        case 2: hipLaunchKernelGGL((f2m_kernel<1, 1, 3>), grid, blk, smem, st, p); break;
-        case 3: hipLaunchKernelGGL((f2m_kernel<5, 5, 1>), grid, blk, smem, st, p); break;
-        case 4: hipLaunchKernelGGL((f2m_kernel<3, 3, 1>), grid, blk, smem, st, p); break;
+        case 1: rc = set_smem(&f2m_kernel<3, 3, 3>, smem); if (!rc) hipLaunchKernelGGL((f2m_kernel<3, 3, 3>), grid, blk, smem, st, p); break;
+        case 2: rc = set_smem(&f2m_kernel<1, 1, 3>, smem); if (!rc) hipLaunchKernelGGL((f2m_kernel<1, 1, 3>), grid, blk, smem, st, p); break;
+        case 3: rc = set_smem(&f2m_kernel<5, 5, 1>, smem); if (!rc) hipLaunchKernelGGL((f2m_kernel<5, 5, 1>), grid, blk, smem, st, p); break;
+        case 4: rc = set_smem(&f2m_kernel<3, 3, 1>, smem); if (!rc) hipLaunchKernelGGL((f2m_kernel<3, 3, 1>), grid, blk, smem, st, p); break;
         default: return ctgan_fail(CTGAN_E_UNSUPPORTED, "fewch f2m: taps");
     }
+    if (rc) return rc;
     ctgan_set_last_symbol("f2m_kernel<%d, %d, %d>", R, S, CS);
     return ctgan_check_launch("fewch_f2m");
 }
@@ -910,7 +923,8 @@ int ctgan_fewch_fwd(const ctgan_conv_desc* d, const float* x, const float* w, co
         p.w = w; p.w_off = 0; p.ws_r = (long long)d->S * d->C * d->K; p.ws_s = (long long)d->C * d->K; p.ws_c = d->K; p.ws_k = 1;
         p.bias = bias; p.resid = resid; p.mask = mask;
         p.N = d->N; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.relu = relu; p.relu_in = relu_in;
-        p.band = pick_band(d->N, d->P, 4);
+        p.band = f2m_band(d->N, d->P, d->Q, d->stride, d->R, d->S, d->C);
+        if (!p.band) return 0;
         ctgan_set_last_kernel("fewch_f2m");
         const int rc = launch_f2m(p, d->R, d->S, d->C, st);
         return rc ? rc : 1;
@@ -980,7 +994,8 @@ int ctgan_fewch_dgrad(const ctgan_conv_desc* d, const float* dy, const float* w,
     p.w = w; p.w_off = rot_off; p.ws_r = -tapR; p.ws_s = -tapS; p.ws_c = 1; p.ws_k = d->K;
     p.bias = bias; p.resid = nullptr; p.mask = nullptr;
     p.N = d->N; p.stride = 1; p.pad_t = d->R - 1 - d->pad_t; p.pad_l = d->S - 1 - d->pad_l; p.relu = 0; p.relu_in = 0;
-    p.band = pick_band(d->N, p.P, 4);
+    p.band = f2m_band(d->N, p.P, p.Q, 1, d->R, d->S, d->K);
+    if (!p.band) return 0;
     ctgan_set_last_kernel("fewch_f2m(dgrad)");
     const int rc = launch_f2m(p, d->R, d->S, d->K, st);
     return rc ? rc : 1;
