@@ -266,6 +266,8 @@ SIGNATURES = {
     'ctgan_score_input': (c_int, [_p, c_int64, c_int32, c_int32, c_float, _p, _p, _p]),
     'ctgan_score_accum': (c_int, [_p, c_int64, c_int32, c_int64, c_int64, c_int32, _p, _p, _p, _p]),
     'ctgan_score_finish': (c_int, [_p, c_int64, c_int32, c_int32, _p, _p]),
+    # feature moments of the classifier Frechet distance (csrc/moments.hip)
+    'ctgan_moments_accum': (c_int, [_p, c_int64, c_int32, _p, _p, _p]),
 }
 
 

@@ -303,8 +303,8 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
-    (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series; the fixed-noise sample
-    grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
+    (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series (and `frechet`
+    when it is a score_cifar.ClassifierScore with a reference); the fixed-noise sample grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
     `dev_every`-th.  Returns the trainer."""
     import os
     import time

@@ -331,13 +331,15 @@ class Evaluator:
 
     def get_classifier_score(self, n, scorer, splits=10):
         """The score of `n` samples under `scorer` (a score_cifar.ClassifierScore), everything on the device: samples -> classifier
-        input (kernels.score_input) -> logits -> streaming statistic -> {'mean', 'std', 'splits', 'hist', 'acc'}, one host copy."""
+        input (kernels.score_input) -> logits -> streaming statistic -> {'mean', 'std', 'splits', 'hist', 'acc'}, one host copy; a scorer
+        with a reference adds 'frechet' from the same classifier passes."""
         return scorer.score_generator(self.t, n, splits=splits)
 
 
 def record_score(ev, series, classifier):
     """One scoring of the loops: the script's sample count through `classifier`, recorded under the script's series names.  A
-    score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels."""
+    score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels
+    and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it."""
     if ev.name not in SCORE_SERIES:
         return
     from .score_cifar import ClassifierScore
@@ -347,6 +349,8 @@ def record_score(ev, series, classifier):
             series.add(name, value)
         if res['acc'] is not None:
             series.add('score_acc', res['acc'])
+        if 'frechet' in res:
+            series.add('frechet', res['frechet'])
         return
     score = ev.get_inception_score(SCORE_SAMPLES[ev.name], classifier)
     for name, value in zip(SCORE_SERIES[ev.name], score):

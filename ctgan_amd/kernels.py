@@ -2635,3 +2635,17 @@ def score_finish(acc, n, splits):
     out = torch.empty(2 + splits, dtype=torch.float64, device=acc.device)
     check(lib.ctgan_score_finish(_ptr(acc), int(n), int(splits), nc, _ptr(out), _stream()), 'score_finish')
     return out
+
+
+# ---------------------------------------------------------------- feature moments of the classifier Frechet distance (csrc/moments.hip)
+def moments_accum(feat, s1, s2):
+    """Adds the raw moments of the chunk feat fp32 [m, D] to the state s1 fp64 [D] (sum_i f_i) and s2 fp64 [D, D] (sum_i f_i f_i^T,
+    full and exactly symmetric), both zeroed by the caller before the first chunk, in place.  D <= 1024."""
+    _need_dev(feat)
+    m, d = _rows2d(feat)
+    for t in (s1, s2):
+        if not t.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % t.device)
+        assert t.dtype == torch.float64 and t.is_contiguous(), 'contiguous fp64 state expected'
+    assert tuple(s1.shape) == (d,) and tuple(s2.shape) == (d, d), 's1 [D], s2 [D, D] expected'
+    check(lib.ctgan_moments_accum(_ptr(feat), m, d, _ptr(s1), _ptr(s2), _stream()), 'moments_accum')

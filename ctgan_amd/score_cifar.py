@@ -18,7 +18,21 @@ normalisation launches in the first chunk (tflib.ops.wn_conv.constant_filters) a
 bit-equal to `predict(averaged=True)` - and made again when the registry's parameter version moves (a classifier that trains on, or
 any registry-wide bump: a GAN training between two scorings makes each scoring normalise once).  They are plain tensors owned by the
 scorer: no cache outside it holds their addresses, so the conv wrappers pack them per call as they do for `predict`.
+
+The classifier Frechet distance.  With a reference set (`reference=` / `set_reference`), `score` and `score_generator` also return
+`'frechet'`: the Frechet distance between the Gaussian fits of the classifier's pooled feature layer (disc_layers[-2], D_WIDTHS[-1] =
+128 wide, the layer the classifier's generator is trained against) over the scored samples and over the reference set, usually the
+training images (`statistics`, once, saved with `FeatureStatistics.save`).
+    features [m, D] -> raw moments    kernels.moments_accum   per chunk, fp64 sum f and sum f f^T into caller-owned device state
+    moments -> mean, covariance       FeatureStatistics       on the host in fp64, from the scoring's one device -> host copy
+    two fits -> distance              frechet_distance        numpy only (two eigh and one eigvalsh of D x D)
+The features come from the SAME classifier pass as the logits (`_classifier(..., features='both')`): no launch of the classifier is
+added or changed, and without a reference the launches and the returned dict are exactly those of a scorer that knows nothing of this.
+Like the score it is a CLASSIFIER statistic, under a self-trained 10-class network: it is NOT comparable to published FID numbers
+(Inception pool3, 2048 features, ImageNet).  A reference records a hash of the classifier's averaged parameters; under any other
+classifier it is refused.
 """
+import hashlib
 import os
 
 import numpy as np
@@ -31,6 +45,61 @@ from .tflib.ops import wn_conv as _wn
 
 MAX_CLASSES = 32            # kernels.score_accum keeps a row's class accumulators in registers
 DEFAULT_CHUNK = 1000        # rows per classifier pass
+
+
+class FeatureStatistics:
+    """The Gaussian fit of a feature layer over `n` rows: `mean` fp64 [D], `cov` fp64 [D, D] (unbiased, n - 1), and `classifier`, the
+    hash (ClassifierScore.fingerprint) of the averaged parameters the features were computed under - None for a synthetic fit."""
+
+    def __init__(self, n, mean, cov, classifier=None):
+        self.n = int(n)
+        self.mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        self.cov = np.ascontiguousarray(cov, dtype=np.float64)
+        self.classifier = None if classifier is None else str(classifier)
+        if self.n < 1 or self.cov.shape != (self.mean.size, self.mean.size):
+            raise ValueError('FeatureStatistics: n %d, mean %s, cov %s' % (self.n, self.mean.shape, self.cov.shape))
+
+    @classmethod
+    def from_moments(cls, n, s1, s2, classifier=None):
+        """From the raw moments s1 = sum_i f_i, s2 = sum_i f_i f_i^T (fp64, what kernels.moments_accum leaves): mean = s1 / n,
+        cov = (s2 - n mean mean^T) / (n - 1); n = 1 has no covariance (NaN), and frechet_distance refuses it."""
+        s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+        mean = s1 / n
+        cov = (s2 - n * np.outer(mean, mean)) / (n - 1) if n > 1 else np.full(s2.shape, np.nan)
+        return cls(n, mean, cov, classifier)
+
+    def save(self, path):
+        """-> `path` (numpy .npz; the name is taken as given)."""
+        with open(path, 'wb') as f:
+            np.savez(f, n=np.int64(self.n), mean=self.mean, cov=self.cov, classifier=np.str_(self.classifier or ''))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(int(z['n']), z['mean'], z['cov'], str(z['classifier']) or None)
+
+
+def _psd_sqrt(cov):
+    w, v = np.linalg.eigh(cov)
+    return (v * np.sqrt(np.maximum(w, 0.0))) @ v.T
+
+
+def frechet_distance(a, b):
+    """|mu_a - mu_b|^2 + tr S_a + tr S_b - 2 tr (S_a^1/2 S_b S_a^1/2)^1/2 between two FeatureStatistics, on the host in fp64 with numpy
+    only: S_a^1/2 from eigh(S_a) with negative eigenvalues clipped at 0, the last trace as the sum of sqrt(max(lambda_k, 0)) over the
+    eigenvalues of the symmetrised product.  Singular covariances (n < D) are fine; n < 2 on either side, different widths, or fits
+    recorded under two different classifiers raise."""
+    if a.n < 2 or b.n < 2:
+        raise ValueError('frechet_distance: a covariance needs at least 2 rows (got %d and %d)' % (a.n, b.n))
+    if a.mean.shape != b.mean.shape:
+        raise ValueError('frechet_distance: %d and %d features' % (a.mean.size, b.mean.size))
+    if a.classifier is not None and b.classifier is not None and a.classifier != b.classifier:
+        raise ValueError('frechet_distance: the two statistics were computed under different classifiers')
+    root = _psd_sqrt(a.cov)
+    prod = root @ b.cov @ root
+    lam = np.linalg.eigvalsh((prod + prod.T) / 2)
+    diff = a.mean - b.mean
+    return float(diff @ diff + np.trace(a.cov) + np.trace(b.cov) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
 
 
 def _module(te):
@@ -47,9 +116,11 @@ class ClassifierScore:
     created (ct_cifar's `Generator.*` names would be picked up by the GAN modules' params_with_name('Generator')).  When PATH does not
     exist and `data_dir` (or `arrays`) is given, the classifier is trained first - ct_cifar.train (te=True: ct_cifar_te.train) for `epochs`
     epochs, which EMPTIES the registry, so construct the scorer before the GAN's parameters - saved to PATH, and the run's
-    `Generator.*` entries are removed."""
+    `Generator.*` entries are removed.
+    reference: a FeatureStatistics, or the path of a saved one (see set_reference): `score` and `score_generator` then also return
+    the classifier Frechet distance to it, `'frechet'`."""
 
-    def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, **train_kw):
+    def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, **train_kw):
         if (trainer is None) == (weights is None):
             raise ValueError('ClassifierScore: pass a trainer or weights=PATH')
         self.trainer = trainer
@@ -66,6 +137,10 @@ class ClassifierScore:
         self.dev = lib._dev()
         self.lut = torch.from_numpy(ct_cifar.byte_table()).to(self.dev)
         self._filters, self._version = {}, None
+        self._fingerprint, self._fp_version = None, None
+        self.reference = None
+        if reference is not None:
+            self.set_reference(reference)
 
     # ---- construction
     @staticmethod
@@ -109,8 +184,44 @@ class ClassifierScore:
         lib.delete_params_with_name('Generator.')
         lib.bump_epoch('Classifier')
 
+    # ---- the reference of the Frechet distance
+    def fingerprint(self):
+        """sha256 over the names, shapes and values of the Classifier.* parameters as the averaged pass sees them.  Made again (one
+        device -> host copy of the parameters) when the registry's parameter version moves; only a scorer with a reference asks."""
+        version = lib.epoch('Classifier')
+        if self._fingerprint is None or version != self._fp_version:
+            avg = dict(self.trainer.d_opt.avg_views()) if self.trainer is not None else {}
+            named = [(n, avg.get(n, p)) for n, p in lib.named_params_with_name('Classifier.') if n.startswith('Classifier.')]
+            h = hashlib.sha256()
+            for n, p in named:
+                h.update(('%s%s;' % (n, tuple(p.shape))).encode())
+            with torch.no_grad():
+                h.update(torch.cat([p.detach().reshape(-1).float() for _, p in named]).cpu().numpy().tobytes())
+            self._fingerprint, self._fp_version = h.hexdigest(), version
+        return self._fingerprint
+
+    def _check_reference(self, ref):
+        if ref.classifier is None:
+            raise ValueError('ClassifierScore: the reference statistics do not record the classifier they were computed under')
+        if ref.classifier != self.fingerprint():
+            raise ValueError('ClassifierScore: the reference statistics were computed under another classifier (%s..., this one is %s...)'
+                             % (ref.classifier[:12], self.fingerprint()[:12]))
+        if ref.mean.size != self.cfg.D_WIDTHS[-1]:
+            raise ValueError('ClassifierScore: %d reference features, %d in the classifier' % (ref.mean.size, self.cfg.D_WIDTHS[-1]))
+
+    def set_reference(self, stats_or_path):
+        """The FeatureStatistics (or the path of a saved one; None: none) that `score` / `score_generator` measure the Frechet distance
+        to.  It must have been computed under this classifier's averaged parameters - checked here and again at every scoring."""
+        ref = stats_or_path
+        if ref is not None and not isinstance(ref, FeatureStatistics):
+            ref = FeatureStatistics.load(ref)
+        if ref is not None:
+            self._check_reference(ref)
+        self.reference = ref
+
     # ---- samples in internal form -> logits
-    def _logits(self, x):
+    def _forward(self, x, features=False):
+        """-> logits [m, K]; features: (logits, the pooled features [m, D]) of the same pass."""
         version = lib.epoch('Classifier')
         if version != self._version:        # (the version also counts registry-wide bumps: a GAN that trains makes every scoring renormalise once)
             self._filters.clear()
@@ -118,14 +229,17 @@ class ClassifierScore:
 
         def run():
             with _wn.constant_filters(self._filters):
-                return ct_cifar._classifier(x, deterministic=True)
+                return ct_cifar._classifier(x, deterministic=True, features='both' if features else False)
 
         if self.trainer is not None:
-            logits = self.trainer._averaged(run, True)
+            out = self.trainer._averaged(run, True)
         else:
             with torch.no_grad():
-                logits = run()
-        return logits.contiguous()
+                out = run()
+        return (out[0].contiguous(), out[1].contiguous()) if features else out.contiguous()
+
+    def _logits(self, x):
+        return self._forward(x)
 
     # ---- the statistic
     def _begin(self, n, splits):
@@ -134,13 +248,43 @@ class ClassifierScore:
             raise ValueError('ClassifierScore: %d samples for %d splits' % (n, splits))
         return (torch.zeros(splits, nc + 1, dtype=torch.float64, device=self.dev), torch.zeros(2 * nc, dtype=torch.int64, device=self.dev))
 
-    def _finish(self, acc, cnt, n, splits, with_labels):
+    def _begin_moments(self):
+        """The caller-owned state of kernels.moments_accum, s1 [D] and s2 [D, D] as views of one zeroed fp64 buffer."""
+        d = self.cfg.D_WIDTHS[-1]
+        buf = torch.zeros(d + d * d, dtype=torch.float64, device=self.dev)
+        return buf, buf[:d], buf[d:].view(d, d)
+
+    def _statistics(self, host, n):
+        d = self.cfg.D_WIDTHS[-1]
+        return FeatureStatistics.from_moments(n, host[:d], host[d:].reshape(d, d), self.fingerprint())
+
+    def _finish(self, acc, cnt, n, splits, with_labels, moments=None):
         nc = self.cfg.N_CLASSES
         out = K.score_finish(acc, n, splits)
-        host = torch.cat([out, cnt.to(torch.float64)]).cpu().numpy()          # the scoring's one device -> host copy (counts < 2^53: exact)
-        counts = host[2 + splits:].astype(np.int64)
-        return {'mean': float(host[0]), 'std': float(host[1]), 'splits': host[2:2 + splits].copy(), 'hist': counts[:nc].copy(),
-                'acc': float(counts[nc:].sum()) / n if with_labels else None}
+        parts = [out, cnt.to(torch.float64)] + ([] if moments is None else [moments])
+        host = torch.cat(parts).cpu().numpy()                # the scoring's one device -> host copy (counts < 2^53: exact)
+        counts = host[2 + splits:2 + splits + 2 * nc].astype(np.int64)
+        res = {'mean': float(host[0]), 'std': float(host[1]), 'splits': host[2:2 + splits].copy(), 'hist': counts[:nc].copy(),
+               'acc': float(counts[nc:].sum()) / n if with_labels else None}
+        if moments is not None:
+            res['frechet'] = frechet_distance(self._statistics(host[2 + splits + 2 * nc:], n), self.reference)
+        return res
+
+    def _score_chunk(self, x, mom):
+        """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it."""
+        if mom is None:
+            return self._logits(x)
+        logits, feat = self._forward(x, True)
+        K.moments_accum(feat, mom[1], mom[2])
+        return logits
+
+    def _begin_frechet(self, n):
+        if self.reference is None:
+            return None
+        if n < 2:
+            raise ValueError('ClassifierScore: the Frechet distance needs at least 2 samples')
+        self._check_reference(self.reference)
+        return self._begin_moments()
 
     def _labels(self, labels, n):
         if labels is None:
@@ -153,7 +297,8 @@ class ClassifierScore:
     def score(self, images_u8, labels=None, splits=10, chunk=None):
         """The score of a uint8 set [N, CHANNELS, IMG, IMG] (the reference's orientation, as CifarSSLData holds it), read through
         kernels.aug_gather's fixed mode in chunks of `chunk` rows (None: min(1000, N)); labels [N]: also the accuracy.
-        -> {'mean', 'std', 'splits' [splits], 'hist' [K] predicted-class counts, 'acc' (None without labels)}."""
+        -> {'mean', 'std', 'splits' [splits], 'hist' [K] predicted-class counts, 'acc' (None without labels)}, and with a reference
+        set 'frechet', the classifier Frechet distance of the set's features to it."""
         cfg = self.cfg
         data = torch.as_tensor(images_u8)
         if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
@@ -161,6 +306,7 @@ class ClassifierScore:
                              % (cfg.CHANNELS, cfg.IMG, cfg.IMG, data.dtype, tuple(data.shape)))
         n = data.shape[0]
         acc, cnt = self._begin(n, splits)
+        mom = self._begin_frechet(n)
         data = data.to(self.dev).contiguous()
         labels = self._labels(labels, n)
         chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
@@ -169,26 +315,66 @@ class ClassifierScore:
         for r0 in range(0, n, chunk):
             m = min(chunk, n - r0)
             idx = torch.arange(r0, r0 + m, dtype=torch.int32, device=self.dev)
-            logits = self._logits(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD))
+            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom)
             K.score_accum(logits, r0, n, splits, acc, cnt, None if labels is None else labels[r0:r0 + m])
-        return self._finish(acc, cnt, n, splits, labels is not None)
+        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0])
 
     def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
         draws them - on the trainer's EVALUATION stream, in statistic groups of 100, `chunk` (a multiple of 100; None: 1000) per
         generator call, the ResNet's labels drawn there unless given - and quantised with the script's SCORE_SCALE as the saved pixels
-        are: the training stream, the weights and the optimizers stay untouched.  The ResNet's labels feed the accuracy count."""
+        are: the training stream, the weights and the optimizers stay untouched.  The ResNet's labels feed the accuracy count.  With a
+        reference set the result also holds 'frechet', from the features of the same classifier passes."""
+        ev, scale = self._evaluator(gan_trainer, 'score_generator')
+        cfg = self.cfg
+        acc, cnt = self._begin(n, splits)
+        mom = self._begin_frechet(n)
+        labels = self._labels(labels, n)
+        r0, with_labels = 0, False
+        for x, lab in ev.score_draws(n, labels, chunk):
+            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom)
+            K.score_accum(logits, r0, n, splits, acc, cnt, None if lab is None else lab.contiguous())
+            with_labels = lab is not None
+            r0 += x.shape[0]
+        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0])
+
+    def _evaluator(self, gan_trainer, what):
         from . import evaluate
         ev = evaluate.Evaluator(gan_trainer)
         cfg = self.cfg
         if ev.name not in evaluate.SCORE_SCALE or ev.mod.cfg.OUTPUT_DIM != cfg.CHANNELS * cfg.IMG * cfg.IMG:
-            raise ValueError('ClassifierScore.score_generator: %s samples are not %dx%dx%d images' % (ev.name, cfg.CHANNELS, cfg.IMG, cfg.IMG))
-        acc, cnt = self._begin(n, splits)
-        labels = self._labels(labels, n)
-        scale, r0, with_labels = evaluate.SCORE_SCALE[ev.name], 0, False
-        for x, lab in ev.score_draws(n, labels, chunk):
-            logits = self._logits(K.score_input(x, cfg.CHANNELS, scale, self.lut))
-            K.score_accum(logits, r0, n, splits, acc, cnt, None if lab is None else lab.contiguous())
-            with_labels = lab is not None
-            r0 += x.shape[0]
-        return self._finish(acc, cnt, n, splits, with_labels)
+            raise ValueError('ClassifierScore.%s: %s samples are not %dx%dx%d images' % (what, ev.name, cfg.CHANNELS, cfg.IMG, cfg.IMG))
+        return ev, evaluate.SCORE_SCALE[ev.name]
+
+    # ---- the feature statistics alone
+    def statistics(self, images_u8, chunk=None):
+        """The FeatureStatistics of a uint8 set [N, CHANNELS, IMG, IMG], read exactly as `score` reads it: what a reference is made of
+        (the training images, once; `.save(path)` keeps it)."""
+        cfg = self.cfg
+        data = torch.as_tensor(images_u8)
+        if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
+            raise ValueError('ClassifierScore.statistics: uint8 [N, %d, %d, %d] images expected (got %s %s)'
+                             % (cfg.CHANNELS, cfg.IMG, cfg.IMG, data.dtype, tuple(data.shape)))
+        n = data.shape[0]
+        if n < 1:
+            raise ValueError('ClassifierScore.statistics: no images')
+        buf, s1, s2 = self._begin_moments()
+        data = data.to(self.dev).contiguous()
+        chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError('ClassifierScore.statistics: chunk must be positive')
+        for r0 in range(0, n, chunk):
+            idx = torch.arange(r0, min(r0 + chunk, n), dtype=torch.int32, device=self.dev)
+            K.moments_accum(self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1], s1, s2)
+        return self._statistics(buf.cpu().numpy(), n)
+
+    def statistics_generator(self, gan_trainer, n, labels=None, chunk=None):
+        """The FeatureStatistics of `n` generator samples, drawn and quantised exactly as `score_generator` draws them (the evaluation
+        stream; the training stream, the weights and the optimizers stay untouched)."""
+        ev, scale = self._evaluator(gan_trainer, 'statistics_generator')
+        if n < 1:
+            raise ValueError('ClassifierScore.statistics_generator: no samples')
+        buf, s1, s2 = self._begin_moments()
+        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
+            K.moments_accum(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1], s1, s2)
+        return self._statistics(buf.cpu().numpy(), n)

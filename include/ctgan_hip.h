@@ -868,6 +868,14 @@ int ctgan_score_accum(const float* logits, int64_t m, int32_t classes, int64_t r
 /* acc -> out double [2 + splits]: out[2 + k] = exp(acc[k, classes] / n_k - sum_j m_j log m_j), m_j = acc[k, j] / n_k (a term with
  * m_j = 0 is 0), n_k the split's length; out[0] their mean, out[1] their population standard deviation.  One workgroup.          */
 int ctgan_score_finish(const double* acc, int64_t n, int32_t splits, int32_t classes, double* out, ctgan_stream_t stream);
+/* Streaming raw moments of a feature layer (csrc/moments.hip), for the classifier Frechet distance of score_cifar.py: f fp32 [m, d]
+ * row-major; s1[a] += sum_i f[i, a], s2[a, b] += sum_i f[i, a] f[i, b] in fp64, s2 the full symmetric [d, d].  Caller-owned,
+ * caller-zeroed state, 8-byte aligned; successive chunks are ordered by the stream.  The fp32 -> fp64 conversions and the fp64
+ * products are exact: the only roundings are those of the sums.  One workgroup per pair (ti <= tj) of 16-column tiles on
+ * v_mfma_f64_16x16x4_f64, four waves with a fixed quarter of the rows each, folded through LDS in wave order; every state element
+ * has one owning workgroup, which adds with a plain load and store (no atomics): the same chunking gives the same bits, and s2 is
+ * exactly symmetric.  m == 0: nothing is launched.  d > 1024: CTGAN_E_UNSUPPORTED, nothing is launched.                          */
+int ctgan_moments_accum(const float* f, int64_t m, int32_t d, double* s1, double* s2, ctgan_stream_t stream);
 
 
 #ifdef __cplusplus
