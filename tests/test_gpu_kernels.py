@@ -264,7 +264,8 @@ def test_conv_vector_and_generic_paths_agree_bitwise(K):
     assert torch.equal(y_vec, y_gen)
 
 
-# (N, H, up, stride-2 dgrad?) -> every pipelined tile configuration, incl. the K-split one
+# (N, H, up) -> the pipelined tile configurations 1, 8, 11, 10, 5, 11 (upsampled) and 5 of dispatch_fwd_pipe, incl. the K-split ones
+# (configurations 2, 3 and 4, every threshold and the symbol that ran: test_gpu_kernels_fp32_paths.py)
 @pytest.mark.parametrize('N,H,up', [(128, 32, False), (64, 16, False), (24, 16, False), (64, 8, False), (7, 8, False),
                                      (128, 8, True), (3, 4, False)])
 def test_pipelined_conv_matches_table_driven_kernel(K, N, H, up):
