@@ -9,6 +9,7 @@ Two kinds of checks per geometry and operator (forward, data gradient, weight gr
 BASELINE.json configs[1] (DCGAN 5x5 stride-2 convs / transposed convs) and configs[4] (3x3, 3x3 stride 2, 4x4 stride-2
 resampling convs at 64..1024 channels) geometries.
 """
+import ctypes
 import zlib
 
 import numpy as np
@@ -54,7 +55,8 @@ EPS = {'bf16': 2.0 ** -9, 'f16': 2.0 ** -12}
 CASES = [
     (4, 128, 16, 16, 256, 5, 2),      # DCGAN critic layer 2 (:92); its data gradient = Deconv2D 256->128 of the generator (:70)
     (8, 256, 8, 8, 512, 5, 2),        # DCGAN critic layer 3 / Deconv2D 512->256
-    (64, 128, 16, 16, 256, 5, 2),     # the same at batch 64: 128x128 tiles
+    (64, 128, 16, 16, 256, 5, 2),     # the same at batch 64: 32 x 2 = 64 forward and 4 x 32 x 1 = 128 data-gradient tiles of 128x128 - below 192, still
+                                      # 64x64 tiles (the wider tiles: tests/test_gpu_kernels16_paths.py)
     (4, 64, 16, 16, 128, 3, 1),       # 3x3 stride 1, C = 64
     (3, 32, 8, 8, 32, 3, 1),          # C = 32: the 32-deep K slice variant; K = 32: partial kout tile
     (2, 96, 8, 12, 160, 3, 1),        # C = 96 (32-deep slices), K = 160 (partial tiles), H != W
@@ -103,8 +105,12 @@ def test_conv16_fwd_dgrad_wgrad(K, case, dt):
             gx2 = K.conv_dgrad(gyd, wd, geom, N, bias=bc.cuda(), mask=cl(m), resid=cl(rr))
             ref_gx2 = torch.where(m.double() > 0, gx_ref + bc.double().view(1, -1, 1, 1), torch.zeros_like(gx_ref)) + rr.double()
             ok, e, what = tol(gx2, ref_gx2, 'dgrad+epilogue'); assert ok, (what, e)
-            if C % 64 == 0 and geom.Q % 4 == 0:
+            d16 = geom.desc(N, xd.stride(), gyd.stride())
+            wgrad16 = bool(K.lib.ctgan_conv2d16_supported(ctypes.byref(d16), 2, K._MMA_CODE[dt]))
+            assert wgrad16 == (C % 64 == 0 and geom.Q % 4 == 0), (case, wgrad16)      # the library refuses exactly the cases left out here
+            if wgrad16:
                 gw, gb = K.conv_wgrad(xd, gyd, geom, with_bias=True)
+                assert K.last_kernel().startswith('wgrad16'), K.last_kernel()
                 ok, e, what = tol(gw, gw_ref, 'wgrad'); assert ok, (what, e)
                 assert relerr(gb, gy.double().sum(dim=(0, 2, 3))) < 2e-5
                 gw2 = K.conv_wgrad(xd, gyd, geom, relu_x=True)
