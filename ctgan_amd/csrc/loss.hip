@@ -902,7 +902,10 @@ int ctgan_gp_head_grad(const float* y, const float* w_out, int32_t n, int32_t hw
     if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gz) | reinterpret_cast<uintptr_t>(w_out)) & 15)
         return ctgan_fail(CTGAN_E_BADARG, "gp_head_grad: unaligned");
     const long long n4 = (long long)n * hw * nf / 4;
-    hipLaunchKernelGGL(gp_head_grad_kernel, dim3(ctgan_blocks(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(s), y, w_out, n4, nf,
+    // one float4 per thread and no stride loop: the grid must cover n4 (ctgan_blocks' default cap of 4096 left everything past
+    // 4,194,304 elements unwritten)
+    if ((n4 + 255) / 256 > 0x7fffffffLL) return ctgan_fail(CTGAN_E_BADARG, "gp_head_grad: too large");
+    hipLaunchKernelGGL(gp_head_grad_kernel, dim3(ctgan_blocks(n4, 256, 0x7fffffff)), dim3(256), 0, static_cast<hipStream_t>(s), y, w_out, n4, nf,
                        mask_scale / (float)hw, gz);
     return ctgan_check_launch("gp_head_grad");
 }
