@@ -304,7 +304,7 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
     (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series (and `frechet`
-    when it is a score_cifar.ClassifierScore with a reference); the fixed-noise sample grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
+    when it is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a manifold); the fixed-noise sample grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
     `dev_every`-th.  Returns the trainer."""
     import os
     import time

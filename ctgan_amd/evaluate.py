@@ -339,7 +339,8 @@ class Evaluator:
 def record_score(ev, series, classifier):
     """One scoring of the loops: the script's sample count through `classifier`, recorded under the script's series names.  A
     score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels
-    and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it."""
+    and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it; when it has
+    a manifold (ClassifierScore.set_manifold), `precision`, `recall` and `nn_dist`: the k-nearest-neighbour manifold estimate against it."""
     if ev.name not in SCORE_SERIES:
         return
     from .score_cifar import ClassifierScore
@@ -351,6 +352,9 @@ def record_score(ev, series, classifier):
             series.add('score_acc', res['acc'])
         if 'frechet' in res:
             series.add('frechet', res['frechet'])
+        for name in ('precision', 'recall', 'nn_dist'):
+            if name in res:
+                series.add(name, res[name])
         return
     score = ev.get_inception_score(SCORE_SAMPLES[ev.name], classifier)
     for name, value in zip(SCORE_SERIES[ev.name], score):

@@ -756,7 +756,8 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
     every `dev_every` iterations (:421-427, evaluate.Evaluator.dev_cost) and - with a `classifier` (no Inception graph ships: the 2015
     graph needs a network) - `inception_50k` / `inception_50k_std` every `score_every` iterations (:414-418), and
-    `frechet` when the classifier is a score_cifar.ClassifierScore with a reference (evaluate.record_score)."""
+    `frechet` when the classifier is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a
+    manifold (evaluate.record_score)."""
     import os
     import time
 

@@ -2649,3 +2649,45 @@ def moments_accum(feat, s1, s2):
         assert t.dtype == torch.float64 and t.is_contiguous(), 'contiguous fp64 state expected'
     assert tuple(s1.shape) == (d,) and tuple(s2.shape) == (d, d), 's1 [D], s2 [D, D] expected'
     check(lib.ctgan_moments_accum(_ptr(feat), m, d, _ptr(s1), _ptr(s2), _stream()), 'moments_accum')
+
+
+# ---------------------------------------------------------------- k-nearest-neighbour manifold estimate (csrc/knn.hip)
+KNN_MAX_K = lib.ctgan_knn_max_k()
+
+
+def _knn_out(out, rows, dtype, what, device):
+    """A caller's output buffer (at least `rows` long; what lies past `rows` stays untouched), or a new one."""
+    if out is None:
+        return torch.empty(rows, dtype=dtype, device=device)
+    if not out.is_cuda:
+        raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % out.device)
+    assert out.dtype == dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= rows, '%s: contiguous %s [>= %d] expected' % (what, dtype, rows)
+    return out
+
+
+def knn_radii(feat, k, out=None):
+    """feat fp32 [n, D] -> fp64 [n]: the squared distance from every row to its k-th nearest OTHER row (self excluded by index; a
+    bit-identical duplicate counts, at exactly 0).  1 <= k <= KNN_MAX_K, n >= k + 1, D <= 1024."""
+    _need_dev(feat)
+    n, d = _rows2d(feat)
+    out = _knn_out(out, n, torch.float64, 'knn_radii', feat.device)
+    check(lib.ctgan_knn_radii(_ptr(feat), n, d, int(k), _ptr(out), _stream()), 'knn_radii')
+    return out
+
+
+def knn_cover(a, b, r2_b=None, covered=None, nn_d2=None, nn_idx=None):
+    """a fp32 [m, D] against b fp32 [n, D] with the squared radii r2_b fp64 [n] (None: nearest neighbours only)
+    -> (covered int32 [m]: 1 iff a_i lies inside some ball (b_j, r2_b[j]) - None without radii; nn_d2 fp64 [m]: the squared distance to
+    the nearest row of b; nn_idx int32 [m]: the lowest index attaining it).  No [m, n] array exists."""
+    _need_dev(a, b)
+    if r2_b is not None and not r2_b.is_cuda:
+        raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % r2_b.device)
+    m, d = _rows2d(a)
+    n, db = _rows2d(b)
+    assert d == db, 'knn_cover: %d and %d features' % (d, db)
+    assert r2_b is None or (r2_b.dtype == torch.float64 and r2_b.is_contiguous() and r2_b.numel() == n), 'knn_cover: fp64 radii [n] expected'
+    covered = None if r2_b is None else _knn_out(covered, m, torch.int32, 'knn_cover', a.device)
+    nn_d2 = _knn_out(nn_d2, m, torch.float64, 'knn_cover', a.device)
+    nn_idx = _knn_out(nn_idx, m, torch.int32, 'knn_cover', a.device)
+    check(lib.ctgan_knn_cover(_ptr(a), m, _ptr(b), n, d, _ptr(r2_b), _ptr(covered), _ptr(nn_d2), _ptr(nn_idx), _stream()), 'knn_cover')
+    return covered, nn_d2, nn_idx

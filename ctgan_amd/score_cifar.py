@@ -31,6 +31,20 @@ added or changed, and without a reference the launches and the returned dict are
 Like the score it is a CLASSIFIER statistic, under a self-trained 10-class network: it is NOT comparable to published FID numbers
 (Inception pool3, 2048 features, ImageNet).  A reference records a hash of the classifier's averaged parameters; under any other
 classifier it is refused.
+
+Precision and recall.  With a manifold set (`manifold=` / `set_manifold`, a FeatureSet: the reference FEATURES, not their fit), `score`
+and `score_generator` also return the k-nearest-neighbour manifold estimate of Kynkaanniemi et al. 2019 in the same feature space:
+`'precision'`, the share of samples inside some reference row's k-th-neighbour ball, `'recall'`, the share of reference rows inside
+some sample's ball, and the memorisation signal: `'nn_dist'`, the median distance of a sample to its nearest reference row, and
+`'nn_zero'`, the number of samples AT distance 0 from one (a replayed reference image).
+    features [m, D] -> one [n, D] buffer   a device copy per chunk, from the same classifier pass as the logits
+    samples vs reference balls             kernels.knn_cover: covered, nearest reference row (fp64 MFMA, no [m, n] array)
+    sample radii, reference vs them        kernels.knn_radii, kernels.knn_cover
+                                           all three once, after the last chunk: a workgroup owns 64 sample rows, so a launch per chunk
+                                           of 1,000 would leave most of the chip idle (measured: DESIGN 19)
+    counts and the median                  reduced on the device, in the scoring's one device -> host copy
+Classifier statistics again: a manifold estimate under a self-trained 10-class network's 128 features, NOT comparable to published
+precision / recall (VGG-16 or Inception features).  A FeatureSet records the classifier's hash as a FeatureStatistics does.
 """
 import hashlib
 import os
@@ -102,6 +116,104 @@ def frechet_distance(a, b):
     return float(diff @ diff + np.trace(a.cov) + np.trace(b.cov) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
 
 
+class FeatureSet:
+    """The feature rows themselves, fp32 [n, D], of a set under the classifier with hash `classifier` (None: synthetic), with the squared
+    k-th-neighbour radii that `radii(k)` computes on the device once per k and keeps (and `save` writes with the features)."""
+
+    def __init__(self, features, classifier=None, radii=None):
+        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32))
+        if f.dim() != 2 or f.dtype != torch.float32 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError('FeatureSet: fp32 [n, D] features expected (got %s %s)' % (f.dtype, tuple(f.shape)))
+        self.features = f.detach().contiguous()
+        self.classifier = None if classifier is None else str(classifier)
+        self._radii = {}
+        for k, r in (radii or {}).items():
+            r = r if isinstance(r, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(r, dtype=np.float64))
+            if r.dtype != torch.float64 or tuple(r.shape) != (self.n,):
+                raise ValueError('FeatureSet: radii of k = %s are not fp64 [%d]' % (k, self.n))
+            self._radii[int(k)] = r.contiguous()
+
+    @property
+    def n(self):
+        return self.features.shape[0]
+
+    @property
+    def width(self):
+        return self.features.shape[1]
+
+    def device_features(self):
+        """The features on the project's device (moved there once)."""
+        dev = lib._dev()
+        if self.features.device != dev:
+            self.features = self.features.to(dev)
+        return self.features
+
+    def radii(self, k):
+        """fp64 [n] on the device: the squared distance of every row to its k-th nearest other row (kernels.knn_radii, once per k)."""
+        k = int(k)
+        if k not in self._radii:
+            if self.n < k + 1:
+                raise ValueError('FeatureSet: %d rows have no %d-th other neighbour' % (self.n, k))
+            self._radii[k] = K.knn_radii(self.device_features(), k)
+        dev = lib._dev()
+        if self._radii[k].device != dev:
+            self._radii[k] = self._radii[k].to(dev)
+        return self._radii[k]
+
+    def save(self, path):
+        """-> `path` (numpy .npz; the name is taken as given): the features, the classifier's hash and every radius computed so far."""
+        arrays = {'radii_%d' % k: r.cpu().numpy() for k, r in self._radii.items()}
+        with open(path, 'wb') as f:
+            np.savez(f, features=self.features.cpu().numpy(), classifier=np.str_(self.classifier or ''),
+                     radii_k=np.asarray(sorted(self._radii), dtype=np.int64), **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(z['features'], str(z['classifier']) or None, {int(k): z['radii_%d' % k] for k in z['radii_k']})
+
+
+def _manifold_counts(samples, reference, k):
+    """The device half of precision_recall -> fp64 [5] on the device: the samples inside some reference ball, the reference rows inside
+    some sample ball, the samples at distance 0 from a reference row, and the square roots of the two middle elements of the sorted
+    nearest-reference distances (their mean is the median).  samples: device features [m, D]."""
+    m = samples.shape[0]
+    ref = reference.device_features()
+    covered, nn_d2, _ = K.knn_cover(samples, ref, reference.radii(k))
+    back, _, _ = K.knn_cover(ref, samples, K.knn_radii(samples, k))
+    ordered = torch.sort(nn_d2).values
+    mid = torch.sqrt(torch.stack([ordered[(m - 1) // 2], ordered[m // 2]]))
+    return torch.cat([torch.stack([covered.sum(), back.sum(), (nn_d2 == 0).sum()]).to(torch.float64), mid])
+
+
+def _manifold_result(host, m, n, k):
+    return {'precision': float(host[0]) / m, 'recall': float(host[1]) / n, 'k': int(k), 'nn_dist': float((host[3] + host[4]) / 2),
+            'nn_zero': int(host[2])}
+
+
+def _check_sets(samples, reference, k):
+    if samples.width != reference.width:
+        raise ValueError('precision_recall: %d and %d features' % (samples.width, reference.width))
+    if samples.classifier is not None and reference.classifier is not None and samples.classifier != reference.classifier:
+        raise ValueError('precision_recall: the two feature sets were computed under different classifiers')
+    if k < 1 or k > K.KNN_MAX_K:
+        raise ValueError('precision_recall: k = %d (1 to %d)' % (k, K.KNN_MAX_K))
+    if samples.n < k + 1 or reference.n < k + 1:
+        raise ValueError('precision_recall: %d and %d rows have no %d-th other neighbour' % (samples.n, reference.n, k))
+
+
+def precision_recall(samples, reference, k=3):
+    """The k-nearest-neighbour manifold estimate (Kynkaanniemi et al. 2019) between two FeatureSets, on the device:
+    -> {'precision': the share of samples within the k-th-neighbour radius of some reference row, 'recall': the share of reference rows
+    within that of some sample, 'k', 'nn_dist': the median over the samples of the distance to the nearest reference row, 'nn_zero': the
+    number of samples at distance exactly 0 from a reference row - bit-identical features}.  Different widths, sets recorded under two
+    different classifiers, or fewer than k + 1 rows on a side raise."""
+    k = int(k)
+    _check_sets(samples, reference, k)
+    host = _manifold_counts(samples.device_features(), reference, k).cpu().numpy()
+    return _manifold_result(host, samples.n, reference.n, k)
+
+
 def _module(te):
     if te:
         from . import ct_cifar_te
@@ -118,9 +230,12 @@ class ClassifierScore:
     epochs, which EMPTIES the registry, so construct the scorer before the GAN's parameters - saved to PATH, and the run's
     `Generator.*` entries are removed.
     reference: a FeatureStatistics, or the path of a saved one (see set_reference): `score` and `score_generator` then also return
-    the classifier Frechet distance to it, `'frechet'`."""
+    the classifier Frechet distance to it, `'frechet'`.
+    manifold: a FeatureSet, or the path of a saved one (see set_manifold), manifold_k: the neighbour count: `score` and `score_generator`
+    then also return `'precision'`, `'recall'`, `'nn_dist'` and `'nn_zero'` against it (precision_recall)."""
 
-    def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, **train_kw):
+    def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, manifold=None, manifold_k=3,
+                 **train_kw):
         if (trainer is None) == (weights is None):
             raise ValueError('ClassifierScore: pass a trainer or weights=PATH')
         self.trainer = trainer
@@ -141,6 +256,9 @@ class ClassifierScore:
         self.reference = None
         if reference is not None:
             self.set_reference(reference)
+        self.manifold, self.manifold_k = None, int(manifold_k)
+        if manifold is not None:
+            self.set_manifold(manifold, manifold_k)
 
     # ---- construction
     @staticmethod
@@ -219,6 +337,32 @@ class ClassifierScore:
             self._check_reference(ref)
         self.reference = ref
 
+    # ---- the manifold of precision and recall
+    def _check_manifold(self, ref):
+        if ref.classifier is None:
+            raise ValueError('ClassifierScore: the manifold features do not record the classifier they were computed under')
+        if ref.classifier != self.fingerprint():
+            raise ValueError('ClassifierScore: the manifold features were computed under another classifier (%s..., this one is %s...)'
+                             % (ref.classifier[:12], self.fingerprint()[:12]))
+        if ref.width != self.cfg.D_WIDTHS[-1]:
+            raise ValueError('ClassifierScore: %d manifold features, %d in the classifier' % (ref.width, self.cfg.D_WIDTHS[-1]))
+
+    def set_manifold(self, features_or_path, k=None):
+        """The FeatureSet (or the path of a saved one; None: none) that `score` / `score_generator` measure precision and recall
+        against, with `k` neighbours (None: as it is).  It must have been computed under this classifier's averaged parameters and hold
+        at least k + 1 rows - checked here and again at every scoring."""
+        ref = features_or_path
+        if ref is not None and not isinstance(ref, FeatureSet):
+            ref = FeatureSet.load(ref)
+        k = self.manifold_k if k is None else int(k)
+        if k < 1 or k > K.KNN_MAX_K:
+            raise ValueError('ClassifierScore: manifold_k = %d (1 to %d)' % (k, K.KNN_MAX_K))
+        if ref is not None:
+            self._check_manifold(ref)
+            if ref.n < k + 1:
+                raise ValueError('ClassifierScore: %d manifold rows have no %d-th other neighbour' % (ref.n, k))
+        self.manifold, self.manifold_k = ref, k
+
     # ---- samples in internal form -> logits
     def _forward(self, x, features=False):
         """-> logits [m, K]; features: (logits, the pooled features [m, D]) of the same pass."""
@@ -258,25 +402,43 @@ class ClassifierScore:
         d = self.cfg.D_WIDTHS[-1]
         return FeatureStatistics.from_moments(n, host[:d], host[d:].reshape(d, d), self.fingerprint())
 
-    def _finish(self, acc, cnt, n, splits, with_labels, moments=None):
+    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None):
         nc = self.cfg.N_CLASSES
         out = K.score_finish(acc, n, splits)
         parts = [out, cnt.to(torch.float64)] + ([] if moments is None else [moments])
+        if man is not None:                                  # three launches over all n samples, once, after the last chunk
+            parts.append(_manifold_counts(man['feat'], self.manifold, self.manifold_k))
         host = torch.cat(parts).cpu().numpy()                # the scoring's one device -> host copy (counts < 2^53: exact)
         counts = host[2 + splits:2 + splits + 2 * nc].astype(np.int64)
         res = {'mean': float(host[0]), 'std': float(host[1]), 'splits': host[2:2 + splits].copy(), 'hist': counts[:nc].copy(),
                'acc': float(counts[nc:].sum()) / n if with_labels else None}
         if moments is not None:
-            res['frechet'] = frechet_distance(self._statistics(host[2 + splits + 2 * nc:], n), self.reference)
+            res['frechet'] = frechet_distance(self._statistics(host[2 + splits + 2 * nc:2 + splits + 2 * nc + moments.numel()], n), self.reference)
+        if man is not None:
+            res.update(_manifold_result(host[-5:], n, self.manifold.n, self.manifold_k))
+            del res['k']
         return res
 
-    def _score_chunk(self, x, mom):
-        """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it."""
-        if mom is None:
+    def _score_chunk(self, x, mom, man=None, r0=0):
+        """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it; with
+        the state of one that has a manifold, they are copied to rows r0.. of its buffer."""
+        if mom is None and man is None:
             return self._logits(x)
         logits, feat = self._forward(x, True)
-        K.moments_accum(feat, mom[1], mom[2])
+        if mom is not None:
+            K.moments_accum(feat, mom[1], mom[2])
+        if man is not None:
+            man['feat'][r0:r0 + feat.shape[0]].copy_(feat)
         return logits
+
+    def _begin_manifold(self, n):
+        """The state of a scoring with a manifold: the one [n, D] device buffer the chunks' features are copied into."""
+        if self.manifold is None:
+            return None
+        if n < self.manifold_k + 1:
+            raise ValueError('ClassifierScore: %d samples have no %d-th other neighbour' % (n, self.manifold_k))
+        self._check_manifold(self.manifold)
+        return {'feat': torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)}
 
     def _begin_frechet(self, n):
         if self.reference is None:
@@ -298,7 +460,8 @@ class ClassifierScore:
         """The score of a uint8 set [N, CHANNELS, IMG, IMG] (the reference's orientation, as CifarSSLData holds it), read through
         kernels.aug_gather's fixed mode in chunks of `chunk` rows (None: min(1000, N)); labels [N]: also the accuracy.
         -> {'mean', 'std', 'splits' [splits], 'hist' [K] predicted-class counts, 'acc' (None without labels)}, and with a reference
-        set 'frechet', the classifier Frechet distance of the set's features to it."""
+        set 'frechet', the classifier Frechet distance of the set's features to it, and with a manifold set 'precision', 'recall',
+        'nn_dist' and 'nn_zero' (precision_recall) of them against it."""
         cfg = self.cfg
         data = torch.as_tensor(images_u8)
         if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
@@ -307,6 +470,7 @@ class ClassifierScore:
         n = data.shape[0]
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
+        man = self._begin_manifold(n)
         data = data.to(self.dev).contiguous()
         labels = self._labels(labels, n)
         chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
@@ -315,28 +479,30 @@ class ClassifierScore:
         for r0 in range(0, n, chunk):
             m = min(chunk, n - r0)
             idx = torch.arange(r0, r0 + m, dtype=torch.int32, device=self.dev)
-            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom)
+            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0)
             K.score_accum(logits, r0, n, splits, acc, cnt, None if labels is None else labels[r0:r0 + m])
-        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0])
+        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man)
 
     def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
         draws them - on the trainer's EVALUATION stream, in statistic groups of 100, `chunk` (a multiple of 100; None: 1000) per
         generator call, the ResNet's labels drawn there unless given - and quantised with the script's SCORE_SCALE as the saved pixels
         are: the training stream, the weights and the optimizers stay untouched.  The ResNet's labels feed the accuracy count.  With a
-        reference set the result also holds 'frechet', from the features of the same classifier passes."""
+        reference set the result also holds 'frechet', with a manifold set 'precision', 'recall', 'nn_dist' and 'nn_zero', all from the
+        features of the same classifier passes."""
         ev, scale = self._evaluator(gan_trainer, 'score_generator')
         cfg = self.cfg
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
+        man = self._begin_manifold(n)
         labels = self._labels(labels, n)
         r0, with_labels = 0, False
         for x, lab in ev.score_draws(n, labels, chunk):
-            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom)
+            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0)
             K.score_accum(logits, r0, n, splits, acc, cnt, None if lab is None else lab.contiguous())
             with_labels = lab is not None
             r0 += x.shape[0]
-        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0])
+        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man)
 
     def _evaluator(self, gan_trainer, what):
         from . import evaluate
@@ -378,3 +544,38 @@ class ClassifierScore:
         for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
             K.moments_accum(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1], s1, s2)
         return self._statistics(buf.cpu().numpy(), n)
+
+    # ---- the features themselves
+    def features(self, images_u8, chunk=None):
+        """The FeatureSet of a uint8 set [N, CHANNELS, IMG, IMG], read exactly as `statistics` reads it: what a manifold is made of (the
+        training images, once; `.save(path)` keeps it with its radii)."""
+        cfg = self.cfg
+        data = torch.as_tensor(images_u8)
+        if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
+            raise ValueError('ClassifierScore.features: uint8 [N, %d, %d, %d] images expected (got %s %s)'
+                             % (cfg.CHANNELS, cfg.IMG, cfg.IMG, data.dtype, tuple(data.shape)))
+        n = data.shape[0]
+        if n < 1:
+            raise ValueError('ClassifierScore.features: no images')
+        out = torch.empty(n, cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
+        data = data.to(self.dev).contiguous()
+        chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError('ClassifierScore.features: chunk must be positive')
+        for r0 in range(0, n, chunk):
+            idx = torch.arange(r0, min(r0 + chunk, n), dtype=torch.int32, device=self.dev)
+            out[r0:r0 + chunk].copy_(self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1])
+        return FeatureSet(out, self.fingerprint())
+
+    def features_generator(self, gan_trainer, n, labels=None, chunk=None):
+        """The FeatureSet of `n` generator samples, drawn and quantised exactly as `statistics_generator` draws them (the evaluation
+        stream; the training stream, the weights and the optimizers stay untouched)."""
+        ev, scale = self._evaluator(gan_trainer, 'features_generator')
+        if n < 1:
+            raise ValueError('ClassifierScore.features_generator: no samples')
+        out = torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
+        r0 = 0
+        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
+            out[r0:r0 + x.shape[0]].copy_(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1])
+            r0 += x.shape[0]
+        return FeatureSet(out, self.fingerprint())

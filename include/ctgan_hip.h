@@ -876,6 +876,22 @@ int ctgan_score_finish(const double* acc, int64_t n, int32_t splits, int32_t cla
  * has one owning workgroup, which adds with a plain load and store (no atomics): the same chunking gives the same bits, and s2 is
  * exactly symmetric.  m == 0: nothing is launched.  d > 1024: CTGAN_E_UNSUPPORTED, nothing is launched.                          */
 int ctgan_moments_accum(const float* f, int64_t m, int32_t d, double* s1, double* s2, ctgan_stream_t stream);
+/* The k-nearest-neighbour manifold estimate in a feature space (csrc/knn.hip), for the precision and recall of score_cifar.py.  The
+ * squared distance is d2(i, j) = max(0, |a_i|^2 + |b_j|^2 - 2 a_i . b_j), every term in fp64 over the fp32 features widened exactly; the
+ * dot products and both norms run on v_mfma_f64_16x16x4_f64 through the same k-ordered chain, so two bit-identical rows are at
+ * d2 == 0.0 exactly and bit-identical rows of b give bit-identical distances.  A workgroup owns 64 rows of a and streams b through
+ * LDS; no [m, n] array, no atomics, one owner per output element: two runs give the same bits.  Features are finite by precondition;
+ * a NaN distance compares false - never a neighbour, never covering.
+ * ctgan_knn_radii: f fp32 [n, d] row-major -> r2 fp64 [n], r2[i] the squared distance from row i to its k-th nearest OTHER row (self
+ * is excluded by index: a bit-identical duplicate elsewhere counts, at distance 0).  k < 1 or n < k + 1: CTGAN_E_BADARG;
+ * k > ctgan_knn_max_k() (8) or d > 1024: CTGAN_E_UNSUPPORTED; nothing is launched either way.
+ * ctgan_knn_cover: a fp32 [m, d], b fp32 [n, d], r2_b fp64 [n] or NULL -> covered int32 [m] = 1 iff some j has d2(i, j) <= r2_b[j]
+ * (not written, and may be NULL, when r2_b is NULL), nn_d2 fp64 [m] = min_j d2(i, j), nn_idx int32 [m] = the LOWEST j attaining it
+ * (all distances NaN: +inf and -1).  m == 0: nothing is launched.  n < 1: CTGAN_E_BADARG.  d > 1024: CTGAN_E_UNSUPPORTED.        */
+int ctgan_knn_max_k(void);
+int ctgan_knn_radii(const float* f, int64_t n, int32_t d, int32_t k, double* r2, ctgan_stream_t stream);
+int ctgan_knn_cover(const float* a, int64_t m, const float* b, int64_t n, int32_t d, const double* r2_b, int32_t* covered, double* nn_d2,
+                    int32_t* nn_idx, ctgan_stream_t stream);
 
 
 #ifdef __cplusplus
