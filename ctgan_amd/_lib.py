@@ -96,16 +96,13 @@ SIGNATURES = {
     'ctgan_conv2d_wgrad_multi': (c_int, [POINTER(ConvDesc), c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), _p, _p, _p,
                                          c_size_t, _p]),
     'ctgan_conv2d_wgrad_group_workspace_bytes': (c_size_t, [POINTER(WgradGroup), c_int32]),
-    'ctgan_conv2d_wgrad_group': (c_int, [POINTER(WgradGroup), c_int32, _p, c_size_t, _p]),
-    'ctgan_conv2d_wgrad_group_ex': (c_int, [POINTER(WgradGroup), c_int32, _p, c_size_t, c_int, _p]),
+    'ctgan_conv2d_wgrad_group': (c_int, [POINTER(WgradGroup), c_int32, _p, c_size_t, c_int, _p]),
     'ctgan_conv2d16_wgrad_group_workspace_bytes': (c_size_t, [POINTER(WgradGroup), c_int32, c_int]),
     'ctgan_conv2d16_wgrad_group': (c_int, [POINTER(WgradGroup), c_int32, c_int, _p, c_size_t, c_int, _p]),
     'ctgan_conv2d_wgrad_group_tile': (c_int, [POINTER(WgradGroup)]),
     'ctgan_conv2d_workspace_bytes': (c_size_t, [_D, c_int]),
-    'ctgan_conv2d_fwd': (c_int, [_D, _p, _p, _p, _p, _p, c_int, _p]),
-    'ctgan_conv2d_fwd_ex': (c_int, [_D, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p]),
-    'ctgan_conv2d_dgrad_ex': (c_int, [_D, _p, _p, _p, _p, _p, _p, _p, c_size_t, c_int, POINTER(EpilogueExt), _p]),
-    'ctgan_conv2d_dgrad': (c_int, [_D, _p, _p, _p, _p, _p, _p, _p, c_size_t, c_int, _p]),
+    'ctgan_conv2d_fwd': (c_int, [_D, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p]),
+    'ctgan_conv2d_dgrad': (c_int, [_D, _p, _p, _p, _p, _p, _p, _p, c_size_t, c_int, POINTER(EpilogueExt), _p]),
     'ctgan_conv2d_repack_filter': (c_int, [_D, _p, _p, _p]),
     'ctgan_conv2d_wgrad': (c_int, [_D, _p, _p, _p, _p, _p, c_size_t, c_int, _p]),
     'ctgan_conv2d16_supported': (c_int, [_D, c_int, c_int]),
@@ -116,13 +113,10 @@ SIGNATURES = {
     'ctgan_conv2d16_pack_filter': (c_int, [_D, c_int, c_int, _p, _p, _p]),
     'ctgan_conv2d16_pack_batch': (c_int, [POINTER(ConvDesc), POINTER(c_int32), c_int32, c_int, POINTER(c_void_p), POINTER(c_void_p), _p]),
     'ctgan_conv2d16_workspace_bytes': (c_size_t, [_D, c_int]),
-    'ctgan_conv2d16_fwd': (c_int, [_D, c_int, _p, _p, _p, _p, _p, c_int, _p, c_size_t, _p]),
-    'ctgan_conv2d16_fwd_ex': (c_int, [_D, c_int, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p, c_size_t, _p]),
-    'ctgan_conv2d16_dgrad': (c_int, [_D, c_int, _p, _p, _p, _p, _p, _p, c_int, _p, c_size_t, _p]),
-    'ctgan_conv2d16_dgrad_ex': (c_int, [_D, c_int, _p, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p, c_size_t, _p]),
+    'ctgan_conv2d16_fwd': (c_int, [_D, c_int, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p, c_size_t, _p]),
+    'ctgan_conv2d16_dgrad': (c_int, [_D, c_int, _p, _p, _p, _p, _p, _p, c_int, POINTER(EpilogueExt), _p, c_size_t, _p]),
     'ctgan_conv2d16_wgrad_workspace_bytes': (c_size_t, [_D, c_int]),
-    'ctgan_conv2d16_wgrad': (c_int, [_D, c_int, _p, _p, _p, _p, c_size_t, c_int, _p]),
-    'ctgan_conv2d16_wgrad_bias': (c_int, [_D, c_int, _p, _p, _p, _p, _p, c_size_t, c_int, _p]),
+    'ctgan_conv2d16_wgrad': (c_int, [_D, c_int, _p, _p, _p, _p, _p, c_size_t, c_int, _p]),
     'ctgan_layernorm_supported': (c_int, [c_int64, c_int32]),
     'ctgan_layernorm_workspace_bytes': (c_size_t, [c_int32, c_int64, c_int32]),
     'ctgan_layernorm_fwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int64, c_int32, c_float, c_int32, _p, c_size_t, _p]),
@@ -197,20 +191,15 @@ SIGNATURES = {
     'ctgan_critic_heads_fwd': (c_int, [_p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_critic_heads_bwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_tail_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, _p]),
-    'ctgan_tail_critic_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, c_float, c_float, c_float,
-                                            _p, _p, _p, _p, _p, _p, _p, _p]),
-    'ctgan_tail_critic_heads_fwd2': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, c_float, _p, c_int32, _p, _p, _p,
-                                             c_float, c_float, c_float, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'ctgan_tail_critic_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, c_float, _p, c_int32, _p, _p, _p,
+                                            c_float, c_float, c_float, _p, _p, _p, _p, _p, _p, _p, _p]),
     'ctgan_tail_heads_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
-                                     _p, _p, _p, _p, _p, _p, _p, _p]),
-    'ctgan_tail_heads_bwd_gp': (c_int, [_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
-                                        _p, _p, _p, _p, _p, _p, _p, _p, c_int32, _p, _p]),
+                                     _p, _p, _p, _p, _p, _p, _p, _p, c_int32, _p, _p]),
     'ctgan_gen_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, c_float, _p, _p, _p, _p, _p, _p]),
     'ctgan_gen_heads_bwd': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _p, _p, _p, _p]),
     'ctgan_gp_head_grad': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p]),
-    'ctgan_gp_head_wgrad_acc': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, _p]),
     'ctgan_gp_finish': (c_int, [_p, _p, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_float, _p, _p]),
-    'ctgan_gp_head_wgrad': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, _p]),
+    'ctgan_gp_head_wgrad': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, c_int, _p]),
     'ctgan_accuracy2': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
     'ctgan_adam_step': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
     'ctgan_adam_advance': (c_int, [_p, c_float, c_float, _p]),

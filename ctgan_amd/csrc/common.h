@@ -21,6 +21,48 @@ static inline unsigned ctgan_blocks(long long n, int per_block, int cap = 4096) 
     return (unsigned)b;
 }
 
+// ---- ctgan_epilogue_ext -> the kernels' dropout parameters (igemm.hip FwdParams, igemm16.hip P16) ----
+// a tensor of C channels on an H x W grid with these (n, c, h, w) element strides is dense channels-last
+static inline bool dense_channels_last(const int64_t* s, int C, int H, int W) {
+    return s[1] == 1 && s[3] == C && s[2] == (int64_t)W * C && s[0] == (int64_t)H * W * C;
+}
+static inline bool keep_drops(float keep) { return keep > 0.f && keep < 1.f; }
+// ext asks for a dropout that drops something: one keep in (0,1), or a range with one
+static inline bool ext_wants_drop(const ctgan_epilogue_ext* ext) {
+    if (!ext) return false;
+    if (ext->n_ranges > 0) {
+        for (int i = 0; i < ext->n_ranges && i < CTGAN_DROP_RANGES; ++i)
+            if (keep_drops(ext->range_keep[i])) return true;
+        return false;
+    }
+    return keep_drops(ext->drop_keep);
+}
+// Fills the drop* fields of a kernel parameter struct: everything off unless `on`, then the seed / counter and either the one keep /
+// stream or, with n_ranges > 0, per range its end (first row past it, written to `ends` - the struct's drop_mend with rows_per_sample =
+// pixels per sample, or its drop_nend with rows_per_sample = 1), keep (outside (0,1) = 1: none), stream and the offset of its first
+// element (sample_elems = elements of one sample of the dense result).  Validation - range count, boundaries, layout - is the caller's.
+template <class P>
+static void set_drop(P& p, int (&ends)[CTGAN_DROP_RANGES], const ctgan_epilogue_ext* ext, bool on, long long rows_per_sample, long long sample_elems) {
+    p.drop = 0; p.drop_keep = 1.f; p.drop_seed = 0; p.drop_sid = 0; p.drop_ctr = nullptr; p.drop_nr = 0;
+    for (int i = 0; i < CTGAN_DROP_RANGES; ++i) { ends[i] = 0x7fffffff; p.drop_rkeep[i] = 1.f; p.drop_rsid[i] = 0; p.drop_roff[i] = 0; }
+    if (!on) return;
+    p.drop = 1; p.drop_seed = ext->drop_seed;
+    p.drop_ctr = reinterpret_cast<const unsigned long long*>(ext->drop_ctr);
+    if (ext->n_ranges > 0) {
+        p.drop_nr = ext->n_ranges < CTGAN_DROP_RANGES ? ext->n_ranges : CTGAN_DROP_RANGES;
+        long long start = 0;
+        for (int i = 0; i < p.drop_nr; ++i) {
+            ends[i] = (int)(ext->range_end[i] * rows_per_sample);
+            p.drop_rkeep[i] = keep_drops(ext->range_keep[i]) ? ext->range_keep[i] : 1.f;
+            p.drop_rsid[i] = (unsigned)ext->range_stream_id[i];
+            p.drop_roff[i] = start * sample_elems;
+            start = ext->range_end[i];
+        }
+    } else if (keep_drops(ext->drop_keep)) {
+        p.drop_keep = ext->drop_keep; p.drop_sid = (unsigned)ext->drop_stream_id;
+    }
+}
+
 // bn.hip, for bn_act.hip: the chunk plan of the partial reductions (part[(sample*hc + chunk)][2][c], `pos` positions per chunk) and the
 // finalisation of the backward's sums (no labels): part -> gscale, goffset [c] and s12 [groups][2][c] = mean(g scale), mean(g scale xhat)
 void ctgan_bn_plan(int n, int hw, int* hc, int* pos);

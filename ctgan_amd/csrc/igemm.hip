@@ -1655,43 +1655,7 @@ size_t ctgan_conv2d_workspace_bytes(const ctgan_conv_desc* d, int op) {
 }
 
 int ctgan_conv2d_fwd(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias, const float* resid,
-                     float* y, int flags, ctgan_stream_t stream) {
-    return ctgan_conv2d_fwd_ex(d, x, w, bias, resid, y, flags, nullptr, stream);
-}
-
-static bool ext_wants_drop(const ctgan_epilogue_ext* ext) {
-    if (!ext) return false;
-    if (ext->n_ranges > 0) {
-        for (int i = 0; i < ext->n_ranges && i < CTGAN_DROP_RANGES; ++i)
-            if (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f) return true;
-        return false;
-    }
-    return ext->drop_keep > 0.f && ext->drop_keep < 1.f;
-}
-// rows_per_sample = output pixels per sample (P*Q), sample_elems = elements of one sample of the (dense) output
-static void set_drop(FwdParams& p, const ctgan_epilogue_ext* ext, int rows_per_sample = 0, long long sample_elems = 0) {
-    p.drop = 0; p.drop_keep = 1.f; p.drop_seed = 0; p.drop_sid = 0; p.drop_ctr = nullptr; p.drop_nr = 0;
-    for (int i = 0; i < CTGAN_DROP_RANGES; ++i) { p.drop_mend[i] = 0x7fffffff; p.drop_rkeep[i] = 1.f; p.drop_rsid[i] = 0; p.drop_roff[i] = 0; }
-    if (!ext_wants_drop(ext)) return;
-    p.drop = 1; p.drop_seed = ext->drop_seed;
-    p.drop_ctr = reinterpret_cast<const unsigned long long*>(ext->drop_ctr);
-    if (ext->n_ranges > 0) {
-        p.drop_nr = ext->n_ranges < CTGAN_DROP_RANGES ? ext->n_ranges : CTGAN_DROP_RANGES;
-        long long start = 0;
-        for (int i = 0; i < p.drop_nr; ++i) {
-            p.drop_mend[i] = (int)(ext->range_end[i] * rows_per_sample);
-            p.drop_rkeep[i] = (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f) ? ext->range_keep[i] : 1.f;
-            p.drop_rsid[i] = (unsigned)ext->range_stream_id[i];
-            p.drop_roff[i] = start * sample_elems;
-            start = ext->range_end[i];
-        }
-    } else {
-        p.drop_keep = ext->drop_keep; p.drop_sid = (unsigned)ext->drop_stream_id;
-    }
-}
-
-int ctgan_conv2d_fwd_ex(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias, const float* resid,
-                        float* y, int flags, const ctgan_epilogue_ext* ext, ctgan_stream_t stream) {
+                     float* y, int flags, const ctgan_epilogue_ext* ext, ctgan_stream_t stream) {
     int rc = check_desc(d, "conv2d_fwd");
     const bool want_drop = ext_wants_drop(ext);
     if (rc) return rc;
@@ -1735,7 +1699,7 @@ int ctgan_conv2d_fwd_ex(const ctgan_conv_desc* d, const float* x, const float* w
         for (int i = 0; i + 1 < ext->n_ranges; ++i)
             if (((long long)ext->range_end[i] * d->P * d->Q) % 128)      // a range boundary inside an M tile: caller drops per range
                 return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d_fwd: dropout row ranges must start at multiples of 128 output pixels");
-    set_drop(p, ext, d->P * d->Q, (long long)d->P * d->Q * d->K);
+    set_drop(p, p.drop_mend, ext, want_drop, d->P * d->Q, (long long)d->P * d->Q * d->K);
     return run_fwd(p, static_cast<hipStream_t>(stream));
 }
 
@@ -1753,13 +1717,8 @@ int ctgan_conv2d_repack_filter(const ctgan_conv_desc* d, const float* w, float* 
 }
 
 int ctgan_conv2d_dgrad(const ctgan_conv_desc* d, const float* dy, const float* w, const float* bias, const float* mask,
-                       const float* resid, float* dx, void* ws, size_t ws_bytes, int flags, ctgan_stream_t stream) {
-    return ctgan_conv2d_dgrad_ex(d, dy, w, bias, mask, resid, dx, ws, ws_bytes, flags, nullptr, stream);
-}
-
-int ctgan_conv2d_dgrad_ex(const ctgan_conv_desc* d, const float* dy, const float* w, const float* bias, const float* mask,
-                          const float* resid, float* dx, void* ws, size_t ws_bytes, int flags, const ctgan_epilogue_ext* ext,
-                          ctgan_stream_t stream) {
+                       const float* resid, float* dx, void* ws, size_t ws_bytes, int flags, const ctgan_epilogue_ext* ext,
+                       ctgan_stream_t stream) {
     int rc = check_desc(d, "conv2d_dgrad");
     const bool want_drop = ext_wants_drop(ext);
     if (rc) return rc;
@@ -1790,14 +1749,13 @@ int ctgan_conv2d_dgrad_ex(const ctgan_conv_desc* d, const float* dy, const float
     // Row ranges (round 5: the merged backward of a critic step carries the main rows and the gradient-penalty rows in ONE data gradient,
     // each range with the mask of its own forward dropout): stride-1 form on a dense channels-last dx, boundaries on 128-pixel tiles.
     if (ext && ext->n_ranges > 0) {
-        if (ext->n_ranges > CTGAN_DROP_RANGES || d->stride != 1 || d->xs[1] != 1 || d->xs[3] != d->C || d->xs[2] != (long long)d->W * d->C ||
-            d->xs[0] != (long long)d->H * d->W * d->C)
+        if (ext->n_ranges > CTGAN_DROP_RANGES || d->stride != 1 || !dense_channels_last(d->xs, d->C, d->H, d->W))
             return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d_dgrad: dropout row ranges need stride 1, a dense channels-last dx and <= %d ranges", CTGAN_DROP_RANGES);
         for (int i = 0; i + 1 < ext->n_ranges; ++i)
             if (((long long)ext->range_end[i] * d->H * d->W) % 128)
                 return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d_dgrad: dropout row ranges must start at multiples of 128 pixels");
     }
-    set_drop(p, ext, d->H * d->W, (long long)d->H * d->W * d->C);
+    set_drop(p, p.drop_mend, ext, want_drop, d->H * d->W, (long long)d->H * d->W * d->C);
     const size_t need = dgrad_filter_elems(d) * sizeof(float);
     const bool pre = (flags & CTGAN_DGRAD_W_REPACKED) != 0;
     const bool repack = !pre && ws && ws_bytes >= need && (d->C % 4 == 0) && (d->K % 32 == 0);
@@ -2073,12 +2031,8 @@ extern "C" int ctgan_conv2d_wgrad_group_tile(const ctgan_wgrad_group* G) {
     return -1;
 }
 
-extern "C" int ctgan_conv2d_wgrad_group(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
-    return ctgan_conv2d_wgrad_group_ex(groups, n, ws, ws_bytes, CTGAN_WGRAD_GROUP_GEMM | CTGAN_WGRAD_GROUP_REDUCE, stream);
-}
-
-extern "C" int ctgan_conv2d_wgrad_group_ex(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes, int phases,
-                                           ctgan_stream_t stream) {
+extern "C" int ctgan_conv2d_wgrad_group(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes, int phases,
+                                          ctgan_stream_t stream) {
     if (!groups || n < 1 || n > CTGAN_WGRAD_GROUP_LIMIT) return ctgan_fail(CTGAN_E_BADARG, "conv2d_wgrad_group: bad argument");
     static thread_local MultiPlan M[CTGAN_WGRAD_GROUP_LIMIT];
     static thread_local WgradParams PT[CTGAN_WGRAD_GROUP_LIMIT];

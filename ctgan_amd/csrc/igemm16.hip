@@ -2400,7 +2400,7 @@ int ctgan_conv2d16_x3_prefers(const ctgan_conv_desc* d, int op) {
 }
 
 int ctgan_conv2d16_bn_in_takes(const ctgan_conv_desc* d) {
-    // the checks of conv2d16_fwd_impl and launch_conv16x3h for a forward launch with ctgan_epilogue_ext::in_bn_*, without the operands
+    // the checks of ctgan_conv2d16_fwd and launch_conv16x3h for a forward launch with ctgan_epilogue_ext::in_bn_*, without the operands
     if (!d || d->stride != 1 || !shape_ok_fwd(d) || !extents_ok(d, CTGAN_CONV_FWD, CTGAN_MMA_F32X3) || !frag_image_shape(d, CTGAN_CONV_FWD)) return 0;
     P16 p{};
     p.nph = 1; p.stride = d->stride;
@@ -2527,28 +2527,16 @@ static int conv16_set_act(P16& p, const ctgan_epilogue_ext* ext, int mma, bool d
         return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: fused LeakyReLU + dropout needs a 16-bit mode and a dense channels-last result", who);
     if (ext->n_ranges < 0 || ext->n_ranges > CTGAN_DROP_RANGES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d sample ranges", who, CTGAN_DROP_RANGES);
     if (ext->act_ref && (reinterpret_cast<uintptr_t>(ext->act_ref) & 15)) return ctgan_fail(CTGAN_E_BADARG, "%s: act_ref must be 16-byte aligned", who);
+    for (int i = 0, start = 0; i < ext->n_ranges; start = ext->range_end[i++])
+        if (ext->range_end[i] < start) return ctgan_fail(CTGAN_E_BADARG, "%s: sample ranges must ascend", who);
     p.act = 1; p.act_alpha = ext->act_alpha; p.act_ref = ext->act_ref;
-    p.drop_seed = ext->drop_seed; p.drop_ctr = reinterpret_cast<const unsigned long long*>(ext->drop_ctr);
-    p.drop_keep = 1.f; p.drop_sid = 0; p.drop_nr = ext->n_ranges;
-    for (int i = 0; i < CTGAN_DROP_RANGES; ++i) { p.drop_nend[i] = 0x7fffffff; p.drop_rkeep[i] = 1.f; p.drop_rsid[i] = 0; p.drop_roff[i] = 0; }
-    if (ext->n_ranges > 0) {
-        long long start = 0;
-        for (int i = 0; i < ext->n_ranges; ++i) {
-            if (ext->range_end[i] < start) return ctgan_fail(CTGAN_E_BADARG, "%s: sample ranges must ascend", who);
-            p.drop_nend[i] = ext->range_end[i];
-            p.drop_rkeep[i] = (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f) ? ext->range_keep[i] : 1.f;
-            p.drop_rsid[i] = (unsigned)ext->range_stream_id[i];
-            p.drop_roff[i] = start * sample_elems;
-            start = ext->range_end[i];
-        }
-    } else if (ext->drop_keep > 0.f && ext->drop_keep < 1.f) {
-        p.drop_keep = ext->drop_keep; p.drop_sid = (unsigned)ext->drop_stream_id;
-    }
+    set_drop(p, p.drop_nend, ext, true, 1, sample_elems);   // ranges in samples, any boundary
+    p.drop = 0;                                              // (the pair is keyed on act; drop selects the halo-patch kernels' epilogue)
     return CTGAN_OK;
 }
 
-static int conv2d16_fwd_impl(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
-                             float* y, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
+int ctgan_conv2d16_fwd(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
+                       float* y, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
     if (!d || !x || !wp || !y || !mma_ok(mma)) return ctgan_fail(CTGAN_E_BADARG, "conv2d16_fwd: bad argument");
     if (!shape_ok_fwd(d)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd: shape outside the 16-bit family");
     if (ext && ext->out_tanh) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd_ex: the tanh epilogue exists in the many -> few pixel kernel only");
@@ -2581,8 +2569,8 @@ static int conv2d16_fwd_impl(const ctgan_conv_desc* d, int mma, const float* x, 
         p.bn_labels = ext->in_bn_labels; p.bn_per = d->N / ext->in_bn_groups;
         return launch_conv16x3h(p, st);
     }
+    const bool dense = dense_channels_last(d->ys, d->K, d->P, d->Q);
     if (ext && ext->act) {                                   // the LeakyReLU + dropout pair in the slice kernels' epilogue
-        const bool dense = d->ys[1] == 1 && d->ys[3] == d->K && d->ys[2] == (int64_t)d->Q * d->K && d->ys[0] == (int64_t)d->P * d->Q * d->K;
         if (resid || p.resid_up) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd_ex: fused LeakyReLU + dropout with a residual");
         if (const int rc = conv16_set_act(p, ext, mma, dense, (long long)d->P * d->Q * d->K, "conv2d16_fwd_ex")) return rc;
         return run_conv16(mma, p, st);
@@ -2590,27 +2578,12 @@ static int conv2d16_fwd_impl(const ctgan_conv_desc* d, int mma, const float* x, 
     const bool ranged = ext && ext->n_ranges > 0;
     const bool want_drop = ext && (ranged || (ext->drop_keep > 0.f && ext->drop_keep < 1.f));
     if (want_drop) {                                         // only the halo-patch kernel has the dropout epilogue
-        const bool dense = d->ys[1] == 1 && d->ys[3] == d->K && d->ys[2] == (int64_t)d->Q * d->K && d->ys[0] == (int64_t)d->P * d->Q * d->K;
         if (mma != CTGAN_MMA_F32X3 || !halo_takes(p) || (ranged && (!dense || ext->n_ranges > CTGAN_DROP_RANGES)))
             return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd_ex: epilogue dropout outside the halo-patch form");
-        p.drop = 1; p.drop_keep = 1.f; p.drop_seed = ext->drop_seed; p.drop_sid = 0;
-        p.drop_ctr = reinterpret_cast<const unsigned long long*>(ext->drop_ctr);
-        for (int i = 0; i < CTGAN_DROP_RANGES; ++i) { p.drop_mend[i] = 0x7fffffff; p.drop_rkeep[i] = 1.f; p.drop_rsid[i] = 0; p.drop_roff[i] = 0; }
-        if (ranged) {
-            p.drop_nr = ext->n_ranges;
-            long long start = 0;
-            for (int i = 0; i < p.drop_nr; ++i) {
-                if (((long long)ext->range_end[i] * d->P * d->Q) % 128)
-                    return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd_ex: dropout row ranges must start at multiples of 128 output pixels");
-                p.drop_mend[i] = (int)((long long)ext->range_end[i] * d->P * d->Q);
-                p.drop_rkeep[i] = (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f) ? ext->range_keep[i] : 1.f;
-                p.drop_rsid[i] = (unsigned)ext->range_stream_id[i];
-                p.drop_roff[i] = start * (long long)d->P * d->Q * d->K;
-                start = ext->range_end[i];
-            }
-        } else {
-            p.drop_keep = ext->drop_keep; p.drop_sid = (unsigned)ext->drop_stream_id;
-        }
+        for (int i = 0; i < ext->n_ranges; ++i)              // (every range, the last included)
+            if (((long long)ext->range_end[i] * d->P * d->Q) % 128)
+                return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_fwd_ex: dropout row ranges must start at multiples of 128 output pixels");
+        set_drop(p, p.drop_mend, ext, true, (long long)d->P * d->Q, (long long)d->P * d->Q * d->K);
         return launch_conv16x3h(p, st);
     }
     if (p.resid_up) {                                        // only the halo-patch kernel reads the residual through the upsample
@@ -2621,23 +2594,9 @@ static int conv2d16_fwd_impl(const ctgan_conv_desc* d, int mma, const float* x, 
     return run_conv16(mma, p, st);
 }
 
-int ctgan_conv2d16_fwd(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
-                       float* y, int flags, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
-    return conv2d16_fwd_impl(d, mma, x, wp, bias, resid, y, flags, nullptr, ws, ws_bytes, stream);
-}
-int ctgan_conv2d16_fwd_ex(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
-                          float* y, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
-    return conv2d16_fwd_impl(d, mma, x, wp, bias, resid, y, flags, ext, ws, ws_bytes, stream);
-}
-
 int ctgan_conv2d16_dgrad(const ctgan_conv_desc* d, int mma, const float* dy, const void* wp, const float* bias, const float* mask,
-                         const float* resid, float* dx, int flags, void* ws, size_t ws_bytes, ctgan_stream_t stream) {
-    return ctgan_conv2d16_dgrad_ex(d, mma, dy, wp, bias, mask, resid, dx, flags, nullptr, ws, ws_bytes, stream);
-}
-
-int ctgan_conv2d16_dgrad_ex(const ctgan_conv_desc* d, int mma, const float* dy, const void* wp, const float* bias, const float* mask,
-                            const float* resid, float* dx, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes,
-                            ctgan_stream_t stream) {
+                         const float* resid, float* dx, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes,
+                         ctgan_stream_t stream) {
     if (!d || !dy || !wp || !dx || !mma_ok(mma)) return ctgan_fail(CTGAN_E_BADARG, "conv2d16_dgrad: bad argument");
     if (!shape_ok_dgrad(d)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad: shape outside the 16-bit family");
     const long long y_extent = (long long)(d->N - 1) * d->ys[0] + (long long)(d->P - 1) * d->ys[2] + (long long)(d->Q - 1) * d->ys[3] + d->K;
@@ -2669,41 +2628,23 @@ int ctgan_conv2d16_dgrad_ex(const ctgan_conv_desc* d, int mma, const float* dy, 
     }
     p.M = d->N * p.P * p.Q;
     hipStream_t st = (hipStream_t)stream;
+    const bool dense = dense_channels_last(d->xs, d->C, d->H, d->W);
     if (ext && ext->act) {                                   // the pair's backward (act_ref = the forward result) in the slice kernels' epilogue
-        const bool dense = d->xs[1] == 1 && d->xs[3] == d->C && d->xs[2] == (int64_t)d->W * d->C && d->xs[0] == (int64_t)d->H * d->W * d->C;
         if (const int rc = conv16_set_act(p, ext, mma, dense, (long long)d->H * d->W * d->C, "conv2d16_dgrad_ex")) return rc;
         return run_conv16(mma, p, st);
     }
-    const bool ranged = ext && ext->n_ranges > 0;
-    bool range_drop = false;
-    if (ranged)
-        for (int i = 0; i < ext->n_ranges && i < CTGAN_DROP_RANGES; ++i) range_drop = range_drop || (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f);
-    if (range_drop || (ext && !ranged && ext->drop_keep > 0.f && ext->drop_keep < 1.f)) {
+    if (ext_wants_drop(ext)) {
         // the data gradient multiplied by a dropout mask (the mask of the dropout whose result the forward conv consumed), as
-        // ctgan_conv2d_dgrad_ex: only the halo-patch kernels have the dropout epilogue, on a dense channels-last dx
-        const bool dense = d->xs[1] == 1 && d->xs[3] == d->C && d->xs[2] == (int64_t)d->W * d->C && d->xs[0] == (int64_t)d->H * d->W * d->C;
+        // ctgan_conv2d_dgrad: only the halo-patch kernels have the dropout epilogue, on a dense channels-last dx
         if (mma != CTGAN_MMA_F32X3 || g.nph != 1 || !dense || !halo_takes(p))
             return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad_ex: epilogue dropout outside the halo-patch form");
-        p.drop = 1; p.drop_keep = ranged ? 1.f : ext->drop_keep; p.drop_seed = ext->drop_seed; p.drop_sid = ranged ? 0u : (unsigned)ext->drop_stream_id;
-        p.drop_ctr = reinterpret_cast<const unsigned long long*>(ext->drop_ctr);
-        p.drop_nr = 0;
-        for (int i = 0; i < CTGAN_DROP_RANGES; ++i) { p.drop_mend[i] = 0x7fffffff; p.drop_rkeep[i] = 1.f; p.drop_rsid[i] = 0; p.drop_roff[i] = 0; }
-        if (ranged) {
-            // sample ranges of dx, each with the mask of its own forward dropout (the merged backward of a critic step, round 5): as in the
-            // forward, boundaries on 128-pixel tiles, Philox indices relative to the range's first element
-            if (ext->n_ranges > CTGAN_DROP_RANGES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad_ex: more than %d sample ranges", CTGAN_DROP_RANGES);
-            p.drop_nr = ext->n_ranges;
-            long long start = 0;
-            for (int i = 0; i < p.drop_nr; ++i) {
-                if (i + 1 < p.drop_nr && ((long long)ext->range_end[i] * d->H * d->W) % 128)
-                    return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad_ex: dropout row ranges must start at multiples of 128 pixels");
-                p.drop_mend[i] = (int)((long long)ext->range_end[i] * d->H * d->W);
-                p.drop_rkeep[i] = (ext->range_keep[i] > 0.f && ext->range_keep[i] < 1.f) ? ext->range_keep[i] : 1.f;
-                p.drop_rsid[i] = (unsigned)ext->range_stream_id[i];
-                p.drop_roff[i] = start * (long long)d->H * d->W * d->C;
-                start = ext->range_end[i];
-            }
-        }
+        // sample ranges of dx, each with the mask of its own forward dropout (the merged backward of a critic step, round 5): as in the
+        // forward, boundaries on 128-pixel tiles (the last range's end is free), Philox indices relative to the range's first element
+        if (ext->n_ranges > CTGAN_DROP_RANGES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad_ex: more than %d sample ranges", CTGAN_DROP_RANGES);
+        for (int i = 0; i + 1 < ext->n_ranges; ++i)
+            if (((long long)ext->range_end[i] * d->H * d->W) % 128)
+                return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_dgrad_ex: dropout row ranges must start at multiples of 128 pixels");
+        set_drop(p, p.drop_mend, ext, true, (long long)d->H * d->W, (long long)d->H * d->W * d->C);
         return launch_conv16x3h(p, st);
     }
     return run_conv16(mma, p, st);
@@ -2730,13 +2671,8 @@ size_t ctgan_conv2d16_wgrad_workspace_bytes(const ctgan_conv_desc* d, int mma) {
     return (size_t)w.splits * ((size_t)d->R * d->S * d->C + 1) * d->K * sizeof(float);
 }
 
-int ctgan_conv2d16_wgrad(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes,
-                         int flags, ctgan_stream_t stream) {
-    return ctgan_conv2d16_wgrad_bias(d, mma, x, dy, dw, nullptr, ws, ws_bytes, flags, stream);
-}
-
-int ctgan_conv2d16_wgrad_bias(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, float* db, void* ws,
-                              size_t ws_bytes, int flags, ctgan_stream_t stream) {
+int ctgan_conv2d16_wgrad(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, float* db, void* ws,
+                         size_t ws_bytes, int flags, ctgan_stream_t stream) {
     if (!d || !x || !dy || !dw || !mma_ok(mma)) return ctgan_fail(CTGAN_E_BADARG, "conv2d16_wgrad: bad argument");
     if (db && (d->K % 4 || (reinterpret_cast<uintptr_t>(db) & 15)))
         return ctgan_fail(CTGAN_E_UNSUPPORTED, "conv2d16_wgrad: the fused bias gradient needs K %% 4 == 0 and a 16-byte aligned db");

@@ -732,7 +732,7 @@ int ctgan_gp_fwd(const float* g, int32_t b, int32_t d, float lambda, float* slop
     hipStream_t st = static_cast<hipStream_t>(s);
     hipLaunchKernelGGL(gp_slopes_kernel, dim3(b), dim3(256), 0, st, g, d, slopes);
     int rc = ctgan_check_launch("gp_slopes");
-    if (rc || !gp) return rc;                        // gp == NULL: the mean is taken by ctgan_tail_critic_heads_fwd2 (from slopes)
+    if (rc || !gp) return rc;                        // gp == NULL: the mean is taken by ctgan_tail_critic_heads_fwd (from slopes)
     hipLaunchKernelGGL(gp_mean_kernel, dim3(1), dim3(256), 0, st, slopes, b, lambda, gp);
     return ctgan_check_launch("gp_mean");
 }
@@ -820,17 +820,10 @@ int ctgan_tail_heads_fwd(const float* y, int32_t n, int32_t hw, int32_t nf, int3
     return ctgan_check_launch("tail_heads_rows");
 }
 int ctgan_tail_critic_heads_fwd(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
-                                const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, const float* gp,
-                                float lambda2, float M, float acgan_scale, float* f, float* d, float* a, float* ct_i, float* probs,
-                                float* ce_i, float* out, ctgan_stream_t s) {
-    return ctgan_tail_critic_heads_fwd2(y, B, hw, nf, w_out, b_out, w_ac, b_ac, ncls, labels, const_cast<float*>(gp), nullptr, 0.f, nullptr, 0,
-                                        nullptr, nullptr, nullptr, lambda2, M, acgan_scale, f, d, a, ct_i, probs, ce_i, out, s);
-}
-int ctgan_tail_critic_heads_fwd2(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
-                                 const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float* gp,
-                                 const float* slopes, float gp_lambda, const float* y_clean, int32_t clean_relu, float* f_clean,
-                                 float* a_clean, float* acc, float lambda2, float M, float acgan_scale, float* f, float* d, float* a,
-                                 float* ct_i, float* probs, float* ce_i, float* out, ctgan_stream_t s) {
+                                const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float* gp,
+                                const float* slopes, float gp_lambda, const float* y_clean, int32_t clean_relu, float* f_clean,
+                                float* a_clean, float* acc, float lambda2, float M, float acgan_scale, float* f, float* d, float* a,
+                                float* ct_i, float* probs, float* ce_i, float* out, ctgan_stream_t s) {
     if (!y || !f || !d || !w_out || !ct_i || !out || B <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 ||
         (w_ac && (!a || !labels || !probs || !ce_i || ncls <= 0)) || (reinterpret_cast<uintptr_t>(y) & 15))
         return ctgan_fail(CTGAN_E_BADARG, "tail_critic_heads_fwd: bad argument");
@@ -847,10 +840,10 @@ int ctgan_tail_critic_heads_fwd2(const float* y, int32_t B, int32_t hw, int32_t 
                        acgan_scale, out, slopes, gp_lambda, y_clean ? a_clean : (const float*)nullptr, labels, ncls, acc);
     return ctgan_check_launch("critic_heads_final");
 }
-int ctgan_tail_heads_bwd_gp(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* ct_i,
-                            const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf, int32_t ncls, float lambda2, float M,
-                            float acgan_scale, float mask_scale, const float* w_out, const float* w_ac, float* gy, float* gw_out,
-                            float* gb_out, float* gw_ac, float* gb_ac, const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t s) {
+int ctgan_tail_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* ct_i,
+                         const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf, int32_t ncls, float lambda2, float M,
+                         float acgan_scale, float mask_scale, const float* w_out, const float* w_ac, float* gy, float* gw_out,
+                         float* gb_out, float* gw_ac, float* gb_ac, const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t s) {
     if (!y || !d || !f || !ct_i || !gout || (n_gout != 1 && n_gout != 4) || !w_out || !gy || !gw_out || !gb_out || B <= 0 || hw <= 0 ||
         nf <= 0 || (nf & 3) || (w_ac && (!probs || !labels || !gw_ac || !gb_ac || ncls <= 0)) || n_gp < 0 || (n_gp > 0 && (!y_gp || !gz_gp)))
         return ctgan_fail(CTGAN_E_BADARG, "tail_heads_bwd: bad argument");
@@ -864,13 +857,6 @@ int ctgan_tail_heads_bwd_gp(const float* y, const float* d, const float* f, cons
                        gout, n_gout, B, hw, nf, ncls, lambda2, M, acgan_scale, mask_scale, w_out, w_ac, gy, gw_out, gb_out, gw_ac, gb_ac,
                        y_gp, n_gp, gz_gp);
     return ctgan_check_launch("tail_heads_bwd");
-}
-int ctgan_tail_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* ct_i,
-                         const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf, int32_t ncls, float lambda2, float M,
-                         float acgan_scale, float mask_scale, const float* w_out, const float* w_ac, float* gy, float* gw_out,
-                         float* gb_out, float* gw_ac, float* gb_ac, ctgan_stream_t s) {
-    return ctgan_tail_heads_bwd_gp(y, d, f, probs, labels, ct_i, gout, n_gout, B, hw, nf, ncls, lambda2, M, acgan_scale, mask_scale, w_out, w_ac, gy,
-                                   gw_out, gb_out, gw_ac, gb_ac, nullptr, 0, nullptr, s);
 }
 int ctgan_gen_heads_fwd(const float* y, int32_t n, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* w_ac,
                         const float* b_ac, int32_t ncls, const int32_t* labels, float ac_scale, float* f, float* d, float* a, float* probs,
@@ -910,7 +896,7 @@ int ctgan_gp_head_grad(const float* y, const float* w_out, int32_t n, int32_t hw
     return ctgan_check_launch("gp_head_grad");
 }
 int ctgan_gp_head_wgrad(const float* gg, const float* y, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gw, float* ws,
-                        ctgan_stream_t s) {
+                        int accumulate, ctgan_stream_t s) {
     const int c4n = nf >> 2;
     if (!gg || !y || !gw || !ws || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || c4n > 256 || (256 % c4n))
         return ctgan_fail(CTGAN_E_BADARG, "gp_head_wgrad: bad argument");
@@ -920,21 +906,7 @@ int ctgan_gp_head_wgrad(const float* gg, const float* y, int32_t n, int32_t hw, 
     hipLaunchKernelGGL(gp_head_wgrad_stage1_kernel, dim3(GPW_SLICES), dim3(256), 0, st, gg, y, (long long)n * hw, nf, ws);
     int rc = ctgan_check_launch("gp_head_wgrad_stage1");
     if (rc) return rc;
-    hipLaunchKernelGGL(gp_head_wgrad_stage2_kernel, dim3((nf + 255) / 256), dim3(256), 0, st, ws, nf, mask_scale / (float)hw, gw, 0);
-    return ctgan_check_launch("gp_head_wgrad_stage2");
-}
-int ctgan_gp_head_wgrad_acc(const float* gg, const float* y, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gw, float* ws,
-                            ctgan_stream_t s) {
-    const int c4n = nf >> 2;
-    if (!gg || !y || !gw || !ws || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || c4n > 256 || (256 % c4n))
-        return ctgan_fail(CTGAN_E_BADARG, "gp_head_wgrad_acc: bad argument");
-    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gg) | reinterpret_cast<uintptr_t>(ws)) & 15)
-        return ctgan_fail(CTGAN_E_BADARG, "gp_head_wgrad_acc: unaligned");
-    hipStream_t st = static_cast<hipStream_t>(s);
-    hipLaunchKernelGGL(gp_head_wgrad_stage1_kernel, dim3(GPW_SLICES), dim3(256), 0, st, gg, y, (long long)n * hw, nf, ws);
-    int rc = ctgan_check_launch("gp_head_wgrad_stage1");
-    if (rc) return rc;
-    hipLaunchKernelGGL(gp_head_wgrad_stage2_kernel, dim3((nf + 255) / 256), dim3(256), 0, st, ws, nf, mask_scale / (float)hw, gw, 1);
+    hipLaunchKernelGGL(gp_head_wgrad_stage2_kernel, dim3((nf + 255) / 256), dim3(256), 0, st, ws, nf, mask_scale / (float)hw, gw, accumulate ? 1 : 0);
     return ctgan_check_launch("gp_head_wgrad_stage2");
 }
 int ctgan_gp_finish(float* ga, const float* gs, const int64_t* gs_strides, int32_t b, int32_t c, int32_t h, int32_t w, float scale, float* slopes,

@@ -361,22 +361,51 @@ def _x_phys_shape(g, N):
     return (N, g.C, g.H // 2, g.W // 2) if g.x_up else (N, g.C, g.H, g.W)
 
 
-def _ext(drop, out_mask=None):
-    """drop = (keep, seed, stream_id, ctr) -> ctgan_epilogue_ext*, or None.  Ranged form (forward launches shared by several
-    passes): {'ranges': [(end_sample, spec or None), ...]} - consecutive sample ranges with their own dropout.
-    out_mask (forward convs): tensor with the result's strides, the result is kept where it is > 0."""
-    e = _ext_struct(drop, out_mask)
-    return None if e is None else ctypes.byref(e)
-
-
-def _act_ext(act):
-    """act = {'alpha': a, 'drop': spec or ranged dict, 'ref': tensor or None} -> ctgan_epilogue_ext* with the fused LeakyReLU + dropout
-    pair switched on (csrc/igemm16.hip conv16_act)."""
-    e = _ext_struct(act['drop'])
-    e.act, e.act_alpha = 1, float(act['alpha'])
-    ref = act.get('ref')
-    e.act_ref = ref.data_ptr() if ref is not None else None
-    return ctypes.byref(e)
+def _epilogue_ext(drop=None, out_mask=None, act=None, bn_in=None, tanh=False):
+    """struct ctgan_epilogue_ext for one conv launch, or None when nothing is set (the launch then gets ext = NULL).
+    drop = (keep, seed, stream_id, ctr): dropout of the result.  Ranged form (forward launches shared by several passes):
+    {'ranges': [(end_sample, spec or None), ...]} - consecutive sample ranges with their own dropout.
+    out_mask (forward convs): tensor with the result's strides, the result is kept where it is > 0.
+    act = {'alpha': a, 'drop': spec or ranged dict, 'ref': tensor or None}: the fused LeakyReLU + dropout pair (csrc/igemm16.hip conv16_act).
+    bn_in = (mean, rstd, scale, offset, groups, labels or None): batch norm of the input on load; tanh: tanh of the result."""
+    if act is not None:
+        assert drop is None
+        drop = act['drop']
+    if drop is None and out_mask is None and bn_in is None and not tanh:
+        return None
+    from ._lib import EpilogueExt
+    if drop is None:
+        e = EpilogueExt(0.0, 0, 0, None)               # keep outside (0,1): no dropout
+    elif isinstance(drop, dict):
+        assert out_mask is None
+        rs = drop['ranges']
+        assert 1 <= len(rs) <= 3
+        spec0 = next(sp for _, sp in rs if sp is not None)
+        e = EpilogueExt(1.0, spec0[1], 0, spec0[3].data_ptr())
+        e.n_ranges = len(rs)
+        for i, (end, sp) in enumerate(rs):
+            assert sp is None or (sp[1] == spec0[1] and sp[3].data_ptr() == spec0[3].data_ptr())
+            e.range_end[i] = int(end)
+            e.range_keep[i] = float(sp[0]) if sp is not None else 1.0
+            e.range_stream_id[i] = int(sp[2]) if sp is not None else 0
+    else:
+        assert out_mask is None
+        keep, seed, sid, ctr = drop
+        assert ctr.is_cuda and ctr.dtype == torch.int64
+        e = EpilogueExt(keep, seed, sid, ctr.data_ptr())
+    if out_mask is not None:
+        e.out_mask = out_mask.data_ptr()
+    if act is not None:
+        e.act, e.act_alpha = 1, float(act['alpha'])
+        ref = act.get('ref')
+        e.act_ref = ref.data_ptr() if ref is not None else None
+    if bn_in is not None:
+        mean, rstd, scale, offset, groups, labels = bn_in
+        e.in_bn_mean, e.in_bn_rstd, e.in_bn_scale, e.in_bn_offset = mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), offset.data_ptr()
+        e.in_bn_groups = int(groups)
+        e.in_bn_labels = labels.data_ptr() if labels is not None else None
+    e.out_tanh = 1 if tanh else 0
+    return e
 
 
 def _act_apply(y, act):
@@ -394,32 +423,6 @@ def _act_apply(y, act):
     return lrelu_dropout_rng2(y, ref, rs[0][0], act['alpha'], a[0], a[1], a[2], b[2], a[3])
 
 
-def _ext_struct(drop, out_mask=None):
-    if drop is None and out_mask is None:
-        return None
-    from ._lib import EpilogueExt
-    if drop is None:
-        e = EpilogueExt(0.0, 0, 0, None)               # keep outside (0,1): no dropout
-        e.out_mask = out_mask.data_ptr()
-        return e
-    assert out_mask is None
-    if isinstance(drop, dict):
-        rs = drop['ranges']
-        assert 1 <= len(rs) <= 3
-        spec0 = next(sp for _, sp in rs if sp is not None)
-        e = EpilogueExt(1.0, spec0[1], 0, spec0[3].data_ptr())
-        e.n_ranges = len(rs)
-        for i, (end, sp) in enumerate(rs):
-            assert sp is None or (sp[1] == spec0[1] and sp[3].data_ptr() == spec0[3].data_ptr())
-            e.range_end[i] = int(end)
-            e.range_keep[i] = float(sp[0]) if sp is not None else 1.0
-            e.range_stream_id[i] = int(sp[2]) if sp is not None else 0
-        return e
-    keep, seed, sid, ctr = drop
-    assert ctr.is_cuda and ctr.dtype == torch.int64
-    return EpilogueExt(keep, seed, sid, ctr.data_ptr())
-
-
 def _dropout_ranges(y, drop):
     """Fallback of the ranged epilogue dropout: one dropout pass per range, on the range's own rows."""
     r0 = 0
@@ -432,6 +435,53 @@ def _dropout_ranges(y, drop):
 
 # A/B switch: the LeakyReLU + dropout pair inside the 16-bit slice kernels' epilogue (default) / as its own launch
 ACT_EPILOGUE = os.environ.get('CTGAN_ACT_EPILOGUE', '1') != '0'
+
+
+def _x3_available():
+    """May the split mode ('f32x3') serve a launch of this configuration: it is the mode, or the fp32 mode's hybrid routing is on."""
+    return MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID)
+
+
+def _x3_prefers(d, op):
+    """... and is it the faster fp32 path for this launch (ctgan_conv2d16_x3_prefers)?"""
+    return _x3_available() and bool(lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), op))
+
+
+def _alloc_out(shape, out_strides, device):
+    """The fp32 result of a conv: logical NCHW `shape`, channels-last unless out_strides is given."""
+    if out_strides is None:
+        return empty_cl(*shape, device)
+    return torch.empty_strided(shape, out_strides, dtype=torch.float32, device=device)
+
+
+def _run_conv(op, family, d, g, N, a, w, out, bias=None, mask=None, resid=None, flags=0, ext=None, wt=None, split_ws=True):
+    """ONE conv launch through the C ABI, inside the PROFILE bracket: op 0 = forward (a = x, out = y), op 1 = data gradient (a = dy, out = dx,
+    mask / resid of its epilogue).  family None: the fp32 family on w (a data gradient: on the repacked filter wt when given, else with the
+    workspace of the per-call repack); a 16-bit mode name: that family on the packed image of w, with the K-split slabs of launches that
+    cannot fill the chip unless split_ws is False.  ext = _epilogue_ext(...) or None.  Returns out; raises what check raises."""
+    e = ctypes.byref(ext) if ext is not None else None
+    dp = ctypes.byref(d)
+    if family is not None:
+        wp = _packed16(w, d, op, g, family)
+        code = _MMA_CODE[family]
+        nb = lib.ctgan_conv2d16_workspace_bytes(dp, op) if split_ws else 0
+        ws = workspace(nb, a.device) if nb else None
+        if op == 0:
+            call = lambda: check(lib.ctgan_conv2d16_fwd(dp, code, _ptr(a), _ptr(wp), _ptr(bias), _ptr(resid), _ptr(out), flags, e, _ptr(ws), nb, _stream()), 'conv2d16_fwd')
+        else:
+            call = lambda: check(lib.ctgan_conv2d16_dgrad(dp, code, _ptr(a), _ptr(wp), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(out), flags, e, _ptr(ws), nb, _stream()), 'conv2d16_dgrad')
+    elif op == 0:
+        call = lambda: check(lib.ctgan_conv2d_fwd(dp, _ptr(a), _ptr(w), _ptr(bias), _ptr(resid), _ptr(out), flags, e, _stream()), 'conv2d_fwd')
+    else:
+        if wt is not None:
+            assert wt.numel() * 4 == lib.ctgan_conv2d_workspace_bytes(dp, 1)
+            filt, ws, nb, flags = wt, None, 0, flags | 1
+        else:
+            ws = workspace(lib.ctgan_conv2d_workspace_bytes(dp, 1), a.device)
+            filt, nb = w, ws.numel()
+        call = lambda: check(lib.ctgan_conv2d_dgrad(dp, _ptr(a), _ptr(filt), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(out), _ptr(ws), nb, flags, e, _stream()), 'conv2d_dgrad')
+    _timed(g, N, call)
+    return out
 
 
 def _conv_act(op, a, w, bias, g, N, relu_in, act, wt=None):
@@ -451,18 +501,9 @@ def _conv_act(op, a, w, bias, g, N, relu_in, act, wt=None):
         assert tuple(ref.shape) == tuple(y.shape) and ref.stride() == y.stride()
     mode = _conv_mode(d, op, ACT_EPILOGUE and MMA_DTYPE in ('bf16', 'f16') and not fewch_handles(g) and not g.x_up)
     if mode is not None:
-        wp = _packed16(w, d, op, g, mode)
-        code = _MMA_CODE[mode]
-        nb = lib.ctgan_conv2d16_workspace_bytes(ctypes.byref(d), op)
-        ws = workspace(nb, a.device) if nb else None
         try:
-            if op == 0:
-                _timed(g, N, lambda: check(lib.ctgan_conv2d16_fwd_ex(ctypes.byref(d), code, _ptr(a), _ptr(wp), _ptr(bias), None, _ptr(y), 2 if relu_in else 0,
-                                                                       _act_ext(act), _ptr(ws), nb, _stream()), 'conv2d16_fwd_ex'))
-            else:
-                _timed(g, N, lambda: check(lib.ctgan_conv2d16_dgrad_ex(ctypes.byref(d), code, _ptr(a), _ptr(wp), None, None, None, _ptr(y), 0,
-                                                                         _act_ext(act), _ptr(ws), nb, _stream()), 'conv2d16_dgrad_ex'))
-            return y
+            return _run_conv(op, mode, d, g, N, a, w, y, bias=bias if op == 0 else None, flags=2 if (op == 0 and relu_in) else 0,
+                             ext=_epilogue_ext(act=act))
         except NotImplementedError:
             pass
     y = conv_fwd(a, w, bias, g, relu_in=relu_in) if op == 0 else conv_dgrad(a, w, g, N, wt=wt)
@@ -485,10 +526,7 @@ def conv_fwd(x, w, bias, g, resid=None, relu=False, out_strides=None, relu_in=Fa
     N = x.shape[0]
     assert tuple(x.shape) == _x_phys_shape(g, N), (tuple(x.shape), _x_phys_shape(g, N))
     assert tuple(w.shape) == (g.R, g.S, g.C, g.K) and w.is_contiguous()
-    if out_strides is None:
-        y = empty_cl(N, g.K, g.P, g.Q, x.device)
-    else:
-        y = torch.empty_strided((N, g.K, g.P, g.Q), out_strides, dtype=torch.float32, device=x.device)
+    y = _alloc_out((N, g.K, g.P, g.Q), out_strides, x.device)
     if resid is not None and resid_up:
         assert tuple(resid.shape) == (N, g.K, g.P // 2, g.Q // 2) and resid.permute(0, 2, 3, 1).is_contiguous()
     elif resid is not None:
@@ -497,40 +535,30 @@ def conv_fwd(x, w, bias, g, resid=None, relu=False, out_strides=None, relu_in=Fa
     fl = (1 if relu else 0) | (2 if relu_in else 0) | (8 if (resid_up and resid is not None) else 0)
     plain = drop is None and not fewch_handles(g)
     mode = _conv_mode(d, 0, plain and not (fl & 8))
-    if (mode is None and (fl & 8) and plain and (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID))
-            and lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0)):
+    if mode is None and (fl & 8) and plain and _x3_prefers(d, 0):
         mode = 'f32x3'                                # the halo-patch kernel reads the residual through the 2x upsample itself
     _x3_log(g, N, d, 0, drop=drop is not None, resid_up=bool(fl & 8), x_up=bool(g.x_up))
-    if (mode is None and drop is not None and not (fl & 8) and g.stride == 1 and not fewch_handles(g)
-            and (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID)) and lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0)):
+    ext = _epilogue_ext(drop=drop)
+    if mode is None and drop is not None and not (fl & 8) and g.stride == 1 and not fewch_handles(g) and _x3_prefers(d, 0):
         # the halo-patch kernel has the fp32 family's dropout epilogue (same Philox draws at the same offsets)
-        wp = _packed16(w, d, 0, g, 'f32x3')
         try:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d16_fwd_ex(ctypes.byref(d), 3, _ptr(x), _ptr(wp), _ptr(bias), _ptr(resid), _ptr(y), fl, _ext(drop), None, 0, _stream()), 'conv2d16_fwd_ex'))
-            return y
+            return _run_conv(0, 'f32x3', d, g, N, x, w, y, bias=bias, resid=resid, flags=fl, ext=ext, split_ws=False)
         except NotImplementedError:
             pass
     if mode is not None:
-        wp = _packed16(w, d, 0, g, mode)
-        code = _MMA_CODE[mode]
-        nb = lib.ctgan_conv2d16_workspace_bytes(ctypes.byref(d), 0)
-        ws = workspace(nb, x.device) if nb else None
-        _timed(g, N, lambda: check(lib.ctgan_conv2d16_fwd(ctypes.byref(d), code, _ptr(x), _ptr(wp), _ptr(bias), _ptr(resid), _ptr(y), fl, _ptr(ws), nb, _stream()), 'conv2d16_fwd'))
-        return y
+        return _run_conv(0, mode, d, g, N, x, w, y, bias=bias, resid=resid, flags=fl)
     if fl & 8:
         try:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d_fwd_ex(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(resid), _ptr(y), fl, _ext(drop), _stream()), 'conv2d_fwd'))
-            return y
+            return _run_conv(0, None, d, g, N, x, w, y, bias=bias, resid=resid, flags=fl, ext=ext)
         except NotImplementedError:          # no vector epilogue: materialise the upsampled residual
             resid = upsample2(resid, 1.0)
             fl &= ~8
     if drop is not None:
         try:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d_fwd_ex(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(resid), _ptr(y), fl, _ext(drop), _stream()), 'conv2d_fwd'))
-            return y
+            return _run_conv(0, None, d, g, N, x, w, y, bias=bias, resid=resid, flags=fl, ext=ext)
         except NotImplementedError:          # no vector epilogue for this call: dropout as its own pass
             pass
-    _timed(g, N, lambda: check(lib.ctgan_conv2d_fwd(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(resid), _ptr(y), fl, _stream()), 'conv2d_fwd'))
+    _run_conv(0, None, d, g, N, x, w, y, bias=bias, resid=resid, flags=fl)
     if drop is None:
         return y
     return _dropout_ranges(y, drop) if isinstance(drop, dict) else dropout_rng(y, *drop)
@@ -540,27 +568,14 @@ def _conv_fwd_masked(x, w, bias, g, out_strides, relu_in, mask):
     """conv_fwd with the out_mask epilogue (ctgan_epilogue_ext.out_mask) on whichever kernel family serves the launch."""
     N = x.shape[0]
     assert tuple(x.shape) == _x_phys_shape(g, N) and tuple(w.shape) == (g.R, g.S, g.C, g.K) and w.is_contiguous()
-    if out_strides is None:
-        y = empty_cl(N, g.K, g.P, g.Q, x.device)
-    else:
-        y = torch.empty_strided((N, g.K, g.P, g.Q), out_strides, dtype=torch.float32, device=x.device)
+    y = _alloc_out((N, g.K, g.P, g.Q), out_strides, x.device)
     if tuple(mask.shape) != tuple(y.shape) or mask.stride() != y.stride():
         return lrelu_bwd(conv_fwd(x, w, bias, g, out_strides=out_strides, relu_in=relu_in), mask, 0.0)
     d = g.desc(N, x.stride(), y.stride())
-    fl = 2 if relu_in else 0
     mode = _conv_mode(d, 0, not fewch_handles(g))
     _x3_log(g, N, d, 0, drop=False, resid_up=False, x_up=bool(g.x_up))
     try:
-        if mode is not None:
-            wp = _packed16(w, d, 0, g, mode)
-            nb = lib.ctgan_conv2d16_workspace_bytes(ctypes.byref(d), 0)
-            ws = workspace(nb, x.device) if nb else None
-            _timed(g, N, lambda: check(lib.ctgan_conv2d16_fwd_ex(ctypes.byref(d), _MMA_CODE[mode], _ptr(x), _ptr(wp), _ptr(bias), None, _ptr(y), fl,
-                                                                 _ext(None, mask), _ptr(ws), nb, _stream()), 'conv2d16_fwd_ex'))
-        else:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d_fwd_ex(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), None, _ptr(y), fl, _ext(None, mask),
-                                                               _stream()), 'conv2d_fwd'))
-        return y
+        return _run_conv(0, mode, d, g, N, x, w, y, bias=bias, flags=2 if relu_in else 0, ext=_epilogue_ext(out_mask=mask))
     except NotImplementedError:
         return lrelu_bwd(conv_fwd(x, w, bias, g, out_strides=out_strides, relu_in=relu_in), mask, 0.0)
 
@@ -611,10 +626,7 @@ def conv_dgrad(gy, w, g, N, out_strides=None, bias=None, wt=None, mask=None, res
         return _conv_act(1, gy, w, None, g, N, False, act, wt=wt)
     assert tuple(gy.shape) == (N, g.K, g.P, g.Q)
     assert tuple(w.shape) == (g.R, g.S, g.C, g.K) and w.is_contiguous()
-    if out_strides is None:
-        dx = empty_cl(N, g.C, g.H, g.W, gy.device)
-    else:
-        dx = torch.empty_strided((N, g.C, g.H, g.W), out_strides, dtype=torch.float32, device=gy.device)
+    dx = _alloc_out((N, g.C, g.H, g.W), out_strides, gy.device)
     d = g.desc(N, dx.stride(), gy.stride())
     if mask is not None:
         mask = match_layout(mask, dx)
@@ -622,36 +634,21 @@ def conv_dgrad(gy, w, g, N, out_strides=None, bias=None, wt=None, mask=None, res
         resid = match_layout(resid, dx)
     mode = _conv_mode(d, 1, drop is None and not fewch_handles(g))
     _x3_log(g, N, d, 1, drop=drop is not None)
-    if (mode is None and drop is not None and g.stride == 1 and not fewch_handles(g)
-            and (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID)) and lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 1)):
+    ext = _epilogue_ext(drop=drop)
+    if mode is None and drop is not None and g.stride == 1 and not fewch_handles(g) and _x3_prefers(d, 1):
         # the halo-patch kernels carry the fp32 family's epilogue dropout (same Philox draws at the same offsets)
-        wp = _packed16(w, d, 1, g, 'f32x3')
         try:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d16_dgrad_ex(ctypes.byref(d), 3, _ptr(gy), _ptr(wp), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(dx), 0,
-                                                                     _ext(drop), None, 0, _stream()), 'conv2d16_dgrad_ex'))
-            return dx
+            return _run_conv(1, 'f32x3', d, g, N, gy, w, dx, bias=bias, mask=mask, resid=resid, ext=ext, split_ws=False)
         except NotImplementedError:
             pass
     if mode is not None:
-        wp = _packed16(w, d, 1, g, mode)
-        code = _MMA_CODE[mode]
-        nb = lib.ctgan_conv2d16_workspace_bytes(ctypes.byref(d), 1)
-        ws = workspace(nb, gy.device) if nb else None
-        _timed(g, N, lambda: check(lib.ctgan_conv2d16_dgrad(ctypes.byref(d), code, _ptr(gy), _ptr(wp), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(dx), 0, _ptr(ws), nb, _stream()), 'conv2d16_dgrad'))
-        return dx
-    if wt is not None:
-        assert wt.numel() * 4 == lib.ctgan_conv2d_workspace_bytes(ctypes.byref(d), 1)
-        filt, ws_p, ws_n, fl = wt, None, 0, 1
-    else:
-        ws = workspace(lib.ctgan_conv2d_workspace_bytes(ctypes.byref(d), 1), gy.device)
-        filt, ws_p, ws_n, fl = w, ws, ws.numel(), 0
+        return _run_conv(1, mode, d, g, N, gy, w, dx, bias=bias, mask=mask, resid=resid)
     if drop is not None:
         try:
-            _timed(g, N, lambda: check(lib.ctgan_conv2d_dgrad_ex(ctypes.byref(d), _ptr(gy), _ptr(filt), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(dx), _ptr(ws_p), ws_n, fl, _ext(drop), _stream()), 'conv2d_dgrad'))
-            return dx
+            return _run_conv(1, None, d, g, N, gy, w, dx, bias=bias, mask=mask, resid=resid, ext=ext, wt=wt)
         except NotImplementedError:
             pass
-    _timed(g, N, lambda: check(lib.ctgan_conv2d_dgrad(ctypes.byref(d), _ptr(gy), _ptr(filt), _ptr(bias), _ptr(mask), _ptr(resid), _ptr(dx), _ptr(ws_p), ws_n, fl, _stream()), 'conv2d_dgrad'))
+    _run_conv(1, None, d, g, N, gy, w, dx, bias=bias, mask=mask, resid=resid, wt=wt)
     if drop is None:
         return dx
     return _dropout_ranges(dx, drop) if isinstance(drop, dict) else dropout_rng(dx, *drop)
@@ -684,8 +681,8 @@ def conv_wgrad(x, gy, g, with_bias=False, relu_x=False, out=None):
             fl16 = 2 if relu_x else 0
 
             def launch(extra=0):
-                check(lib.ctgan_conv2d16_wgrad_bias(ctypes.byref(d16), code, _ptr(x), _ptr(gy16), _ptr(dw), _ptr(db) if fused_b else None,
-                                                    _ptr(ws), ws.numel(), fl16 | extra, _stream()), 'conv2d16_wgrad')
+                check(lib.ctgan_conv2d16_wgrad(ctypes.byref(d16), code, _ptr(x), _ptr(gy16), _ptr(dw), _ptr(db) if fused_b else None,
+                                               _ptr(ws), ws.numel(), fl16 | extra, _stream()), 'conv2d16_wgrad')
             if PROFILE is None:
                 launch()
             else:               # bench.py: the GEMM alone inside the event bracket (what rocprofv3 lists under its symbol), its reduction after it
@@ -828,7 +825,7 @@ def conv_wgrad_group(groups):
         raise NotImplementedError('conv2d_wgrad_group: unsupported group')
     ws = workspace(nb, dev)            # (stream order: the split-mode launch above has read its slabs before these are written)
     if PROFILE is None:
-        check(lib.ctgan_conv2d_wgrad_group(arr, n, _ptr(ws), ws.numel(), _stream()), 'conv2d_wgrad_group')
+        check(lib.ctgan_conv2d_wgrad_group(arr, n, _ptr(ws), ws.numel(), 3, _stream()), 'conv2d_wgrad_group')
         return
     # bench.py's roofline leg: each grouped GEMM launch (one per tile configuration) alone inside its own event bracket (what rocprofv3
     # lists under that symbol), the batched split-K reduction after them
@@ -841,11 +838,11 @@ def conv_wgrad_group(groups):
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record(st)
         for _ in range(PROFILE_REPS):
-            check(lib.ctgan_conv2d_wgrad_group_ex(arr, n, _ptr(ws), ws.numel(), 1 | (16 << t), _stream()), 'conv2d_wgrad_group')
+            check(lib.ctgan_conv2d_wgrad_group(arr, n, _ptr(ws), ws.numel(), 1 | (16 << t), _stream()), 'conv2d_wgrad_group')
         e1.record(st)
         flops = sum(_conv_flops(groups[i][1], sum(sg[0].shape[0] for sg in groups[i][0])) for i in members)
         PROFILE.append((last_kernel(), flops, e0, e1, PROFILE_REPS, ('group', len(members)), last_symbol()))
-    check(lib.ctgan_conv2d_wgrad_group_ex(arr, n, _ptr(ws), ws.numel(), 2, _stream()), 'conv2d_wgrad_group')
+    check(lib.ctgan_conv2d_wgrad_group(arr, n, _ptr(ws), ws.numel(), 2, _stream()), 'conv2d_wgrad_group')
 
 
 def im2col(x, g, cpad):
@@ -1502,14 +1499,14 @@ def conv_fwd_bn_in_supported(x, g, tanh=False, labels=None, resid=None):
         return labels is None and resid is None
     if tanh:
         return False
-    if not (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID)):
+    if not _x3_available():
         return False
     y_strides = (g.K * g.P * g.Q, 1, g.Q * g.K, g.K)          # channels-last result (empty_cl)
     d = g.desc(x.shape[0], x.stride(), y_strides)
     # the launcher's own question (tiles of the fragment-streaming halo kernel inside one image); the fp32 mode also asks its routing
     if not lib.ctgan_conv2d16_bn_in_takes(ctypes.byref(d)):
         return False
-    return MMA_DTYPE == 'f32x3' or bool(lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0))
+    return MMA_DTYPE == 'f32x3' or _x3_prefers(d, 0)
 
 
 def conv_fwd_bn_in(x, w, bias, g, mean, rstd, scale, offset, groups, relu_in=True, tanh=False, out_strides=None, labels=None, resid=None,
@@ -1518,37 +1515,26 @@ def conv_fwd_bn_in(x, w, bias, g, mean, rstd, scale, offset, groups, relu_in=Tru
     the conv stages its input (ctgan_epilogue_ext.in_bn_*): the many -> few pixel kernel (3x3, <= 4 output channels, 32-pixel rows; no labels,
     no resid) or, in the split mode, the fragment-streaming halo kernel (stride 1, tiles inside one image, relu_in) - NotImplementedError
     elsewhere.  mean / rstd [groups, C] from bn_stats; scale / offset [C], or [n_labels, C] tables with labels (int32 per sample)."""
-    from ._lib import EpilogueExt
     _need_dev(x, w, bias, mean, rstd, scale, offset, labels, resid)
     N = x.shape[0]
     assert tuple(x.shape) == (N, g.C, g.H, g.W) and tuple(w.shape) == (g.R, g.S, g.C, g.K) and w.is_contiguous() and not g.x_up
     assert tuple(mean.shape) == (groups, g.C) and tuple(rstd.shape) == (groups, g.C) and scale.shape[-1] == g.C and offset.shape[-1] == g.C
     assert labels is not None or scale.numel() == g.C
-    if out_strides is None:
-        y = empty_cl(N, g.K, g.P, g.Q, x.device)
-    else:
-        y = torch.empty_strided((N, g.K, g.P, g.Q), out_strides, dtype=torch.float32, device=x.device)
+    y = _alloc_out((N, g.K, g.P, g.Q), out_strides, x.device)
     d = g.desc(N, x.stride(), y.stride())
-    e = EpilogueExt(0.0, 0, 0, None)
-    e.in_bn_mean, e.in_bn_rstd, e.in_bn_scale, e.in_bn_offset = mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), offset.data_ptr()
-    e.in_bn_groups, e.out_tanh = int(groups), 1 if tanh else 0
-    e.in_bn_labels = labels.data_ptr() if labels is not None else None
+    ext = _epilogue_ext(bn_in=(mean, rstd, scale, offset, groups, labels), tanh=tanh)
     if fewch_handles(g):
         if labels is not None or resid is not None:
             raise NotImplementedError('conv_fwd_bn_in: the many -> few kernel takes neither labels nor a residual')
-        _timed(g, N, lambda: check(lib.ctgan_conv2d_fwd_ex(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), None, _ptr(y), 2 if relu_in else 0, ctypes.byref(e), _stream()), 'conv2d_fwd'))
-        return y
-    if tanh or not (MMA_DTYPE == 'f32x3' or (MMA_DTYPE is None and X3_HYBRID and lib.ctgan_conv2d16_x3_prefers(ctypes.byref(d), 0))):
+        return _run_conv(0, None, d, g, N, x, w, y, bias=bias, flags=2 if relu_in else 0, ext=ext)
+    if tanh or not (MMA_DTYPE == 'f32x3' or _x3_prefers(d, 0)):
         raise NotImplementedError('conv_fwd_bn_in: batch norm on load exists in the split mode\'s halo kernel and in the many -> few pixel kernel')
     if resid is not None and resid_up:
         assert tuple(resid.shape) == (N, g.K, g.P // 2, g.Q // 2) and resid.permute(0, 2, 3, 1).is_contiguous()
     elif resid is not None:
         assert is_dense_like(resid, y)
-    wp = _packed16(w, d, 0, g, 'f32x3')
     fl = (2 if relu_in else 0) | (8 if (resid_up and resid is not None) else 0)
-    _timed(g, N, lambda: check(lib.ctgan_conv2d16_fwd_ex(ctypes.byref(d), 3, _ptr(x), _ptr(wp), _ptr(bias), _ptr(resid), _ptr(y), fl, ctypes.byref(e), None, 0, _stream()),
-                               'conv2d16_fwd_ex'))
-    return y
+    return _run_conv(0, 'f32x3', d, g, N, x, w, y, bias=bias, resid=resid, flags=fl, ext=ext, split_ws=False)
 
 
 def bn_fwd_f64(x, scale, offset, labels, groups, relu, eps=1e-5):
@@ -2045,40 +2031,27 @@ def tail_critic_heads_fwd(y, B, w_out, b_out, w_ac, b_ac, labels, gp, lam2, M, s
     n, hw, nf = _cl_rows(y)
     assert n == 3 * B and w_out.is_contiguous() and w_out.numel() == nf
     dev = y.device
-    if slopes is not None or y_clean is not None:
-        assert slopes is None or (gp is not None and slopes.is_contiguous() and slopes.numel() == B)
-        ncls = w_ac.shape[1] if w_ac is not None else 0
-        f_c = a_c = acc = None
-        if y_clean is not None:
-            n2, hw2, nf2 = _cl_rows(y_clean)
-            assert (n2, hw2, nf2) == (2 * B, hw, nf) and w_ac is not None
-            f_c = torch.empty(n2, nf, dtype=torch.float32, device=dev)
-            a_c = torch.empty(n2, ncls, dtype=torch.float32, device=dev)
-            acc = torch.empty(2, dtype=torch.float32, device=dev)
-        f = torch.empty(n, nf, dtype=torch.float32, device=dev)
-        d = torch.empty(n, dtype=torch.float32, device=dev)
-        a = torch.empty(n, ncls, dtype=torch.float32, device=dev) if w_ac is not None else None
-        probs = torch.empty(B, ncls, dtype=torch.float32, device=dev) if w_ac is not None else None
-        ce_i = torch.empty(B, dtype=torch.float32, device=dev) if w_ac is not None else None
-        ct_i = torch.empty(B, dtype=torch.float32, device=dev)
-        out = torch.empty(5, dtype=torch.float32, device=dev)
-        check(lib.ctgan_tail_critic_heads_fwd2(_ptr(y), B, hw, nf, _ptr(w_out), _ptr(b_out), _ptr(w_ac), _ptr(b_ac), ncls, _ptr(labels), _ptr(gp),
-                                               _ptr(slopes), gp_lambda, _ptr(y_clean), 1 if clean_relu else 0, _ptr(f_c), _ptr(a_c), _ptr(acc),
-                                               lam2, M, scale, _ptr(f), _ptr(d), _ptr(a), _ptr(ct_i), _ptr(probs), _ptr(ce_i), _ptr(out),
-                                               _stream()), 'tail_critic_heads_fwd2')
-        return out, f, d, a, ct_i, probs, acc
+    assert slopes is None or (gp is not None and slopes.is_contiguous() and slopes.numel() == B)
+    ncls = w_ac.shape[1] if w_ac is not None else 0
+    f_c = a_c = acc = None
+    if y_clean is not None:
+        n2, hw2, nf2 = _cl_rows(y_clean)
+        assert (n2, hw2, nf2) == (2 * B, hw, nf) and w_ac is not None
+        f_c = torch.empty(n2, nf, dtype=torch.float32, device=dev)
+        a_c = torch.empty(n2, ncls, dtype=torch.float32, device=dev)
+        acc = torch.empty(2, dtype=torch.float32, device=dev)
     f = torch.empty(n, nf, dtype=torch.float32, device=dev)
     d = torch.empty(n, dtype=torch.float32, device=dev)
-    ncls = w_ac.shape[1] if w_ac is not None else 0
     a = torch.empty(n, ncls, dtype=torch.float32, device=dev) if w_ac is not None else None
     probs = torch.empty(B, ncls, dtype=torch.float32, device=dev) if w_ac is not None else None
     ce_i = torch.empty(B, dtype=torch.float32, device=dev) if w_ac is not None else None
     ct_i = torch.empty(B, dtype=torch.float32, device=dev)
     out = torch.empty(5, dtype=torch.float32, device=dev)
     check(lib.ctgan_tail_critic_heads_fwd(_ptr(y), B, hw, nf, _ptr(w_out), _ptr(b_out), _ptr(w_ac), _ptr(b_ac), ncls, _ptr(labels), _ptr(gp),
+                                          _ptr(slopes), gp_lambda, _ptr(y_clean), 1 if clean_relu else 0, _ptr(f_c), _ptr(a_c), _ptr(acc),
                                           lam2, M, scale, _ptr(f), _ptr(d), _ptr(a), _ptr(ct_i), _ptr(probs), _ptr(ce_i), _ptr(out),
                                           _stream()), 'tail_critic_heads_fwd')
-    return out, f, d, a, ct_i, probs, None
+    return out, f, d, a, ct_i, probs, acc
 
 
 def tail_heads_bwd(y, d, f, probs, labels, ct_i, gout, B, lam2, M, scale, mask_scale, w_out, w_ac, out=None, y_gp=None, out_gp=None):
@@ -2102,9 +2075,9 @@ def tail_heads_bwd(y, d, f, probs, labels, ct_i, gout, B, lam2, M, scale, mask_s
         n_gp = y_gp.shape[0]
         assert out_gp is not None and tuple(out_gp.shape) == tuple(y_gp.shape) and _cl_rows(y_gp) == (n_gp, hw, nf) and _cl_rows(out_gp) == (n_gp, hw, nf)
         assert w_out.is_contiguous()
-    check(lib.ctgan_tail_heads_bwd_gp(_ptr(y), _ptr(d), _ptr(f), _ptr(probs), _ptr(labels), _ptr(ct_i), _ptr(gout), gout.numel(), B, hw, nf, ncls,
-                                      lam2, M, scale, mask_scale, _ptr(w_out), _ptr(w_ac), _ptr(gy), _ptr(gw_out), _ptr(gb_out), _ptr(gw_ac),
-                                      _ptr(gb_ac), _ptr(y_gp), n_gp, _ptr(out_gp), _stream()), 'tail_heads_bwd')
+    check(lib.ctgan_tail_heads_bwd(_ptr(y), _ptr(d), _ptr(f), _ptr(probs), _ptr(labels), _ptr(ct_i), _ptr(gout), gout.numel(), B, hw, nf, ncls,
+                                   lam2, M, scale, mask_scale, _ptr(w_out), _ptr(w_ac), _ptr(gy), _ptr(gw_out), _ptr(gb_out), _ptr(gw_ac),
+                                   _ptr(gb_ac), _ptr(y_gp), n_gp, _ptr(out_gp), _stream()), 'tail_heads_bwd')
     return gy, gw_out, gb_out, gw_ac, gb_ac
 
 
@@ -2157,10 +2130,8 @@ def gp_head_wgrad(gg, y, mask_scale, like, add_to=None):
     ws = torch.empty(64 * nf, dtype=torch.float32, device=y.device)
     if add_to is not None:
         assert add_to.is_contiguous() and add_to.numel() == nf
-        check(lib.ctgan_gp_head_wgrad_acc(_ptr(gg), _ptr(y), n, hw, nf, mask_scale, _ptr(add_to), _ptr(ws), _stream()), 'gp_head_wgrad_acc')
-        return add_to
-    gw = torch.empty_like(like)
-    check(lib.ctgan_gp_head_wgrad(_ptr(gg), _ptr(y), n, hw, nf, mask_scale, _ptr(gw), _ptr(ws), _stream()), 'gp_head_wgrad')
+    gw = add_to if add_to is not None else torch.empty_like(like)
+    check(lib.ctgan_gp_head_wgrad(_ptr(gg), _ptr(y), n, hw, nf, mask_scale, _ptr(gw), _ptr(ws), 0 if add_to is None else 1, _stream()), 'gp_head_wgrad')
     return gw
 
 

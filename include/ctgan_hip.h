@@ -90,11 +90,11 @@ typedef struct ctgan_epilogue_ext {
     int32_t range_end[CTGAN_DROP_RANGES];
     float range_keep[CTGAN_DROP_RANGES];
     uint64_t range_stream_id[CTGAN_DROP_RANGES];
-    /* forward only (ctgan_conv2d_fwd_ex, ctgan_conv2d16_fwd_ex): the result is kept only where out_mask > 0 (strides of y; after the
+    /* forward only (ctgan_conv2d_fwd, ctgan_conv2d16_fwd): the result is kept only where out_mask > 0 (strides of y; after the
      * bias, before resid - the order of the dgrad epilogue's mask).  Used by the double backward of the gradient penalty, where the
      * conv that follows multiplies its input with a constant ReLU mask (TF/CT_gan_cifar_resnet.py:284-286 through :109-141).  NULL = none. */
     const float* out_mask;
-    /* 16-bit slice kernels only (ctgan_conv2d16_fwd_ex / ctgan_conv2d16_dgrad_ex, mma = CTGAN_MMA_BF16 / CTGAN_MMA_F16, dense channels-last
+    /* 16-bit slice kernels only (ctgan_conv2d16_fwd / ctgan_conv2d16_dgrad, mma = CTGAN_MMA_BF16 / CTGAN_MMA_F16, dense channels-last
      * result): act = 1 applies the LeakyReLU + dropout pair of the DCGAN critics (TF/CT_gan_cifar.py:86-98, TF/CT_gan_mnist.py:94-106:
      * tf.nn.dropout(LeakyReLU(conv))) to the result r after bias / mask / resid / relu:
      *     out = r * (ref > 0 ? 1 : act_alpha) * floor(keep + u) / keep,   ref = act_ref ? act_ref[same offset] : r
@@ -104,7 +104,7 @@ typedef struct ctgan_epilogue_ext {
     int32_t act;
     float act_alpha;
     const float* act_ref;
-    /* ctgan_conv2d_fwd_ex, many -> few convs on the one-pixel-per-lane kernel only (3x3, <= 4 output channels, 32-pixel rows; the generator's
+    /* ctgan_conv2d_fwd, many -> few convs on the one-pixel-per-lane kernel only (3x3, <= 4 output channels, 32-pixel rows; the generator's
      * output stage tanh(Conv2D(relu(Batchnorm(h)))), TF/CT_gan_cifar_resnet.py:164-166, evaluated without a tape): training-mode batch norm of
      * the INPUT applied while it is staged - x' = (x - in_bn_mean[g][c]) * in_bn_rstd[g][c] * in_bn_scale[c] + in_bn_offset[c], g = sample /
      * (N / in_bn_groups), then CTGAN_IN_RELU if set; the SAME zero padding stays zero - and out_tanh: tanh of the result.  The arithmetic of
@@ -115,16 +115,11 @@ typedef struct ctgan_epilogue_ext {
     const float* in_bn_offset;
     int32_t in_bn_groups;
     int32_t out_tanh;
-    /* ... and on ctgan_conv2d16_fwd_ex (mma = CTGAN_MMA_F32X3, stride 1, launches the fragment-streaming halo kernel takes with tiles inside one image,
+    /* ... and on ctgan_conv2d16_fwd (mma = CTGAN_MMA_F32X3, stride 1, launches the fragment-streaming halo kernel takes with tiles inside one image,
      * CTGAN_IN_RELU set): the same batch norm while the halo patch is staged - the generator's Conv2 layers (TF/CT_gan_cifar_resnet.py:134-141) without
      * a tape.  in_bn_labels (int32 per sample, or NULL): conditional batch norm - in_bn_scale / in_bn_offset are [n_labels][C] tables.  */
     const int32_t* in_bn_labels;
 } ctgan_epilogue_ext;
-int ctgan_conv2d_fwd_ex(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias, const float* resid,
-                        float* y, int flags, const ctgan_epilogue_ext* ext, ctgan_stream_t stream);
-int ctgan_conv2d_dgrad_ex(const ctgan_conv_desc* d, const float* dy, const float* w, const float* bias,
-                          const float* mask, const float* resid, float* dx, void* ws, size_t ws_bytes, int flags,
-                          const ctgan_epilogue_ext* ext, ctgan_stream_t stream);
 /* Weight gradient of ONE filter over several (x, dy) pairs of the same geometry and strides (the uses of the filter in
  * different passes of a step: the dropout passes and the gradient-penalty double backward,
  * TF/CT_gan_cifar_resnet.py:284,335-336 sum them in tf.gradients): dw = sum_s wgrad(xs[s], dys[s]) in one launch + one
@@ -158,14 +153,15 @@ typedef struct ctgan_wgrad_group {
     const float* add_dw;
     const float* add_db;
 } ctgan_wgrad_group;
-size_t ctgan_conv2d_wgrad_group_workspace_bytes(const ctgan_wgrad_group* groups, int32_t n);
-int ctgan_conv2d_wgrad_group(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes,
-                             ctgan_stream_t stream);
-/* The two phases of the grouped launch separately (bench.py times the GEMM launches alone, as rocprofv3 reports them): the grouped
-   weight-gradient kernels write the split-K slabs, the batched reduction sums them into dw / db in a fixed order.             */
+/* phases = CTGAN_WGRAD_GROUP_GEMM | CTGAN_WGRAD_GROUP_REDUCE for the whole call, or the two phases of the grouped launch separately
+   (bench.py times the GEMM launches alone, as rocprofv3 reports them): the grouped weight-gradient kernels write the split-K slabs, the
+   batched reduction sums them into dw / db in a fixed order.                                                                    */
 enum { CTGAN_WGRAD_GROUP_GEMM = 1, CTGAN_WGRAD_GROUP_REDUCE = 2,
        /* optional: restrict the GEMM phase to the launch of one tile configuration (bit CTGAN_WGRAD_GROUP_TILE0 << t, t = 0..3) */
        CTGAN_WGRAD_GROUP_TILE0 = 16, CTGAN_WGRAD_GROUP_TILE_MASK = 16 | 32 | 64 | 128 };
+size_t ctgan_conv2d_wgrad_group_workspace_bytes(const ctgan_wgrad_group* groups, int32_t n);
+int ctgan_conv2d_wgrad_group(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes, int phases,
+                             ctgan_stream_t stream);
 /* The same grouped call on the 16-bit family - mma = CTGAN_MMA_F32X3 (fp32 accuracy on the bf16 matrix cores at 6/16 of the fp32 MFMA's
    cost: the hybrid fp32 mode's weight gradients) or CTGAN_MMA_BF16 / CTGAN_MMA_F16 (the small weight gradients of the mixed-precision configs):
    every segment of every group is one problem of ONE launch of 128x128-tile workgroups with a common pixels-per-split, then one batched
@@ -178,23 +174,22 @@ int ctgan_conv2d16_wgrad_group(const ctgan_wgrad_group* groups, int32_t n, int m
                                ctgan_stream_t stream);
 /* the launch (0..3) of a grouped call that problem g rides in; -1 if it does not qualify */
 int ctgan_conv2d_wgrad_group_tile(const ctgan_wgrad_group* g);
-int ctgan_conv2d_wgrad_group_ex(const ctgan_wgrad_group* groups, int32_t n, void* ws, size_t ws_bytes, int phases,
-                                ctgan_stream_t stream);
 /* ---- convolution family  (replaces tf.nn.conv2d TF/tflib/ops/conv2d.py:106-112,
  *      tf.nn.conv2d_transpose TF/tflib/ops/deconv2d.py:97-103, tf.matmul
  *      TF/tflib/ops/linear.py:132-137 (as 1x1 conv on a 1x1 image), and the conv gradient nodes
  *      tf.gradients / compute_gradients generate, TF/CT_gan_cifar_resnet.py:284,335-336) ------- */
 size_t ctgan_conv2d_workspace_bytes(const ctgan_conv_desc* d, int op);
-/* y = conv(x,w) [+ bias[k]] [+ resid (same strides as y)] [relu if flags&CTGAN_EPI_RELU]       */
-int ctgan_conv2d_fwd(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias,
-                     const float* resid, float* y, int flags, ctgan_stream_t stream);
+/* y = conv(x,w) [+ bias[k]] [+ resid (same strides as y)] [relu if flags&CTGAN_EPI_RELU]; ext (NULL = none): the
+ * epilogue extension above                                                                     */
+int ctgan_conv2d_fwd(const ctgan_conv_desc* d, const float* x, const float* w, const float* bias, const float* resid,
+                     float* y, int flags, const ctgan_epilogue_ext* ext, ctgan_stream_t stream);
 /* dx = adjoint of conv w.r.t. x, applied to dy [+ bias[c]] (dx has the strides d->xs; x_up must
  * be 0).  With bias this is Deconv2D's forward (TF/tflib/ops/deconv2d.py:97-110).               */
 /* epilogue: dx = (conv^T(dy,w) + bias) [kept only where mask > 0: the ReLU backward of conv(relu(x)),
- * mask = x] [+ resid].  mask and resid have the strides of dx.                                    */
+ * mask = x] [+ resid] [times the dropout mask of ext; NULL = none].  mask and resid have the strides of dx. */
 int ctgan_conv2d_dgrad(const ctgan_conv_desc* d, const float* dy, const float* w, const float* bias,
-                       const float* mask, const float* resid, float* dx, void* ws, size_t ws_bytes,
-                       int flags, ctgan_stream_t stream);
+                       const float* mask, const float* resid, float* dx, void* ws, size_t ws_bytes, int flags,
+                       const ctgan_epilogue_ext* ext, ctgan_stream_t stream);
 /* wt[r',s',k,c] = w[R-1-r',S-1-s',c,k]: the rotated, I/O-swapped filter the data gradient multiplies
  * with.  Callers that run several dgrads per weight update repack once and pass
  * CTGAN_DGRAD_W_REPACKED (then `w` is wt and no workspace is needed).                            */
@@ -268,7 +263,7 @@ int ctgan_conv2d16_supported(const ctgan_conv_desc* d, int op, int mma);        
  * on the fp32 MFMA entry points - the results carry fp32 accuracy either way.  A forward launch with prefers = 1 and stride 1 also
  * accepts CTGAN_RESID_UP.                                                                                                    */
 int ctgan_conv2d16_x3_prefers(const ctgan_conv_desc* d, int op);
-/* 1 when ctgan_conv2d16_fwd_ex (mma = CTGAN_MMA_F32X3, CTGAN_IN_RELU) takes this forward launch with the input batch norm on load
+/* 1 when ctgan_conv2d16_fwd (mma = CTGAN_MMA_F32X3, CTGAN_IN_RELU) takes this forward launch with the input batch norm on load
  * (ctgan_epilogue_ext::in_bn_*): stride 1 on the fragment-streaming halo kernel with every tile inside one image.  The launcher asks
  * the same function, so a caller that gets 1 here never computes the moments for a launch that is then refused.                   */
 int ctgan_conv2d16_bn_in_takes(const ctgan_conv_desc* d);
@@ -284,29 +279,22 @@ int ctgan_conv2d16_pack_batch(const ctgan_conv_desc* descs, const int32_t* ops, 
 /* ws (optional, ctgan_conv2d16_workspace_bytes(d, op) bytes): slabs for a K split of launches whose pixel x channel tiles cannot
  * fill the chip (8x8 / 4x4 layers at batch 64); NULL = never split.                                                      */
 size_t ctgan_conv2d16_workspace_bytes(const ctgan_conv_desc* d, int op);
+/* ext (NULL = none) with the epilogue dropout of ctgan_conv2d_fwd (same ext, same draws): mma = CTGAN_MMA_F32X3 on launches the halo-patch
+ * kernel takes (ctgan_conv2d16_x3_prefers, stride 1); CTGAN_E_UNSUPPORTED otherwise - the caller then uses ctgan_conv2d_fwd.       */
 int ctgan_conv2d16_fwd(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
-                       float* y, int flags, void* ws, size_t ws_bytes, ctgan_stream_t stream);
-/* forward with the epilogue dropout of ctgan_conv2d_fwd_ex (same ext, same draws): mma = CTGAN_MMA_F32X3 on launches the halo-patch
- * kernel takes (ctgan_conv2d16_x3_prefers, stride 1); CTGAN_E_UNSUPPORTED otherwise - the caller then uses ctgan_conv2d_fwd_ex.   */
-int ctgan_conv2d16_fwd_ex(const ctgan_conv_desc* d, int mma, const float* x, const void* wp, const float* bias, const float* resid,
-                          float* y, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes, ctgan_stream_t stream);
-int ctgan_conv2d16_dgrad(const ctgan_conv_desc* d, int mma, const float* dy, const void* wp, const float* bias,
-                         const float* mask, const float* resid, float* dx, int flags, void* ws, size_t ws_bytes,
-                         ctgan_stream_t stream);
-/* data gradient with the epilogue dropout of ctgan_conv2d_dgrad_ex (dx multiplied by the mask of ext's dropout, same draws at the same
+                       float* y, int flags, const ctgan_epilogue_ext* ext, void* ws, size_t ws_bytes, ctgan_stream_t stream);
+/* ext (NULL = none) with the epilogue dropout of ctgan_conv2d_dgrad (dx multiplied by the mask of ext's dropout, same draws at the same
  * physical offsets): mma = CTGAN_MMA_F32X3, stride 1, dense channels-last dx, launches the halo-patch kernels take; CTGAN_E_UNSUPPORTED
- * otherwise - the caller then uses ctgan_conv2d_dgrad_ex.                                                                          */
-int ctgan_conv2d16_dgrad_ex(const ctgan_conv_desc* d, int mma, const float* dy, const void* wp, const float* bias,
-                            const float* mask, const float* resid, float* dx, int flags, const ctgan_epilogue_ext* ext, void* ws,
-                            size_t ws_bytes, ctgan_stream_t stream);
+ * otherwise - the caller then uses ctgan_conv2d_dgrad.                                                                             */
+int ctgan_conv2d16_dgrad(const ctgan_conv_desc* d, int mma, const float* dy, const void* wp, const float* bias,
+                         const float* mask, const float* resid, float* dx, int flags, const ctgan_epilogue_ext* ext, void* ws,
+                         size_t ws_bytes, ctgan_stream_t stream);
 size_t ctgan_conv2d16_wgrad_workspace_bytes(const ctgan_conv_desc* d, int mma);
-int ctgan_conv2d16_wgrad(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, void* ws,
+/* db != NULL: the bias gradient db[K] = sum over pixels of dy fused into the same launch (the workgroups of the first tile row sum the dy
+ * tiles they stage; fixed-order reduction): replaces the separate ctgan_colsum pass.  db NULL = the filter gradient alone.         */
+int ctgan_conv2d16_wgrad(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, float* db, void* ws,
                          size_t ws_bytes, int flags, ctgan_stream_t stream);
-/* ... with the bias gradient db[K] = sum over pixels of dy fused into the same launch (the workgroups of the first tile row sum the dy
- * tiles they stage; fixed-order reduction): replaces the separate ctgan_colsum pass.  db NULL = ctgan_conv2d16_wgrad.              */
-int ctgan_conv2d16_wgrad_bias(const ctgan_conv_desc* d, int mma, const float* x, const float* dy, float* dw, float* db, void* ws,
-                              size_t ws_bytes, int flags, ctgan_stream_t stream);
-/* flags of ctgan_conv2d16_wgrad(_bias) besides CTGAN_IN_RELU: launch only the split-K GEMM (slabs stay in ws) / only the reduction of
+/* flags of ctgan_conv2d16_wgrad besides CTGAN_IN_RELU: launch only the split-K GEMM (slabs stay in ws) / only the reduction of
    slabs a GEMM-only call left there - bench.py times the two kernels apart, as rocprofv3 lists them                               */
 enum { CTGAN_WGRAD16_GEMM_ONLY = 0x100, CTGAN_WGRAD16_REDUCE_ONLY = 0x200 };
 /* dw[r,s,c,k] = sum_{n,p,q} x[..] * dy[n,k,p,q]   (HWIO, contiguous; deterministic split-K);
@@ -584,26 +572,23 @@ int ctgan_tail_heads_fwd(const float* y, int32_t n, int32_t hw, int32_t nf, int3
 /* tail_heads_fwd on the 3B rows of a critic step (relu = 0) + ctgan_critic_heads_fwd in two launches: the workgroup of
  * real sample i owns both of its dropout passes (rows i and 2B+i) and writes ct_i[i], probs[i,:] and ce_i[i] (scratch
  * [B]); a one-workgroup kernel then takes the batch means into out[5].                                                */
-int ctgan_tail_critic_heads_fwd(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
-                                const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels,
-                                const float* gp, float lambda2, float M, float acgan_scale, float* f, float* d, float* a,
-                                float* ct_i, float* probs, float* ce_i, float* out, ctgan_stream_t stream);
-/* ... with two more reductions folded into the same two launches:
+/* ... with two optional reductions folded into the same two launches (slopes = NULL, y_clean = NULL: neither, gp is only read):
  *   slopes != NULL (gp then non-NULL): the gradient penalty's batch mean gp[0] = gp_lambda * mean((slopes - 1)^2) (:286) is taken by the
  *     one-workgroup kernel and written to gp[0] before it enters out[] (pair with ctgan_gp_fwd(.., gp = NULL));
  *   y_clean != NULL ([2B][hw][nf], real rows then fake rows, the dropout-free pass :228): a_clean [2B,ncls] = class head of its rows
  *     (relu'd first when clean_relu; f_clean [2B,nf] scratch) by extra workgroups of the rows launch, and the accuracies acc[2]
  *     (:249-266, as ctgan_accuracy2) by the one-workgroup kernel.                                                              */
-int ctgan_tail_critic_heads_fwd2(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
-                                 const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float* gp,
-                                 const float* slopes, float gp_lambda, const float* y_clean, int32_t clean_relu, float* f_clean,
-                                 float* a_clean, float* acc, float lambda2, float M, float acgan_scale, float* f, float* d, float* a,
-                                 float* ct_i, float* probs, float* ce_i, float* out, ctgan_stream_t stream);
-int ctgan_tail_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels,
-                         const float* ct_i, const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf,
-                         int32_t ncls, float lambda2, float M, float acgan_scale, float mask_scale, const float* w_out,
-                         const float* w_ac, float* gy, float* gw_out, float* gb_out, float* gw_ac, float* gb_ac,
-                         ctgan_stream_t stream);
+int ctgan_tail_critic_heads_fwd(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
+                                const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float* gp,
+                                const float* slopes, float gp_lambda, const float* y_clean, int32_t clean_relu, float* f_clean,
+                                float* a_clean, float* acc, float lambda2, float M, float acgan_scale, float* f, float* d, float* a,
+                                float* ct_i, float* probs, float* ce_i, float* out, ctgan_stream_t stream);
+/* n_gp > 0: also writes gz_gp = ctgan_gp_head_grad(y_gp) for the n_gp rows of the penalty pass (the seeds of BOTH backward chains in
+ * one launch - the hand-scheduled critic step, critic_schedule.py, runs them as one chain); y_gp = NULL, n_gp = 0, gz_gp = NULL: none. */
+int ctgan_tail_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* ct_i,
+                         const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf, int32_t ncls, float lambda2, float M,
+                         float acgan_scale, float mask_scale, const float* w_out, const float* w_ac, float* gy, float* gw_out,
+                         float* gb_out, float* gw_ac, float* gb_ac, const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t stream);
 /* Generator-step loss on the critic's output head (TF/CT_gan_cifar_resnet.py:321-330): cost = -mean(d) + ac_scale * CE(a, labels)
  * with f, d, a as in ctgan_tail_heads_fwd (two launches), and its backward straight to the gradient w.r.t. the last critic
  * conv's result (both Linear data gradients, the mean's broadcast, the relu/dropout mask) in one launch; the critic's weights
@@ -614,25 +599,17 @@ int ctgan_gen_heads_fwd(const float* y, int32_t n, int32_t hw, int32_t nf, const
 int ctgan_gen_heads_bwd(const float* y, const float* probs, const int32_t* labels, const float* gout, int32_t n, int32_t hw,
                         int32_t nf, int32_t ncls, float ac_scale, float mask_scale, const float* w_out, const float* w_ac,
                         float* gy, ctgan_stream_t stream);
-/* Round 5 (the hand-scheduled critic step, critic_schedule.py): three launches folded into their neighbours.
- *   ctgan_tail_heads_bwd_gp  = ctgan_tail_heads_bwd that also writes gz_gp = ctgan_gp_head_grad(y_gp) for the n_gp rows of the penalty pass
- *                              (the seeds of BOTH backward chains in one launch - the step runs them as one chain);
- *   ctgan_gp_head_wgrad_acc  = ctgan_gp_head_wgrad that ADDS onto gw (the head weight's gradient from the dropout passes);
+/* Round 5 (the hand-scheduled critic step, critic_schedule.py): launches folded into their neighbours.
+ *   ctgan_gp_head_wgrad      : accumulate != 0 ADDS onto gw (the head weight's gradient from the dropout passes) instead of writing it;
  *   ctgan_gp_finish          : ga [b, c*h*w] (NCHW, in place) += scale * upsample2(gs [b,c,h/2,w/2], element strides gs_strides[4]) and
  *                              slopes[b] = ||ga[b,:]||_2 - dD/dx_hat = gradient through the first conv + gradient through the pooled 1x1
  *                              shortcut (:146-153, :284-285) in one launch instead of upsample + add + ctgan_gp_fwd.                      */
-int ctgan_tail_heads_bwd_gp(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* ct_i,
-                            const float* gout, int32_t n_gout, int32_t B, int32_t hw, int32_t nf, int32_t ncls, float lambda2, float M,
-                            float acgan_scale, float mask_scale, const float* w_out, const float* w_ac, float* gy, float* gw_out,
-                            float* gb_out, float* gw_ac, float* gb_ac, const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t stream);
-int ctgan_gp_head_wgrad_acc(const float* gg, const float* y, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gw,
-                            float* ws /* 64 * nf floats */, ctgan_stream_t stream);
 int ctgan_gp_finish(float* ga, const float* gs, const int64_t* gs_strides, int32_t b, int32_t c, int32_t h, int32_t w, float scale, float* slopes,
                     ctgan_stream_t stream);
 int ctgan_gp_head_grad(const float* y, const float* w_out, int32_t n, int32_t hw, int32_t nf, float mask_scale,
                        float* gz, ctgan_stream_t stream);
 int ctgan_gp_head_wgrad(const float* gg, const float* y, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gw,
-                        float* ws /* 64 * nf floats */, ctgan_stream_t stream);
+                        float* ws /* 64 * nf floats */, int accumulate, ctgan_stream_t stream);
 /* ACGAN accuracies of the clean critic pass (:249-266): logits [2B,ncls] (real rows, then fake rows); acc[2]   */
 int ctgan_accuracy2(const float* logits, const int32_t* labels, int32_t B, int32_t ncls, float* acc,
                     ctgan_stream_t stream);

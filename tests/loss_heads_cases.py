@@ -627,7 +627,7 @@ def check_tail_critic(be, B, nf, H, W, ncls):
             gr = torch.autograd.grad(combr, rins + [dr], retain_graph=True)
             check_tail_grads('tail_heads bwd', gg, gr[:-1], gr[-1])
 
-        # the same forward with the penalty's mean and the clean pass folded in (ctgan_tail_critic_heads_fwd2), then the backward with its
+        # the same forward with the penalty's mean and the clean pass folded in (ctgan_tail_critic_heads_fwd with slopes / y_clean), then the backward with its
         # outputs in the leading rows of larger buffers and the penalty pass's rows riding the launch
         sl = torch.tensor([GP_TARGETS[i % 4] for i in range(B)]) + torch.rand(B, generator=g) * 0.1
         gp_ref = 10.0 * ((sl.double() - 1) ** 2).mean()

@@ -51,6 +51,21 @@ def test_removed_step_variants_stay_removed():
     assert not [n for n in list(_lib.SIGNATURES) + list(_lib.DEBUG_SIGNATURES) if 'chain8x8' in n]
 
 
+def test_forwarding_twins_stay_removed():
+    """One C entry per operation: the nine entry points that only forwarded to a wider sibling (or differed from it in one flag) are gone from
+    the ctypes table and from the library's exports; the un-suffixed name carries the wider signature."""
+    from ctgan_amd import _lib
+    twins = ('ctgan_conv2d_fwd_ex', 'ctgan_conv2d_dgrad_ex', 'ctgan_conv2d16_fwd_ex', 'ctgan_conv2d16_dgrad_ex', 'ctgan_conv2d16_wgrad_bias',
+             'ctgan_conv2d_wgrad_group_ex', 'ctgan_tail_critic_heads_fwd2', 'ctgan_tail_heads_bwd_gp', 'ctgan_gp_head_wgrad_acc')
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in twins:
+        assert name not in _lib.SIGNATURES, name
+        assert not hasattr(lib, name), name
+    ext = ctypes.POINTER(_lib.EpilogueExt)
+    for name in ('ctgan_conv2d_fwd', 'ctgan_conv2d_dgrad', 'ctgan_conv2d16_fwd', 'ctgan_conv2d16_dgrad'):
+        assert ext in _lib.SIGNATURES[name][1], name
+
+
 def test_conv_desc_layout_matches_header():
     """struct ctgan_conv_desc: 14 int32 then 2 x int64[4] (8-byte aligned) = 120 bytes."""
     from ctgan_amd._lib import ConvDesc
@@ -63,7 +78,7 @@ def test_error_reporting_without_gpu():
     from ctgan_amd import _lib
     rc = _lib.lib.ctgan_dropout(None, None, None, 4, 0.0, None)
     assert rc == -1 and b'keep' in _lib.lib.ctgan_last_error()
-    rc = _lib.lib.ctgan_conv2d_fwd(None, None, None, None, None, None, 0, None)
+    rc = _lib.lib.ctgan_conv2d_fwd(None, None, None, None, None, None, 0, None, None)
     assert rc == -1
 
 

@@ -881,7 +881,7 @@ def test_fused_critic_tail_heads(K, B, nf, H, with_a):
 
 @pytest.mark.parametrize('B,nf,H', [(64, 128, 8), (5, 32, 4)])
 def test_penalty_mean_and_clean_accuracies_folded_into_the_heads_launches(K, B, nf, H):
-    """ctgan_tail_critic_heads_fwd2: gp from the slopes (written into the slot gp_fwd(defer_mean=True) left) and the clean pass's class
+    """ctgan_tail_critic_heads_fwd with slopes / y_clean: gp from the slopes (written into the slot gp_fwd(defer_mean=True) left) and the clean pass's class
     head + accuracies inside the two launches of the fused heads - bit-identical to gp_fwd + tail_critic_heads_fwd + tail_heads_fwd +
     accuracy2 as separate launches."""
     g = torch.Generator().manual_seed(B + nf)
@@ -1072,8 +1072,8 @@ def test_many_to_few_one_pixel_per_lane_kernel(K, N, C, dgrad):
 
 
 def test_launches_folded_into_their_neighbours_for_the_hand_scheduled_critic_step(K):
-    """Round 5 (critic_schedule.py): (i) ctgan_tail_heads_bwd_gp = tail_heads_bwd + gp_head_grad for the penalty rows in one launch, bit for bit;
-    (ii) ctgan_gp_head_wgrad_acc adds onto a finished gradient; (iii) ctgan_gp_finish = upsample2 + add + per-sample norms."""
+    """Round 5 (critic_schedule.py): (i) ctgan_tail_heads_bwd with penalty rows = tail_heads_bwd + gp_head_grad for the penalty rows in one launch, bit for bit;
+    (ii) ctgan_gp_head_wgrad (accumulate) adds onto a finished gradient; (iii) ctgan_gp_finish = upsample2 + add + per-sample norms."""
     g = torch.Generator().manual_seed(9)
     B, nf, hw = 8, 128, 64
     y = cl(torch.randn(4 * B, nf, 8, 8, generator=g))

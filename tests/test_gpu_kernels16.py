@@ -509,7 +509,7 @@ def test_f32x3_halo_kernel_applies_the_epilogue_dropout_of_the_fp32_family(K, ra
 
 
 def test_f32x3_wgrad_with_the_fused_bias_gradient(K):
-    """ctgan_conv2d16_wgrad_bias: db = column sums of dy from the same launch (workgroups of the first tile row), equal to the separate
+    """ctgan_conv2d16_wgrad with db: db = column sums of dy from the same launch (workgroups of the first tile row), equal to the separate
     column-sum pass to fp32 summation error, for one split and many, and dw unchanged by it (bit-identical to the launch without db)."""
     for N, C, H, Ko, k, st in [(8, 128, 16, 128, 3, 1), (128, 128, 32, 128, 4, 2), (2, 128, 8, 256, 3, 1)]:
         g = torch.Generator().manual_seed(N)

@@ -343,10 +343,38 @@ def test_one_plane_slab_cap_falls_back_to_one_split(K):
             y = K.empty_cl(N, Ko, g.P, g.Q, pr.xd.device)
             d = g.desc(N, pr.xd.stride(), y.stride())
             wp = K._packed16(pr.wd, d, 0, g, dt)
-            K.check(K.lib.ctgan_conv2d16_fwd(ctypes.byref(d), MMA[dt], K._ptr(pr.xd), K._ptr(wp), K._ptr(pr.bd), None, K._ptr(y), 0, K._ptr(ws), nbytes,
-                                             K._stream()), 'conv2d16_fwd')
+            K.check(K.lib.ctgan_conv2d16_fwd(ctypes.byref(d), MMA[dt], K._ptr(pr.xd), K._ptr(wp), K._ptr(pr.bd), None, K._ptr(y), 0, None, K._ptr(ws),
+                                             nbytes, K._stream()), 'conv2d16_fwd')
             ran(K, *conv16_names(MMA[dt], T64K64, split, False))
             close16(y, pr.y, dt, True, 'fwd with %d B of workspace' % nbytes)
+
+
+def test_null_ext_and_an_ext_with_nothing_on_take_the_same_path(K):
+    """ctgan_conv2d16_fwd / ctgan_conv2d16_dgrad (bf16) with ext = NULL and with an ext that switches nothing on: the same kernel and the same
+    bits.  (The entry points that took no ext used to forward NULL to these; one entry per operation leaves the equivalence to this test.)"""
+    from ctgan_amd._lib import EpilogueExt
+    N, C, H, W, Ko, k = 2, 64, 8, 8, 64, 3
+    g = gen('null-ext')
+    geom = K.ConvGeom(C, H, W, Ko, k, k, 1, False)
+    x, gy = cl(torch.randn(N, C, H, W, generator=g)), cl(torch.randn(N, Ko, H, W, generator=g))
+    w = (torch.randn(k, k, C, Ko, generator=g) / np.sqrt(k * k * C)).to('cuda')
+    d = geom.desc(N, x.stride(), gy.stride())
+    wp = [K._packed16(w, d, op, geom, 'bf16') for op in (0, 1)]
+    nb = [K.lib.ctgan_conv2d16_workspace_bytes(ctypes.byref(d), op) for op in (0, 1)]
+    ws = torch.empty(max(nb + [16]), dtype=torch.uint8, device='cuda')
+    p, st, runs = K._ptr, K._stream(), []
+    for fill, e in ((1.0, None), (2.0, EpilogueExt(0.0, 0, 0, None))):
+        ext = None if e is None else ctypes.byref(e)
+        y, dx = K.empty_cl(N, Ko, H, W, x.device).fill_(fill), K.empty_cl(N, C, H, W, x.device).fill_(fill)
+        K.check(K.lib.ctgan_conv2d16_fwd(ctypes.byref(d), MMA['bf16'], p(x), p(wp[0]), None, None, p(y), 0, ext, p(ws), nb[0], st), 'conv2d16_fwd')
+        sym_fwd = K.last_symbol()
+        K.check(K.lib.ctgan_conv2d16_dgrad(ctypes.byref(d), MMA['bf16'], p(gy), p(wp[1]), None, None, None, p(dx), 0, ext, p(ws), nb[1], st),
+                'conv2d16_dgrad')
+        runs.append((y, sym_fwd, dx, K.last_symbol()))
+    (y0, sf0, dx0, sd0), (y1, sf1, dx1, sd1) = runs
+    print('fwd %s | dgrad %s' % (sf0, sd0))
+    assert sf0 == sf1 and sd0 == sd1 and sf0 and sd0
+    assert torch.equal(y0, y1) and torch.equal(dx0, dx1)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------ B

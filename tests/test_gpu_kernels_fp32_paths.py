@@ -429,6 +429,31 @@ def test_data_gradient_dropout_epilogue_and_its_fallback(K):
         close(got.cpu().double() * keep, ref * kept, 2e-5, 'dgrad dropout ' + ('NCHW fallback' if strides else 'vector epilogue'))
 
 
+def test_null_ext_and_an_ext_with_nothing_on_take_the_same_path(K):
+    """ctgan_conv2d_fwd / ctgan_conv2d_dgrad with ext = NULL and with an ext that switches nothing on: the same kernel and the same bits.  (The
+    entry points that took no ext used to forward NULL to these; one entry per operation leaves the equivalence to this test.)"""
+    import ctypes
+    from ctgan_amd._lib import EpilogueExt
+    N, C, H, W, Ko, k = 2, 32, 8, 8, 32, 3
+    g = gen('null-ext')
+    geom = K.ConvGeom(C, H, W, Ko, k, k, 1, False)
+    x, gy, w = cl(torch.randn(N, C, H, W, generator=g)), cl(torch.randn(N, Ko, H, W, generator=g)), dev(filt(g, k, C, Ko))
+    d = geom.desc(N, x.stride(), gy.stride())
+    ws = torch.empty(K.lib.ctgan_conv2d_workspace_bytes(ctypes.byref(d), 1), dtype=torch.uint8, device='cuda')
+    p, st, runs = K._ptr, K._stream(), []
+    for fill, e in ((1.0, None), (2.0, EpilogueExt(0.0, 0, 0, None))):
+        ext = None if e is None else ctypes.byref(e)
+        y, dx = K.empty_cl(N, Ko, H, W, x.device).fill_(fill), K.empty_cl(N, C, H, W, x.device).fill_(fill)
+        K.check(K.lib.ctgan_conv2d_fwd(ctypes.byref(d), p(x), p(w), None, None, p(y), 0, ext, st), 'conv2d_fwd')
+        sym_fwd = K.last_symbol()
+        K.check(K.lib.ctgan_conv2d_dgrad(ctypes.byref(d), p(gy), p(w), None, None, None, p(dx), p(ws), ws.numel(), 0, ext, st), 'conv2d_dgrad')
+        runs.append((y, sym_fwd, dx, K.last_symbol()))
+    (y0, sf0, dx0, sd0), (y1, sf1, dx1, sd1) = runs
+    print('fwd %s | dgrad %s' % (sf0, sd0))
+    assert sf0 == sf1 and sd0 == sd1 and sf0 and sd0
+    assert torch.equal(y0, y1) and torch.equal(dx0, dx1)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------ C
 # (N, C, H, W, Ko, k, tile): C % 32 == 0 and Ko % 4 == 0, so that every loader combination can run the same values
 TILE_CASES = [

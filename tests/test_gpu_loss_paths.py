@@ -104,7 +104,7 @@ def test_tail_critic_heads(be, B, nf, H, W, ncls):
 @pytest.mark.parametrize('clean_relu', [False, True])
 @pytest.mark.parametrize('B,nf,H,W,ncls', C.TAIL_CRITIC_CASES)
 def test_clean_rows_of_the_folded_forward(K, be, B, nf, H, W, ncls, clean_relu):
-    """ctgan_tail_critic_heads_fwd2 through the C ABI: the wrapper keeps only the two accuracies of the clean pass, and an accuracy over a few
+    """ctgan_tail_critic_heads_fwd with the clean rows, through the C ABI: the wrapper keeps only the two accuracies of the clean pass, and an accuracy over a few
     rows does not move when the logits are slightly wrong.  Here f_clean and a_clean themselves are compared with fp64, for clean_relu off and
     on, next to main rows that hold negative values (they are averaged as they are: `relu` and `relu2` must not be swapped)."""
     from ctgan_amd._lib import check, lib
@@ -120,9 +120,9 @@ def test_clean_rows_of_the_folded_forward(K, be, B, nf, H, W, ncls, clean_relu):
     f_c, a_c, acc = new(2 * B, nf), new(2 * B, ncls), new(2)
     ins = [be.cl(y), be.dev(w_out), be.dev(b_out), be.dev(w_ac), be.dev(b_ac), be.dev(lab), be.cl(yc)]
     p = K._ptr
-    check(lib.ctgan_tail_critic_heads_fwd2(p(ins[0]), B, H * W, nf, p(ins[1]), p(ins[2]), p(ins[3]), p(ins[4]), ncls, p(ins[5]), None, None, 0.0,
-                                           p(ins[6]), 1 if clean_relu else 0, p(f_c), p(a_c), p(acc), 2.0, 0.0, 1.0, p(f), p(d), p(a), p(ct_i),
-                                           p(probs), p(ce_i), p(out), K._stream()), 'tail_critic_heads_fwd2')
+    check(lib.ctgan_tail_critic_heads_fwd(p(ins[0]), B, H * W, nf, p(ins[1]), p(ins[2]), p(ins[3]), p(ins[4]), ncls, p(ins[5]), None, None, 0.0,
+                                          p(ins[6]), 1 if clean_relu else 0, p(f_c), p(a_c), p(acc), 2.0, 0.0, 1.0, p(f), p(d), p(a), p(ct_i),
+                                          p(probs), p(ce_i), p(out), K._stream()), 'tail_critic_heads_fwd')
     C.close('tail_heads fwd f', f_c, f_c_ref, C.FWD_TOL)
     C.close('tail_heads fwd d, a', a_c, a_c_ref, C.DOT_TOL)
     C.close('tail_heads fwd f', f, f_ref, C.FWD_TOL)
@@ -188,9 +188,9 @@ def _refusals(K):
         tail = [2.0, 0.0, 1.0] + [p(o) for o in outs] + [st]
         if slopes or clean:
             mid = [p(rnd(1)) if slopes else None, 10.0, p(rnd(2 * hw * nf)) if clean else None, 0] + [p(o) for o in extra]
-            R['tail_critic_heads_fwd2 ' + name] = ('ctgan_tail_critic_heads_fwd2', head + mid + tail, outs + extra)
+            R['tail_critic_heads_fwd (folded) ' + name] = ('ctgan_tail_critic_heads_fwd', head + mid + tail, outs + extra)
         else:
-            R['tail_critic_heads_fwd ' + name] = ('ctgan_tail_critic_heads_fwd', head + tail, outs)
+            R['tail_critic_heads_fwd ' + name] = ('ctgan_tail_critic_heads_fwd', head + [None, 0.0, None, 0, None, None, None] + tail, outs)
 
     def gen_fwd(name, nf, off=0, n=2):
         outs = [sent(2 * nf), sent(2), sent(2 * ncls), sent(2 * ncls), sent(1)]          # f, d, a, probs, out
@@ -205,7 +205,7 @@ def _refusals(K):
     def tail_bwd(name, nf=8, off=0, gy_off=0, n_gout=4, B=1, n_gp=0, gp_off=0, w_off=0):
         gy = sent(3 * hw * nf)[gy_off:]
         outs = [gy, sent(nf), sent(1), sent(nf * ncls), sent(ncls), sent(max(n_gp, 1) * hw * nf)]       # gy, gw_out, gb_out, gw_ac, gb_ac, gz_gp
-        R['tail_heads_bwd ' + name] = ('ctgan_tail_heads_bwd_gp',
+        R['tail_heads_bwd ' + name] = ('ctgan_tail_heads_bwd',
                                        [p(rnd(3 * hw * nf, off)), p(rnd(3)), p(rnd(3 * nf)), p(rnd(ncls)), p(lab), p(rnd(1)), p(rnd(4)), n_gout, B, hw, nf,
                                         ncls, 2.0, 0.0, 1.0, 2.0, p(rnd(nf, w_off)), p(rnd(nf * ncls))] + [p(o) for o in outs[:5]] +
                                        [p(rnd(max(n_gp, 1) * hw * nf, gp_off)) if n_gp else None, n_gp, p(outs[5]) if n_gp else None, st], outs)
@@ -215,9 +215,10 @@ def _refusals(K):
         R['gp_head_grad ' + name] = ('ctgan_gp_head_grad', [p(rnd(2 * nf, off)), p(rnd(nf, w_off)), n, hw, nf, 2.0, p(gz), st], [gz])
 
     def head_wgrad(name, nf=8, off=0, gg_off=0, ws_off=0, n=2):
-        for fn in ('ctgan_gp_head_wgrad', 'ctgan_gp_head_wgrad_acc'):
+        for acc in (0, 1):
             gw, ws = sent(nf), sent(64 * nf)[ws_off:]
-            R['%s %s' % (fn[6:], name)] = (fn, [p(rnd(2 * hw * nf, gg_off)), p(rnd(2 * hw * nf, off)), n, hw, nf, 2.0, p(gw), p(ws), st], [gw, ws])
+            R['gp_head_wgrad%s %s' % (' (accumulating)' if acc else '', name)] = (
+                'ctgan_gp_head_wgrad', [p(rnd(2 * hw * nf, gg_off)), p(rnd(2 * hw * nf, off)), n, hw, nf, 2.0, p(gw), p(ws), acc, st], [gw, ws])
 
     def finish(name, B, Cn, H, W):
         ga, sl = sent(max(B, 1) * Cn * H * W), sent(max(B, 1))

@@ -416,7 +416,7 @@ def test_hand_scheduled_critic_step_equals_the_autograd_path_on_gpu(setup, dim, 
 
 @pytest.mark.parametrize('split_mode', [True, False])
 def test_data_gradient_with_per_range_dropout_masks_equals_one_dropout_per_range(split_mode):
-    """ctgan_conv2d16_dgrad_ex / ctgan_conv2d_dgrad_ex with sample ranges (round 5: the merged backward carries the rows of the dropout
+    """ctgan_conv2d16_dgrad / ctgan_conv2d_dgrad with sample ranges (round 5: the merged backward carries the rows of the dropout
     passes and of the penalty pass in one data gradient, each range with the mask of its own forward dropout): the epilogue form
     against the plain data gradient followed by ctgan_dropout_rng on each range's own rows - same Philox draws, bit for bit."""
     import ctgan_amd.kernels as K

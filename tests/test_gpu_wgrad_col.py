@@ -158,7 +158,7 @@ def _q16(t, dt):
 def test_column_kernel_in_the_16bit_modes_is_exact_on_representable_operands(K, dt, case):
     """bf16 / fp16 modes (BASELINE configs[1] / [4]): one rounded plane per operand, 64-pixel slices.  With operands that are representable in
     the 16-bit format every product is exact in fp32, so the kernel must agree with the fp64 oracle to fp32 summation error - any
-    indexing / ring / polyphase / transposition mistake shows at full size.  Through the single-problem entry (ctgan_conv2d16_wgrad_bias),
+    indexing / ring / polyphase / transposition mistake shows at full size.  Through the single-problem entry (ctgan_conv2d16_wgrad),
     which routes to the filter-column kernel."""
     N, C, H, Ko, k, st = case
     gen = torch.Generator().manual_seed(N * 7 + H)
