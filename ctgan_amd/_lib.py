@@ -257,6 +257,10 @@ SIGNATURES = {
     'ctgan_score_finish': (c_int, [_p, c_int64, c_int32, c_int32, _p, _p]),
     # feature moments of the classifier Frechet distance (csrc/moments.hip)
     'ctgan_moments_accum': (c_int, [_p, c_int64, c_int32, _p, _p, _p]),
+    # ... per class of a label column, and the confusion matrix of the same pass
+    'ctgan_class_moments_max_rows': (c_int, []),
+    'ctgan_class_moments_accum': (c_int, [_p, _p, c_int64, c_int32, c_int32, _p, _p, _p, _p]),
+    'ctgan_confusion_accum': (c_int, [_p, _p, c_int64, c_int32, _p, _p]),
     # k-nearest-neighbour manifold estimate: precision and recall (csrc/knn.hip)
     'ctgan_knn_max_k': (c_int, []),
     'ctgan_knn_radii': (c_int, [_p, c_int64, c_int32, c_int32, _p, _p]),

@@ -4,6 +4,7 @@
 //   mean_i sum_j p_ij (log p_ij - log m_j) = (1/n) sum_i sum_j p_ij log p_ij - sum_j m_j log m_j,   m = mean_i p_i
 //   reductions: per-thread fp64 partials, an LDS tree in a fixed order, one thread adds to the caller's state with plain loads and
 //   stores; no float atomics - the same bits on every run.  The class counts are integers (LDS / global integer adds: exact in any order).
+#include "argmax.h"
 #include "common.h"
 #include "pixel_u8.h"
 
@@ -45,12 +46,8 @@ __global__ __launch_bounds__(TPB) void score_accum_kernel(const float* __restric
     for (int j = 0; j < KMAX + GRP; ++j) s[j] = 0.;
     for (long long row = a + tid; row < b; row += TPB) {
         const float* z = logits + row * K;
-        float best = z[0];                               // numpy.argmax: the first maximum, a NaN counting as one
-        int arg = 0;
-        for (int j = 1; j < K; ++j) {
-            const float v = z[j];
-            if (!(best != best) && (v > best || v != v)) { best = v; arg = j; }
-        }
+        float best;
+        const int arg = ctgan_argmax_first(z, K, best);  // numpy.argmax: the first maximum, a NaN counting as one
         const double mx = (double)best;
         double se = 0.;
         for (int j = 0; j < K; ++j) se += exp((double)z[j] - mx);

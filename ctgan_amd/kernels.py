@@ -2622,6 +2622,45 @@ def moments_accum(feat, s1, s2):
     check(lib.ctgan_moments_accum(_ptr(feat), m, d, _ptr(s1), _ptr(s2), _stream()), 'moments_accum')
 
 
+CLASS_MOMENTS_MAX_ROWS = lib.ctgan_class_moments_max_rows()
+
+
+def _class_state(*tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % t.device)
+        assert t.is_contiguous(), 'contiguous state expected'
+
+
+def class_moments_accum(feat, labels, cnt, s1, s2):
+    """moments_accum per class of a label column, in one launch: feat fp32 [m, D], labels int32 [m]; state cnt int64 [K] (rows per class),
+    s1 fp64 [K, D], s2 fp64 [K, D, D], zeroed by the caller before the first chunk, in place.  The state of class c receives what
+    moments_accum adds from feat[labels == c] (the same bits); a label outside [0, K) adds to nothing.  K <= 32, D <= 1024; a chunk
+    longer than CLASS_MOMENTS_MAX_ROWS goes in successive calls of at most that many rows."""
+    _need_dev(feat, labels)
+    m, d = _rows2d(feat)
+    _class_state(cnt, s1, s2)
+    assert s1.dtype == torch.float64 and s2.dtype == torch.float64 and cnt.dtype == torch.int64, 'fp64 moments and int64 counts expected'
+    nc = cnt.numel()
+    assert cnt.dim() == 1 and tuple(s1.shape) == (nc, d) and tuple(s2.shape) == (nc, d, d), 'cnt [K], s1 [K, D], s2 [K, D, D] expected'
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (m,), 'int32 labels [m] expected'
+    for r0 in range(0, max(m, 1), CLASS_MOMENTS_MAX_ROWS):
+        r1 = min(r0 + CLASS_MOMENTS_MAX_ROWS, m)
+        check(lib.ctgan_class_moments_accum(_ptr(feat[r0:r1]), _ptr(labels[r0:r1]), r1 - r0, d, nc, _ptr(cnt), _ptr(s1), _ptr(s2), _stream()),
+              'class_moments_accum')
+
+
+def confusion_accum(logits, labels, conf):
+    """conf[labels[i], argmax(logits[i])] += 1 (score_accum's argmax: the first maximum) over logits fp32 [m, K], labels int32 [m], into
+    conf int64 [K, K] zeroed by the caller, in place; a row with a label outside [0, K) is ignored.  K <= 32."""
+    _need_dev(logits, labels)
+    m, nc = _rows2d(logits)
+    _class_state(conf)
+    assert conf.dtype == torch.int64 and tuple(conf.shape) == (nc, nc), 'int64 conf [K, K] expected'
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (m,), 'int32 labels [m] expected'
+    check(lib.ctgan_confusion_accum(_ptr(logits), _ptr(labels), m, nc, _ptr(conf), _stream()), 'confusion_accum')
+
+
 # ---------------------------------------------------------------- k-nearest-neighbour manifold estimate (csrc/knn.hip)
 KNN_MAX_K = lib.ctgan_knn_max_k()
 

@@ -45,6 +45,19 @@ some sample's ball, and the memorisation signal: `'nn_dist'`, the median distanc
     counts and the median                  reduced on the device, in the scoring's one device -> host copy
 Classifier statistics again: a manifold estimate under a self-trained 10-class network's 128 features, NOT comparable to published
 precision / recall (VGG-16 or Inception features).  A FeatureSet records the classifier's hash as a FeatureStatistics does.
+
+Per-class statistics.  The headline generator is class-conditional, and every statistic above pools its ten classes: a collapse inside
+one class, or good images under the wrong label, hardly moves them.  With a class reference set (`class_reference=` /
+`set_class_reference`, a ClassStatistics: one Gaussian fit per label, `class_statistics` of the labelled training images, once),
+`score` with labels and `score_generator` of a conditional generator also return `'frechet_class'` [K], the Frechet distance per
+conditioned label, `'intra_frechet'`, its mean, `'n_class'` [K], `'confusion'` [K, K] (conditioned label x predicted class) and
+`'acc_class'` [K], its diagonal over its row sums.
+    features [m, D], labels [m] -> raw moments per class   kernels.class_moments_accum   one launch per chunk: every workgroup compacts
+                                                           its class's rows and runs moments_accum's loop over them (the same bits)
+    logits [m, K], labels [m] -> confusion matrix          kernels.confusion_accum       one launch per chunk, integer counters
+    moments -> fits -> distances                           ClassStatistics, intra_frechet  on the host, from the one device -> host copy
+Samples without labels are refused before any launch; a label outside [0, K) shows in the counts and is refused after the copy.  Again
+classifier statistics under a self-trained 10-class network: NOT comparable to published intra-FID numbers.
 """
 import hashlib
 import os
@@ -114,6 +127,94 @@ def frechet_distance(a, b):
     lam = np.linalg.eigvalsh((prod + prod.T) / 2)
     diff = a.mean - b.mean
     return float(diff @ diff + np.trace(a.cov) + np.trace(b.cov) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
+
+
+class ClassStatistics:
+    """The Gaussian fits of a feature layer per class label: `n` int64 [K] rows per class, `mean` fp64 [K, D], `cov` fp64 [K, D, D]
+    (unbiased), and `classifier` as FeatureStatistics records it.  A class with fewer than 2 rows has a NaN covariance, an empty one a
+    NaN mean too.  The raw moments are not kept: `pooled` rebuilds them per class from the fit, s1 = n mean and
+    s2 = (n - 1) cov + n mean mean^T, each within a few roundings (under 8 2^-53 (|s2| + n |mean| |mean|^T) elementwise) of the sums
+    the fit was made from - below the summation error n 2^-52 |F|^T |F| those sums are known to once a class has a handful of rows."""
+
+    def __init__(self, n, mean, cov, classifier=None):
+        self.n = np.ascontiguousarray(n, dtype=np.int64).reshape(-1)
+        self.mean = np.ascontiguousarray(mean, dtype=np.float64)
+        self.cov = np.ascontiguousarray(cov, dtype=np.float64)
+        self.classifier = None if classifier is None else str(classifier)
+        k = self.n.size
+        if k < 1 or (self.n < 0).any() or self.mean.ndim != 2 or self.mean.shape[0] != k or self.cov.shape != (k, self.mean.shape[1], self.mean.shape[1]):
+            raise ValueError('ClassStatistics: n %s, mean %s, cov %s' % (self.n.shape, self.mean.shape, self.cov.shape))
+
+    @property
+    def classes(self):
+        return self.n.size
+
+    @property
+    def width(self):
+        return self.mean.shape[1]
+
+    @classmethod
+    def from_moments(cls, cnt, s1, s2, classifier=None):
+        """From the per-class raw moments kernels.class_moments_accum leaves (cnt [K], s1 [K, D], s2 [K, D, D]):
+        FeatureStatistics.from_moments per class; NaN where a class has too few rows."""
+        cnt = np.asarray(cnt, dtype=np.int64).reshape(-1)
+        s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+        mean, cov = np.full(s1.shape, np.nan), np.full(s2.shape, np.nan)
+        for c in range(cnt.size):
+            if cnt[c] > 0:
+                fit = FeatureStatistics.from_moments(int(cnt[c]), s1[c], s2[c])
+                mean[c], cov[c] = fit.mean, fit.cov
+        return cls(cnt, mean, cov, classifier)
+
+    def of(self, c):
+        """The FeatureStatistics of class `c` (which must have at least one row)."""
+        if self.n[c] < 1:
+            raise ValueError('ClassStatistics: class %d has no rows' % c)
+        return FeatureStatistics(int(self.n[c]), self.mean[c], self.cov[c], self.classifier)
+
+    def pooled(self):
+        """The FeatureStatistics of all counted rows together, from the sum over the classes of the rebuilt raw moments."""
+        d = self.width
+        s1, s2 = np.zeros(d), np.zeros((d, d))
+        for c in range(self.classes):
+            nc = int(self.n[c])
+            if nc > 0:
+                outer = nc * np.outer(self.mean[c], self.mean[c])
+                s1 += nc * self.mean[c]
+                s2 += outer if nc == 1 else (nc - 1) * self.cov[c] + outer
+        total = int(self.n.sum())
+        if total < 1:
+            raise ValueError('ClassStatistics: no rows')
+        return FeatureStatistics.from_moments(total, s1, s2, self.classifier)
+
+    def save(self, path):
+        """-> `path` (numpy .npz; the name is taken as given)."""
+        with open(path, 'wb') as f:
+            np.savez(f, n=self.n, mean=self.mean, cov=self.cov, classifier=np.str_(self.classifier or ''))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(z['n'], z['mean'], z['cov'], str(z['classifier']) or None)
+
+
+def intra_frechet(a, b):
+    """The per-class Frechet distance between two ClassStatistics -> {'frechet_class': fp64 [K], frechet_distance(a.of(c), b.of(c)), NaN
+    where either side has fewer than 2 rows of class c; 'intra_frechet': its mean over the classes that are not NaN}.  Different class
+    counts, widths or recorded classifiers raise, and so does a pair without a class of 2 rows on both sides."""
+    if a.classes != b.classes:
+        raise ValueError('intra_frechet: %d and %d classes' % (a.classes, b.classes))
+    if a.width != b.width:
+        raise ValueError('intra_frechet: %d and %d features' % (a.width, b.width))
+    if a.classifier is not None and b.classifier is not None and a.classifier != b.classifier:
+        raise ValueError('intra_frechet: the two statistics were computed under different classifiers')
+    dist = np.full(a.classes, np.nan)
+    for c in range(a.classes):
+        if a.n[c] >= 2 and b.n[c] >= 2:
+            dist[c] = frechet_distance(a.of(c), b.of(c))
+    if np.isnan(dist).all():
+        raise ValueError('intra_frechet: no class has 2 rows on both sides')
+    return {'frechet_class': dist, 'intra_frechet': float(np.nanmean(dist))}
 
 
 class FeatureSet:
@@ -232,10 +333,12 @@ class ClassifierScore:
     reference: a FeatureStatistics, or the path of a saved one (see set_reference): `score` and `score_generator` then also return
     the classifier Frechet distance to it, `'frechet'`.
     manifold: a FeatureSet, or the path of a saved one (see set_manifold), manifold_k: the neighbour count: `score` and `score_generator`
-    then also return `'precision'`, `'recall'`, `'nn_dist'` and `'nn_zero'` against it (precision_recall)."""
+    then also return `'precision'`, `'recall'`, `'nn_dist'` and `'nn_zero'` against it (precision_recall).
+    class_reference: a ClassStatistics, or the path of a saved one (see set_class_reference): `score` (with labels) and `score_generator`
+    (of a conditional generator) then also return `'frechet_class'`, `'intra_frechet'`, `'n_class'`, `'confusion'` and `'acc_class'`."""
 
     def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, manifold=None, manifold_k=3,
-                 **train_kw):
+                 class_reference=None, **train_kw):
         if (trainer is None) == (weights is None):
             raise ValueError('ClassifierScore: pass a trainer or weights=PATH')
         self.trainer = trainer
@@ -259,6 +362,9 @@ class ClassifierScore:
         self.manifold, self.manifold_k = None, int(manifold_k)
         if manifold is not None:
             self.set_manifold(manifold, manifold_k)
+        self.class_reference = None
+        if class_reference is not None:
+            self.set_class_reference(class_reference)
 
     # ---- construction
     @staticmethod
@@ -337,6 +443,29 @@ class ClassifierScore:
             self._check_reference(ref)
         self.reference = ref
 
+    # ---- the reference of the per-class Frechet distance
+    def _check_class_reference(self, ref):
+        if ref.classifier is None:
+            raise ValueError('ClassifierScore: the class reference statistics do not record the classifier they were computed under')
+        if ref.classifier != self.fingerprint():
+            raise ValueError('ClassifierScore: the class reference statistics were computed under another classifier (%s..., this one is %s...)'
+                             % (ref.classifier[:12], self.fingerprint()[:12]))
+        if ref.width != self.cfg.D_WIDTHS[-1]:
+            raise ValueError('ClassifierScore: %d class reference features, %d in the classifier' % (ref.width, self.cfg.D_WIDTHS[-1]))
+        if ref.classes != self.cfg.N_CLASSES:
+            raise ValueError('ClassifierScore: %d reference classes, %d in the classifier' % (ref.classes, self.cfg.N_CLASSES))
+
+    def set_class_reference(self, stats_or_path):
+        """The ClassStatistics (or the path of a saved one; None: none) that `score` / `score_generator` measure the per-class Frechet
+        distance to.  It must have been computed under this classifier's averaged parameters, at its width and class count - checked
+        here and again at every scoring."""
+        ref = stats_or_path
+        if ref is not None and not isinstance(ref, ClassStatistics):
+            ref = ClassStatistics.load(ref)
+        if ref is not None:
+            self._check_class_reference(ref)
+        self.class_reference = ref
+
     # ---- the manifold of precision and recall
     def _check_manifold(self, ref):
         if ref.classifier is None:
@@ -398,14 +527,39 @@ class ClassifierScore:
         buf = torch.zeros(d + d * d, dtype=torch.float64, device=self.dev)
         return buf, buf[:d], buf[d:].view(d, d)
 
+    def _begin_class_moments(self):
+        """The caller-owned state of kernels.class_moments_accum and kernels.confusion_accum: cnt [K] and conf [K, K] as views of one zeroed
+        int64 buffer, s1 [K, D] and s2 [K, D, D] as views of one zeroed fp64 buffer."""
+        k, d = self.cfg.N_CLASSES, self.cfg.D_WIDTHS[-1]
+        ints = torch.zeros(k + k * k, dtype=torch.int64, device=self.dev)
+        mom = torch.zeros(k * d + k * d * d, dtype=torch.float64, device=self.dev)
+        return {'ints': ints, 'cnt': ints[:k], 'conf': ints[k:].view(k, k), 'mom': mom, 's1': mom[:k * d].view(k, d), 's2': mom[k * d:].view(k, d, d)}
+
+    def _begin_class(self, with_labels, what):
+        if self.class_reference is None:
+            return None
+        if not with_labels:
+            raise ValueError('ClassifierScore.%s: a class reference is set and the samples have no labels' % what)
+        self._check_class_reference(self.class_reference)
+        return self._begin_class_moments()
+
+    def _class_statistics(self, host_cnt, host_mom, n):
+        k, d = self.cfg.N_CLASSES, self.cfg.D_WIDTHS[-1]
+        cnt = np.asarray(host_cnt).astype(np.int64)
+        if int(cnt.sum()) != n:
+            raise ValueError('ClassifierScore: %d of %d rows have a label in [0, %d)' % (int(cnt.sum()), n, k))
+        return ClassStatistics.from_moments(cnt, host_mom[:k * d].reshape(k, d), host_mom[k * d:].reshape(k, d, d), self.fingerprint())
+
     def _statistics(self, host, n):
         d = self.cfg.D_WIDTHS[-1]
         return FeatureStatistics.from_moments(n, host[:d], host[d:].reshape(d, d), self.fingerprint())
 
-    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None):
+    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None, cls=None):
         nc = self.cfg.N_CLASSES
         out = K.score_finish(acc, n, splits)
         parts = [out, cnt.to(torch.float64)] + ([] if moments is None else [moments])
+        if cls is not None:
+            parts += [cls['ints'].to(torch.float64), cls['mom']]
         if man is not None:                                  # three launches over all n samples, once, after the last chunk
             parts.append(_manifold_counts(man['feat'], self.manifold, self.manifold_k))
         host = torch.cat(parts).cpu().numpy()                # the scoring's one device -> host copy (counts < 2^53: exact)
@@ -414,17 +568,30 @@ class ClassifierScore:
                'acc': float(counts[nc:].sum()) / n if with_labels else None}
         if moments is not None:
             res['frechet'] = frechet_distance(self._statistics(host[2 + splits + 2 * nc:2 + splits + 2 * nc + moments.numel()], n), self.reference)
+        if cls is not None:
+            at = 2 + splits + 2 * nc + (0 if moments is None else moments.numel())
+            ints = host[at:at + nc + nc * nc].astype(np.int64)
+            stats = self._class_statistics(ints[:nc], host[at + nc + nc * nc:at + nc + nc * nc + cls['mom'].numel()], n)
+            res.update(intra_frechet(stats, self.class_reference))
+            conf = ints[nc:].reshape(nc, nc)
+            rows = conf.sum(axis=1)
+            res.update({'n_class': stats.n.copy(), 'confusion': conf,
+                        'acc_class': np.where(rows > 0, np.diag(conf) / np.maximum(rows, 1), np.nan)})
         if man is not None:
             res.update(_manifold_result(host[-5:], n, self.manifold.n, self.manifold_k))
             del res['k']
         return res
 
-    def _score_chunk(self, x, mom, man=None, r0=0):
+    def _score_chunk(self, x, mom, man=None, r0=0, cls=None, lab=None):
         """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it; with
-        the state of one that has a manifold, they are copied to rows r0.. of its buffer."""
-        if mom is None and man is None:
+        the state of one that has a manifold, they are copied to rows r0.. of its buffer; with the state of one that has a class reference,
+        the features go into the state of their label `lab` and the logits into the confusion matrix."""
+        if mom is None and man is None and cls is None:
             return self._logits(x)
         logits, feat = self._forward(x, True)
+        if cls is not None:
+            K.class_moments_accum(feat, lab, cls['cnt'], cls['s1'], cls['s2'])
+            K.confusion_accum(logits, lab, cls['conf'])
         if mom is not None:
             K.moments_accum(feat, mom[1], mom[2])
         if man is not None:
@@ -468,6 +635,7 @@ class ClassifierScore:
             raise ValueError('ClassifierScore.score: uint8 [N, %d, %d, %d] images expected (got %s %s)'
                              % (cfg.CHANNELS, cfg.IMG, cfg.IMG, data.dtype, tuple(data.shape)))
         n = data.shape[0]
+        cls = self._begin_class(labels is not None, 'score')
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
@@ -479,9 +647,10 @@ class ClassifierScore:
         for r0 in range(0, n, chunk):
             m = min(chunk, n - r0)
             idx = torch.arange(r0, r0 + m, dtype=torch.int32, device=self.dev)
-            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0)
-            K.score_accum(logits, r0, n, splits, acc, cnt, None if labels is None else labels[r0:r0 + m])
-        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man)
+            lab = None if labels is None else labels[r0:r0 + m]
+            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0, cls, lab)
+            K.score_accum(logits, r0, n, splits, acc, cnt, lab)
+        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls)
 
     def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
@@ -492,17 +661,19 @@ class ClassifierScore:
         features of the same classifier passes."""
         ev, scale = self._evaluator(gan_trainer, 'score_generator')
         cfg = self.cfg
+        cls = self._begin_class(ev.resnet, 'score_generator')      # (only the ResNet's generator is conditional: score_draws yields its labels)
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
         labels = self._labels(labels, n)
         r0, with_labels = 0, False
         for x, lab in ev.score_draws(n, labels, chunk):
-            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0)
-            K.score_accum(logits, r0, n, splits, acc, cnt, None if lab is None else lab.contiguous())
+            lab = None if lab is None else lab.contiguous()
+            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab)
+            K.score_accum(logits, r0, n, splits, acc, cnt, lab)
             with_labels = lab is not None
             r0 += x.shape[0]
-        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man)
+        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man, cls)
 
     def _evaluator(self, gan_trainer, what):
         from . import evaluate
@@ -544,6 +715,45 @@ class ClassifierScore:
         for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
             K.moments_accum(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1], s1, s2)
         return self._statistics(buf.cpu().numpy(), n)
+
+    # ---- the per-class feature statistics alone
+    def class_statistics(self, images_u8, labels, chunk=None):
+        """The ClassStatistics of a labelled uint8 set [N, CHANNELS, IMG, IMG], labels [N] in [0, N_CLASSES), read exactly as `statistics`
+        reads it: what a class reference is made of (the labelled training images, once; `.save(path)` keeps it)."""
+        cfg = self.cfg
+        data = torch.as_tensor(images_u8)
+        if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
+            raise ValueError('ClassifierScore.class_statistics: uint8 [N, %d, %d, %d] images expected (got %s %s)'
+                             % (cfg.CHANNELS, cfg.IMG, cfg.IMG, data.dtype, tuple(data.shape)))
+        n = data.shape[0]
+        if n < 1 or labels is None:
+            raise ValueError('ClassifierScore.class_statistics: no images, or no labels')
+        labels = self._labels(labels, n)
+        st = self._begin_class_moments()
+        data = data.to(self.dev).contiguous()
+        chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError('ClassifierScore.class_statistics: chunk must be positive')
+        for r0 in range(0, n, chunk):
+            idx = torch.arange(r0, min(r0 + chunk, n), dtype=torch.int32, device=self.dev)
+            feat = self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1]
+            K.class_moments_accum(feat, labels[r0:r0 + chunk], st['cnt'], st['s1'], st['s2'])
+        return self._class_statistics(st['cnt'].cpu().numpy(), st['mom'].cpu().numpy(), n)
+
+    def class_statistics_generator(self, gan_trainer, n, labels=None, chunk=None):
+        """The ClassStatistics of `n` samples of a conditional generator under the labels they were generated from, drawn and quantised
+        exactly as `statistics_generator` draws them (the evaluation stream; the training stream, the weights and the optimizers stay
+        untouched).  An unconditional generator's samples have no labels: ValueError."""
+        ev, scale = self._evaluator(gan_trainer, 'class_statistics_generator')
+        if n < 1:
+            raise ValueError('ClassifierScore.class_statistics_generator: no samples')
+        if not ev.resnet:
+            raise ValueError('ClassifierScore.class_statistics_generator: %s samples have no labels' % ev.name)
+        st = self._begin_class_moments()
+        for x, lab in ev.score_draws(n, self._labels(labels, n), chunk):
+            feat = self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1]
+            K.class_moments_accum(feat, lab.contiguous(), st['cnt'], st['s1'], st['s2'])
+        return self._class_statistics(st['cnt'].cpu().numpy(), st['mom'].cpu().numpy(), n)
 
     # ---- the features themselves
     def features(self, images_u8, chunk=None):

@@ -853,6 +853,23 @@ int ctgan_score_finish(const double* acc, int64_t n, int32_t splits, int32_t cla
  * has one owning workgroup, which adds with a plain load and store (no atomics): the same chunking gives the same bits, and s2 is
  * exactly symmetric.  m == 0: nothing is launched.  d > 1024: CTGAN_E_UNSUPPORTED, nothing is launched.                          */
 int ctgan_moments_accum(const float* f, int64_t m, int32_t d, double* s1, double* s2, ctgan_stream_t stream);
+/* The same moments segmented by a label column, for the per-class Frechet distance of score_cifar.py: labels int32 [m]; caller-owned,
+ * caller-zeroed state cnt int64 [classes], s1 double [classes, d], s2 double [classes, d, d], 8-byte aligned.  With R_c the chunk's
+ * rows of label c in ascending row order: cnt[c] += |R_c|, s1[c] += sum f_i, s2[c] += sum f_i f_i^T over R_c.  A label outside
+ * [0, classes) belongs to no class and adds to nothing (the caller sees it in cnt).  One launch, grid (tile pairs, classes): every
+ * workgroup compacts its class's rows into an LDS list (wave ballots, a prefix over the waves: stable), then runs the loop of
+ * ctgan_moments_accum through the list - one body, a row indirection the only difference.  Contract: after a call the state of
+ * class c holds the bits ctgan_moments_accum leaves from the [|R_c|, d] array of those rows gathered in order; an absent class's
+ * state is not touched.  No atomics, one owner per state element.  m == 0: nothing is launched.
+ * m > ctgan_class_moments_max_rows() (8192, the LDS list), classes > 32 or d > 1024: CTGAN_E_UNSUPPORTED, nothing is launched.    */
+int ctgan_class_moments_max_rows(void);
+int ctgan_class_moments_accum(const float* f, const int32_t* labels, int64_t m, int32_t d, int32_t classes, int64_t* cnt, double* s1,
+                              double* s2, ctgan_stream_t stream);
+/* conf[labels[i], argmax(logits[i, :])] += 1 over logits fp32 [m, classes], labels int32 [m], into the caller-owned, caller-zeroed
+ * conf int64 [classes, classes] (conditioned label x predicted class).  The argmax is ctgan_score_accum's (first maximum, as
+ * numpy.argmax); a row with a label outside [0, classes) is ignored.  LDS integer counters per workgroup, then integer adds: exact
+ * in any order.  m == 0: nothing is launched.  classes > 32: CTGAN_E_UNSUPPORTED, nothing is launched.                           */
+int ctgan_confusion_accum(const float* logits, const int32_t* labels, int64_t m, int32_t classes, int64_t* conf, ctgan_stream_t stream);
 /* The k-nearest-neighbour manifold estimate in a feature space (csrc/knn.hip), for the precision and recall of score_cifar.py.  The
  * squared distance is d2(i, j) = max(0, |a_i|^2 + |b_j|^2 - 2 a_i . b_j), every term in fp64 over the fp32 features widened exactly; the
  * dot products and both norms run on v_mfma_f64_16x16x4_f64 through the same k-ordered chain, so two bit-identical rows are at

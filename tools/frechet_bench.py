@@ -11,7 +11,7 @@ A figure is the median (and min / max) of `--runs` scorings after `--warmup` unt
 device synchronise; the two alternate run by run and score the same samples (the evaluation stream's counter is put back before each
 scoring; the score keys of the two must be equal).  Also timed: building the one-off reference over `--reference-rows` uint8 images
 (ClassifierScore.statistics; from a host array, and from a tensor already on the device), the host-side distance alone, and
-kernels.moments_accum per launch at `--shapes` (device events around `--launches` back-to-back launches; the kernel's own time comes from
+kernels.moments_accum and kernels.class_moments_accum (`--classes` uniformly random labels) per launch at `--shapes` (device events around `--launches` back-to-back launches; the kernel's own time comes from
 a rocprofv3 --kernel-trace run of this tool with --kernel-only).  Prints one JSON line; --out writes it to a file.
 
     python tools/frechet_bench.py [--out profiles/frechet_bench.json]
@@ -64,6 +64,29 @@ def kernel_times(shapes, launches):
     return out
 
 
+def class_kernel_times(shapes, classes, launches):
+    """kernels.class_moments_accum per launch over uniformly random labels of `classes` classes, microseconds, as kernel_times."""
+    import ctgan_amd.kernels as K
+    out = {}
+    for m, d in shapes:
+        f = torch.randn(m, d, device='cuda')
+        lab = torch.randint(0, classes, (m,), device='cuda', dtype=torch.int32)
+        cnt = torch.zeros(classes, dtype=torch.int64, device='cuda')
+        s1 = torch.zeros(classes, d, dtype=torch.float64, device='cuda')
+        s2 = torch.zeros(classes, d, d, dtype=torch.float64, device='cuda')
+        for _ in range(10):
+            K.class_moments_accum(f, lab, cnt, s1, s2)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            K.class_moments_accum(f, lab, cnt, s1, s2)
+        b.record()
+        torch.cuda.synchronize()
+        out['%dx%dx%d' % (m, d, classes)] = {'us_per_launch': a.elapsed_time(b) * 1e3 / launches, 'launches': launches,
+                                             'workgroups': ((d + 15) // 16) * ((d + 15) // 16 + 1) // 2 * classes}
+    return out
+
+
 def measure(name, n, scorer, reference, dev, runs, warmup):
     from ctgan_amd import evaluate
     mod, gan = B.gan_trainer(name, dev)
@@ -98,6 +121,7 @@ def main():
     ap.add_argument('--reference-rows', type=int, default=50000)
     ap.add_argument('--launches', type=int, default=200)
     ap.add_argument('--shapes', default='1000x192,1000x128,100x128')
+    ap.add_argument('--classes', type=int, default=10, help='classes of the class_moments_accum launches at --shapes')
     ap.add_argument('--kernel-only', action='store_true', help='only the moments_accum launches (for a kernel trace of its own)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -108,7 +132,8 @@ def main():
     shapes = [tuple(int(v) for v in s.split('x')) for s in a.shapes.split(',')]
     res = {'what': 'one scoring of the script\'s sample count under a full-width CT classifier, with a Frechet reference set and without '
                    '(plain: the baseline); wall clock ended by a device synchronise, the two alternating on the same samples',
-           'device_name': torch.cuda.get_device_name(0), 'runs': a.runs, 'warmup': a.warmup, 'moments_accum': kernel_times(shapes, a.launches)}
+           'device_name': torch.cuda.get_device_name(0), 'runs': a.runs, 'warmup': a.warmup, 'moments_accum': kernel_times(shapes, a.launches),
+           'class_moments_accum': class_kernel_times(shapes, a.classes, a.launches)}
     if not a.kernel_only:
         scorer = B.build_scorer(dev, a.init_rows)
         images = np.random.RandomState(4).randint(0, 256, (a.reference_rows, 3, 32, 32)).astype(np.uint8)
