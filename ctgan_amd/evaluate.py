@@ -341,7 +341,8 @@ def record_score(ev, series, classifier):
     score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels
     and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it; when it has
     a manifold (ClassifierScore.set_manifold), `precision`, `recall` and `nn_dist`: the k-nearest-neighbour manifold estimate against it; when it has a class reference
-    (ClassifierScore.set_class_reference), `intra_frechet`: the mean per-class Frechet distance to it."""
+    (ClassifierScore.set_class_reference), `intra_frechet`: the mean per-class Frechet distance to it; when it has a kernel reference
+    (ClassifierScore.set_kernel_reference), `kid`: the unbiased kernel distance to it."""
     if ev.name not in SCORE_SERIES:
         return
     from .score_cifar import ClassifierScore
@@ -353,7 +354,7 @@ def record_score(ev, series, classifier):
             series.add('score_acc', res['acc'])
         if 'frechet' in res:
             series.add('frechet', res['frechet'])
-        for name in ('precision', 'recall', 'nn_dist', 'intra_frechet'):
+        for name in ('precision', 'recall', 'nn_dist', 'intra_frechet', 'kid'):
             if name in res:
                 series.add(name, res[name])
         return

@@ -2701,3 +2701,29 @@ def knn_cover(a, b, r2_b=None, covered=None, nn_d2=None, nn_idx=None):
     nn_idx = _knn_out(nn_idx, m, torch.int32, 'knn_cover', a.device)
     check(lib.ctgan_knn_cover(_ptr(a), m, _ptr(b), n, d, _ptr(r2_b), _ptr(covered), _ptr(nn_d2), _ptr(nn_idx), _stream()), 'knn_cover')
     return covered, nn_d2, nn_idx
+
+
+# ---------------------------------------------------------------- polynomial-kernel tile sums of the kernel distance (csrc/kid.hip)
+KERNEL_TILE = lib.ctgan_kernel_tile()
+
+
+def kernel_tile_sums(a, b, gamma=None, coef0=1.0, exclude_diag=False, out=None):
+    """a fp32 [m, D] against b fp32 [n, D] -> fp64 [ceil(m / KERNEL_TILE), ceil(n / KERNEL_TILE)] on the device: element [p, q] is the sum
+    of (gamma a_i . b_j + coef0)^3 over the rows i of tile p and j of tile q, in fp64 throughout (gamma None: 1 / D).  exclude_diag: a
+    set against itself (pass b = a; m != n is refused) without the pairs i == j.  Every element has one summation order: the same bits
+    for every grid shape and every run.  No [m, n] array exists.  D <= 1024."""
+    _need_dev(a, b)
+    m, d = _rows2d(a)
+    n, db = _rows2d(b)
+    assert d == db, 'kernel_tile_sums: %d and %d features' % (d, db)
+    mt, nt = -(-m // KERNEL_TILE), -(-n // KERNEL_TILE)
+    if out is None:
+        out = torch.empty(mt, nt, dtype=torch.float64, device=a.device)
+    else:
+        if not out.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % out.device)
+        assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (mt, nt), \
+            'kernel_tile_sums: contiguous fp64 [%d, %d] expected' % (mt, nt)
+    check(lib.ctgan_kernel_tile_sums(_ptr(a), m, _ptr(b), n, d, 1.0 / d if gamma is None else float(gamma), float(coef0), int(bool(exclude_diag)),
+                                     _ptr(out), _stream()), 'kernel_tile_sums')
+    return out

@@ -58,6 +58,19 @@ conditioned label, `'intra_frechet'`, its mean, `'n_class'` [K], `'confusion'` [
     moments -> fits -> distances                           ClassStatistics, intra_frechet  on the host, from the one device -> host copy
 Samples without labels are refused before any launch; a label outside [0, K) shows in the counts and is refused after the copy.  Again
 classifier statistics under a self-trained 10-class network: NOT comparable to published intra-FID numbers.
+
+The kernel distance.  The Frechet distance is biased in the sample count - two sets from one distribution are at 1.6 with 1,000 samples
+and at 0.15 with 20,000 - and the two CIFAR loops score at 1,000 and at 50,000.  With a kernel reference set
+(`kernel_reference=` / `set_kernel_reference`, a FeatureSet), `score` and `score_generator` also return `'kid'`: the unbiased estimate
+of the squared maximum mean discrepancy under the cubic kernel k(x, y) = (x . y / D + 1)^3 of Binkowski et al. 2018, whose expectation
+does not depend on either count, with `'kid_blocks'`, the same estimate on disjoint blocks of rows, and `'kid_std'`, their spread.
+    features [m, D] -> one [n, D] buffer   the manifold's buffer: one buffer and one copy per chunk when both are set
+    all-pairs kernel sums                  kernels.kernel_tile_sums: samples x samples and samples x reference, once, after the last
+                                           chunk (fp64 MFMA, one fp64 sum per 64 x 64 tile, no [m, n] array); the reference's own sums
+                                           once per FeatureSet (`kernel_tiles`, saved with it)
+    tile sums -> estimate, blocks          fp64 torch reductions on the device, in the scoring's one device -> host copy
+A classifier-feature kernel distance under a self-trained 10-class network's 128 features: NOT comparable to published KID (Inception
+pool3, 2048 features).
 """
 import hashlib
 import os
@@ -219,9 +232,10 @@ def intra_frechet(a, b):
 
 class FeatureSet:
     """The feature rows themselves, fp32 [n, D], of a set under the classifier with hash `classifier` (None: synthetic), with the squared
-    k-th-neighbour radii that `radii(k)` computes on the device once per k and keeps (and `save` writes with the features)."""
+    k-th-neighbour radii that `radii(k)` computes on the device once per k and keeps (and `save` writes with the features), and the set's
+    own kernel tile sums that `kernel_tiles()` computes once and keeps (and `save` writes once they exist)."""
 
-    def __init__(self, features, classifier=None, radii=None):
+    def __init__(self, features, classifier=None, radii=None, kernel_tiles=None):
         f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32))
         if f.dim() != 2 or f.dtype != torch.float32 or f.shape[0] < 1 or f.shape[1] < 1:
             raise ValueError('FeatureSet: fp32 [n, D] features expected (got %s %s)' % (f.dtype, tuple(f.shape)))
@@ -233,6 +247,13 @@ class FeatureSet:
             if r.dtype != torch.float64 or tuple(r.shape) != (self.n,):
                 raise ValueError('FeatureSet: radii of k = %s are not fp64 [%d]' % (k, self.n))
             self._radii[int(k)] = r.contiguous()
+        self._kernel_tiles = None
+        if kernel_tiles is not None:
+            t = kernel_tiles if isinstance(kernel_tiles, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kernel_tiles, dtype=np.float64))
+            tiles = -(-self.n // K.KERNEL_TILE)
+            if t.dtype != torch.float64 or tuple(t.shape) != (tiles, tiles):
+                raise ValueError('FeatureSet: kernel tile sums are not fp64 [%d, %d]' % (tiles, tiles))
+            self._kernel_tiles = t.contiguous()
 
     @property
     def n(self):
@@ -261,9 +282,23 @@ class FeatureSet:
             self._radii[k] = self._radii[k].to(dev)
         return self._radii[k]
 
+    def kernel_tiles(self):
+        """fp64 [ceil(n / 64), ceil(n / 64)] on the device: the sums of (f_i . f_j / D + 1)^3 over the pairs i != j of every 64 x 64 tile of
+        the set against itself (kernels.kernel_tile_sums, once)."""
+        if self._kernel_tiles is None:
+            f = self.device_features()
+            self._kernel_tiles = K.kernel_tile_sums(f, f, exclude_diag=True)
+        dev = lib._dev()
+        if self._kernel_tiles.device != dev:
+            self._kernel_tiles = self._kernel_tiles.to(dev)
+        return self._kernel_tiles
+
     def save(self, path):
-        """-> `path` (numpy .npz; the name is taken as given): the features, the classifier's hash and every radius computed so far."""
+        """-> `path` (numpy .npz; the name is taken as given): the features, the classifier's hash, every radius computed so far and the
+        kernel tile sums if they have been computed."""
         arrays = {'radii_%d' % k: r.cpu().numpy() for k, r in self._radii.items()}
+        if self._kernel_tiles is not None:
+            arrays['kernel_tiles'] = self._kernel_tiles.cpu().numpy()
         with open(path, 'wb') as f:
             np.savez(f, features=self.features.cpu().numpy(), classifier=np.str_(self.classifier or ''),
                      radii_k=np.asarray(sorted(self._radii), dtype=np.int64), **arrays)
@@ -271,7 +306,8 @@ class FeatureSet:
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            return cls(z['features'], str(z['classifier']) or None, {int(k): z['radii_%d' % k] for k in z['radii_k']})
+            return cls(z['features'], str(z['classifier']) or None, {int(k): z['radii_%d' % k] for k in z['radii_k']},
+                       z['kernel_tiles'] if 'kernel_tiles' in z.files else None)
 
 
 def _manifold_counts(samples, reference, k):
@@ -315,6 +351,65 @@ def precision_recall(samples, reference, k=3):
     return _manifold_result(host, samples.n, reference.n, k)
 
 
+def kernel_subset(m, n, subset=None):
+    """The block size of kernel_distance's error bar for `m` samples and `n` reference rows: a given `subset` must be a positive multiple
+    of the kernel tile (64); None: 64 max(1, min(1024, min(m, n) // 4) // 64) - 1024 at 50,000 rows, near the conventional 1,000, and
+    192 at 1,000."""
+    tile = K.KERNEL_TILE
+    if subset is None:
+        return tile * max(1, min(1024, min(m, n) // 4) // tile)
+    s = int(subset)
+    if s != subset or s < tile or s % tile:
+        raise ValueError('kernel_distance: subset = %s (a positive multiple of %d)' % (subset, tile))
+    return s
+
+
+def _kernel_values(xx, yy, xy, m, n, s):
+    """The device half of kernel_distance -> fp64 [1 + P] on the device: the estimate over all rows, then the P = min(m // s, n // s)
+    block estimates.  xx [ceil(m / 64)]^2 and yy [ceil(n / 64)]^2: the two sets' own tile sums without the diagonal, xy: the cross sums."""
+    parts = [xx.sum() / (m * (m - 1.0)) + yy.sum() / (n * (n - 1.0)) - 2.0 * xy.sum() / (float(m) * n)]
+    t, p = s // K.KERNEL_TILE, min(m // s, n // s)
+    if p > 0:
+        idx = torch.arange(p, device=xx.device)
+
+        def diagonal(tiles):          # the sums of the p diagonal t x t blocks of a tile matrix
+            return tiles[:p * t, :p * t].reshape(p, t, p, t)[idx, :, idx, :].sum(dim=(1, 2))
+
+        parts.append((diagonal(xx) + diagonal(yy)) / (s * (s - 1.0)) - 2.0 * diagonal(xy) / (float(s) * s))
+    return torch.cat([v.reshape(-1) for v in parts])
+
+
+def _kernel_result(host, s):
+    blocks = np.array(host[1:], dtype=np.float64)
+    return {'kid': float(host[0]), 'kid_std': float(blocks.std(ddof=1)) if blocks.size >= 2 else None, 'kid_blocks': blocks, 'subset': int(s)}
+
+
+def _check_kernel_sets(samples, reference):
+    if samples.width != reference.width:
+        raise ValueError('kernel_distance: %d and %d features' % (samples.width, reference.width))
+    if samples.classifier is not None and reference.classifier is not None and samples.classifier != reference.classifier:
+        raise ValueError('kernel_distance: the two feature sets were computed under different classifiers')
+    if samples.n < 2 or reference.n < 2:
+        raise ValueError('kernel_distance: %d and %d rows (at least 2 on each side)' % (samples.n, reference.n))
+
+
+def kernel_distance(samples, reference, subset=None):
+    """The unbiased kernel distance (Binkowski et al. 2018: the squared maximum mean discrepancy under k(x, y) = (x . y / D + 1)^3)
+    between two FeatureSets of m and n rows, on the device:
+    -> {'kid': Sxx / (m (m - 1)) + Syy / (n (n - 1)) - 2 Sxy / (m n) over ALL rows of both sets, Sxx and Syy the kernel sums over the
+    pairs i != j within a set and Sxy over all pairs across; 'kid_blocks' fp64 [P]: the same estimate on the P = min(m // s, n // s)
+    disjoint blocks of s = `subset` consecutive rows of either set (kernel_subset; rows are i.i.d. draws or a shuffled file, so
+    consecutive blocks serve); 'kid_std': their standard deviation (ddof = 1), None when P < 2; 'subset': s}.  Its expectation does not
+    depend on m or n, and it may be negative.  Different widths, sets recorded under two different classifiers, or fewer than 2 rows on
+    a side raise."""
+    _check_kernel_sets(samples, reference)
+    m, n = samples.n, reference.n
+    s = kernel_subset(m, n, subset)
+    xy = K.kernel_tile_sums(samples.device_features(), reference.device_features())
+    host = _kernel_values(samples.kernel_tiles(), reference.kernel_tiles(), xy, m, n, s).cpu().numpy()
+    return _kernel_result(host, s)
+
+
 def _module(te):
     if te:
         from . import ct_cifar_te
@@ -335,10 +430,13 @@ class ClassifierScore:
     manifold: a FeatureSet, or the path of a saved one (see set_manifold), manifold_k: the neighbour count: `score` and `score_generator`
     then also return `'precision'`, `'recall'`, `'nn_dist'` and `'nn_zero'` against it (precision_recall).
     class_reference: a ClassStatistics, or the path of a saved one (see set_class_reference): `score` (with labels) and `score_generator`
-    (of a conditional generator) then also return `'frechet_class'`, `'intra_frechet'`, `'n_class'`, `'confusion'` and `'acc_class'`."""
+    (of a conditional generator) then also return `'frechet_class'`, `'intra_frechet'`, `'n_class'`, `'confusion'` and `'acc_class'`.
+    kernel_reference: a FeatureSet, or the path of a saved one (see set_kernel_reference), kernel_subset: the block size of the error
+    bar (None: kernel_subset's rule): `score` and `score_generator` then also return `'kid'`, `'kid_std'` and `'kid_blocks'`
+    (kernel_distance)."""
 
     def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, manifold=None, manifold_k=3,
-                 class_reference=None, **train_kw):
+                 class_reference=None, kernel_reference=None, kernel_subset=None, **train_kw):
         if (trainer is None) == (weights is None):
             raise ValueError('ClassifierScore: pass a trainer or weights=PATH')
         self.trainer = trainer
@@ -365,6 +463,7 @@ class ClassifierScore:
         self.class_reference = None
         if class_reference is not None:
             self.set_class_reference(class_reference)
+        self.set_kernel_reference(kernel_reference, kernel_subset)
 
     # ---- construction
     @staticmethod
@@ -492,6 +591,32 @@ class ClassifierScore:
                 raise ValueError('ClassifierScore: %d manifold rows have no %d-th other neighbour' % (ref.n, k))
         self.manifold, self.manifold_k = ref, k
 
+    # ---- the reference of the kernel distance
+    def _check_kernel_reference(self, ref):
+        if ref.classifier is None:
+            raise ValueError('ClassifierScore: the kernel reference features do not record the classifier they were computed under')
+        if ref.classifier != self.fingerprint():
+            raise ValueError('ClassifierScore: the kernel reference features were computed under another classifier (%s..., this one is %s...)'
+                             % (ref.classifier[:12], self.fingerprint()[:12]))
+        if ref.width != self.cfg.D_WIDTHS[-1]:
+            raise ValueError('ClassifierScore: %d kernel reference features, %d in the classifier' % (ref.width, self.cfg.D_WIDTHS[-1]))
+
+    def set_kernel_reference(self, features_or_path, subset=None):
+        """The FeatureSet (or the path of a saved one; None: none) that `score` / `score_generator` measure the kernel distance to, with
+        blocks of `subset` rows for its error bar (None: kernel_subset's rule at every scoring).  It must have been computed under this
+        classifier's averaged parameters and hold at least 2 rows - checked here and again at every scoring.  Its own tile sums are
+        computed at the first scoring unless it carries them (FeatureSet.kernel_tiles, saved with it)."""
+        ref = features_or_path
+        if ref is not None and not isinstance(ref, FeatureSet):
+            ref = FeatureSet.load(ref)
+        if subset is not None:
+            kernel_subset(2, 2, subset)
+        if ref is not None:
+            self._check_kernel_reference(ref)
+            if ref.n < 2:
+                raise ValueError('ClassifierScore: a kernel reference of %d rows (at least 2)' % ref.n)
+        self.kernel_reference, self.kernel_subset = ref, None if subset is None else int(subset)
+
     # ---- samples in internal form -> logits
     def _forward(self, x, features=False):
         """-> logits [m, K]; features: (logits, the pooled features [m, D]) of the same pass."""
@@ -554,12 +679,17 @@ class ClassifierScore:
         d = self.cfg.D_WIDTHS[-1]
         return FeatureStatistics.from_moments(n, host[:d], host[d:].reshape(d, d), self.fingerprint())
 
-    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None, cls=None):
+    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None, cls=None, ker=None):
         nc = self.cfg.N_CLASSES
         out = K.score_finish(acc, n, splits)
         parts = [out, cnt.to(torch.float64)] + ([] if moments is None else [moments])
         if cls is not None:
             parts += [cls['ints'].to(torch.float64), cls['mom']]
+        if ker is not None:                                  # two launches over all n samples, once, after the last chunk
+            ref, feat = self.kernel_reference, ker['feat']
+            parts.append(_kernel_values(K.kernel_tile_sums(feat, feat, exclude_diag=True), ref.kernel_tiles(),
+                                        K.kernel_tile_sums(feat, ref.device_features()), n, ref.n, ker['subset']))
+            tail = parts[-1].numel()
         if man is not None:                                  # three launches over all n samples, once, after the last chunk
             parts.append(_manifold_counts(man['feat'], self.manifold, self.manifold_k))
         host = torch.cat(parts).cpu().numpy()                # the scoring's one device -> host copy (counts < 2^53: exact)
@@ -580,12 +710,18 @@ class ClassifierScore:
         if man is not None:
             res.update(_manifold_result(host[-5:], n, self.manifold.n, self.manifold_k))
             del res['k']
+            host = host[:-5]
+        if ker is not None:
+            res.update(_kernel_result(host[-tail:], ker['subset']))
+            del res['subset']
         return res
 
-    def _score_chunk(self, x, mom, man=None, r0=0, cls=None, lab=None):
+    def _score_chunk(self, x, mom, man=None, r0=0, cls=None, lab=None, ker=None):
         """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it; with
         the state of one that has a manifold, they are copied to rows r0.. of its buffer; with the state of one that has a class reference,
-        the features go into the state of their label `lab` and the logits into the confusion matrix."""
+        the features go into the state of their label `lab` and the logits into the confusion matrix; the state of one that has a kernel
+        reference holds the manifold's buffer when there is one: one copy serves both."""
+        man = ker if man is None else man
         if mom is None and man is None and cls is None:
             return self._logits(x)
         logits, feat = self._forward(x, True)
@@ -606,6 +742,18 @@ class ClassifierScore:
             raise ValueError('ClassifierScore: %d samples have no %d-th other neighbour' % (n, self.manifold_k))
         self._check_manifold(self.manifold)
         return {'feat': torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)}
+
+    def _begin_kernel(self, n, man):
+        """The state of a scoring with a kernel reference: the block size and the [n, D] device buffer of the chunks' features - the
+        manifold's when there is one."""
+        ref = self.kernel_reference
+        if ref is None:
+            return None
+        if n < 2:
+            raise ValueError('ClassifierScore: the kernel distance needs at least 2 samples')
+        self._check_kernel_reference(ref)
+        feat = man['feat'] if man is not None else torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
+        return {'feat': feat, 'subset': kernel_subset(n, ref.n, self.kernel_subset)}
 
     def _begin_frechet(self, n):
         if self.reference is None:
@@ -628,7 +776,8 @@ class ClassifierScore:
         kernels.aug_gather's fixed mode in chunks of `chunk` rows (None: min(1000, N)); labels [N]: also the accuracy.
         -> {'mean', 'std', 'splits' [splits], 'hist' [K] predicted-class counts, 'acc' (None without labels)}, and with a reference
         set 'frechet', the classifier Frechet distance of the set's features to it, and with a manifold set 'precision', 'recall',
-        'nn_dist' and 'nn_zero' (precision_recall) of them against it."""
+        'nn_dist' and 'nn_zero' (precision_recall) of them against it, and with a kernel reference set 'kid', 'kid_std' and 'kid_blocks'
+        (kernel_distance) of them against it."""
         cfg = self.cfg
         data = torch.as_tensor(images_u8)
         if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
@@ -639,6 +788,7 @@ class ClassifierScore:
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
+        ker = self._begin_kernel(n, man)
         data = data.to(self.dev).contiguous()
         labels = self._labels(labels, n)
         chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
@@ -648,32 +798,33 @@ class ClassifierScore:
             m = min(chunk, n - r0)
             idx = torch.arange(r0, r0 + m, dtype=torch.int32, device=self.dev)
             lab = None if labels is None else labels[r0:r0 + m]
-            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0, cls, lab)
+            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0, cls, lab, ker)
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
-        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls)
+        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls, ker)
 
     def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
         draws them - on the trainer's EVALUATION stream, in statistic groups of 100, `chunk` (a multiple of 100; None: 1000) per
         generator call, the ResNet's labels drawn there unless given - and quantised with the script's SCORE_SCALE as the saved pixels
         are: the training stream, the weights and the optimizers stay untouched.  The ResNet's labels feed the accuracy count.  With a
-        reference set the result also holds 'frechet', with a manifold set 'precision', 'recall', 'nn_dist' and 'nn_zero', all from the
-        features of the same classifier passes."""
+        reference set the result also holds 'frechet', with a manifold set 'precision', 'recall', 'nn_dist' and 'nn_zero', with a kernel
+        reference set 'kid', 'kid_std' and 'kid_blocks', all from the features of the same classifier passes."""
         ev, scale = self._evaluator(gan_trainer, 'score_generator')
         cfg = self.cfg
         cls = self._begin_class(ev.resnet, 'score_generator')      # (only the ResNet's generator is conditional: score_draws yields its labels)
         acc, cnt = self._begin(n, splits)
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
+        ker = self._begin_kernel(n, man)
         labels = self._labels(labels, n)
         r0, with_labels = 0, False
         for x, lab in ev.score_draws(n, labels, chunk):
             lab = None if lab is None else lab.contiguous()
-            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab)
+            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab, ker)
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
             with_labels = lab is not None
             r0 += x.shape[0]
-        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man, cls)
+        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man, cls, ker)
 
     def _evaluator(self, gan_trainer, what):
         from . import evaluate

@@ -886,6 +886,19 @@ int ctgan_knn_max_k(void);
 int ctgan_knn_radii(const float* f, int64_t n, int32_t d, int32_t k, double* r2, ctgan_stream_t stream);
 int ctgan_knn_cover(const float* a, int64_t m, const float* b, int64_t n, int32_t d, const double* r2_b, int32_t* covered, double* nn_d2,
                     int32_t* nn_idx, ctgan_stream_t stream);
+/* The all-pairs polynomial-kernel sums of the unbiased kernel distance of score_cifar.py (csrc/kid.hip).  a fp32 [m, d], b fp32 [n, d]
+ * row-major -> sums fp64 [ceil(m / T), ceil(n / T)] row-major, T = ctgan_kernel_tile() (64):
+ *   sums[p][q] = sum over i in [T p, min(T p + T, m)), j in [T q, min(T q + T, n)) of (gamma a_i . b_j + coef0)^3,
+ * without the pairs i == j (by global index) when exclude_diag != 0 - the caller passes a == b then, and m != n is CTGAN_E_BADARG.
+ * Every term is fp64 over the fp32 features widened exactly: the dot products run on v_mfma_f64_16x16x4_f64 (exact products, only the
+ * sums round), then v = gamma dot + coef0 and v v v in fp64.  Padded rows and the excluded diagonal are masked by index.  The grid is
+ * (tiles of a) x (slabs of consecutive tiles of b), the slab length chosen so that few rows of a still fill the chip; every element of
+ * sums has one owning workgroup and one summation order that does not depend on the slab length: the same bits for every grid shape
+ * and every run.  No atomics, no [m, n] array.  m < 1, n < 1, d < 1, more than 2^30 rows or a null pointer: CTGAN_E_BADARG;
+ * d > 1024: CTGAN_E_UNSUPPORTED; nothing is launched either way.                                                                  */
+int ctgan_kernel_tile(void);
+int ctgan_kernel_tile_sums(const float* a, int64_t m, const float* b, int64_t n, int32_t d, double gamma, double coef0, int32_t exclude_diag,
+                           double* sums, ctgan_stream_t stream);
 
 
 #ifdef __cplusplus
