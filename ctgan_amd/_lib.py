@@ -210,7 +210,14 @@ SIGNATURES = {
     'ctgan_rmsprop_step': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
     'ctgan_rmsprop_step_packed': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float, c_float,
                                           c_float, c_float, _p]),
-    'ctgan_dropout_rng': (c_int, [_p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
+    'ctgan_adam_step_avg': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p]),
+    'ctgan_adam_step_packed_avg': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float,
+                                           c_float, c_float, c_float, _p, c_float, _p]),
+    'ctgan_rmsprop_step_avg': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p]),
+    'ctgan_rmsprop_step_packed_avg': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float,
+                                              c_float, c_float, c_float, _p, c_float, _p]),
+    'ctgan_exchange': (c_int, [_p, _p, c_int64, _p]),
+    'ctgan_dropout_rng':(c_int, [_p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_dropout_rng_mask': (c_int, [_p, _p, _p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_lrelu_dropout_rng': (c_int, [_p, _p, _p, c_int64, c_float, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_lrelu_dropout_rng2': (c_int, [_p, _p, _p, c_int64, c_int64, c_float, c_float, c_uint64, c_uint64, c_uint64, _p, _p]),

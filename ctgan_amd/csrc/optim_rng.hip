@@ -24,14 +24,25 @@ __device__ __forceinline__ void adam_elem(float& th, float& m, float& v, float g
     m = mi; v = vi;
     th = th - lr_t * mi / (sqrtf(vi) + eps);
 }
+// The weight average of the generator (not in the reference; Yazici et al. 2019): avg <- avg + rate (theta_new - avg), the LAST thing an
+// update kernel does to an element - after the clip of rmsprop_elem, and also for an element whose non-finite gradient was skipped: the
+// average follows the weights as they are.  Contraction off like adam_elem: two roundings (the product, the sum) in every kernel form.
+__device__ __forceinline__ float avg_elem(float a, float th, float rate) {
+#pragma clang fp contract(off)
+    return a + rate * (th - a);
+}
+// Every update kernel is a template on "keeps an average": the AVG = false instantiation is the code without it (avg / avg_rate unused).
+template <bool AVG>
 __global__ void adam_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float* state, float b1, float b2,
-                            float eps, float gscale) {
+                            float eps, float gscale, float* __restrict__ avg, float avg_rate) {
     const float lr = state[0], b1p = state[1], b2p = state[2];
     const float lr_t = lr * sqrtf(1.f - b2p) / (1.f - b1p);
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         adam_elem(th[i], m[i], v[i], g[i], gscale, b1, b2, eps, lr_t, state + 3);
+        if constexpr (AVG) avg[i] = avg_elem(avg[i], th[i], avg_rate);
+    }
 }
 __global__ void adam_advance_kernel(float* state, float b1, float b2) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { state[1] *= b1; state[2] *= b2; }
@@ -72,8 +83,10 @@ __global__ void pack_kernel(const PackTable t, float* __restrict__ flat) {
 // pack_kernel + adam_kernel in one launch (single-rank steps: nothing happens between the gather and the update).
 // The flat bucket is still written - it is the gradient the caller reports and the tests read.  Same per-element arithmetic as
 // adam_kernel on the packed bucket (bit-identical results).
+template <bool AVG>
 __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, float* __restrict__ th, float* __restrict__ m,
-                                   float* __restrict__ v, float* state, float b1, float b2, float eps, float gscale) {
+                                   float* __restrict__ v, float* state, float b1, float b2, float eps, float gscale,
+                                   float* __restrict__ avg, float avg_rate) {
     const float lr = state[0], b1p = state[1], b2p = state[2];
     const float lr_t = lr * sqrtf(1.f - b2p) / (1.f - b1p);
     const float* src = t.src[blockIdx.y];
@@ -86,6 +99,7 @@ __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, 
         float4* th4 = reinterpret_cast<float4*>(th + off);
         float4* m4 = reinterpret_cast<float4*>(m + off);
         float4* v4 = reinterpret_cast<float4*>(v + off);
+        float4* a4 = AVG ? reinterpret_cast<float4*>(avg + off) : nullptr;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
             const float4 gr = src ? src4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
             f4[i] = gr;
@@ -95,12 +109,20 @@ __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, 
 #pragma unroll
             for (int k = 0; k < 4; ++k) adam_elem(tp[k], mp[k], vp[k], gv[k], gscale, b1, b2, eps, lr_t, state + 3);
             m4[i] = mm; v4[i] = vv; th4[i] = tt;
+            if constexpr (AVG) {
+                float4 aa = a4[i];
+                float* ap = &aa.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ap[k] = avg_elem(ap[k], tp[k], avg_rate);
+                a4[i] = aa;
+            }
         }
     } else {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
             const float gr = src ? src[i] : 0.f;
             flat[off + i] = gr;
             adam_elem(th[off + i], m[off + i], v[off + i], gr, gscale, b1, b2, eps, lr_t, state + 3);
+            if constexpr (AVG) avg[off + i] = avg_elem(avg[off + i], th[off + i], avg_rate);
         }
     }
 }
@@ -120,17 +142,22 @@ __device__ __forceinline__ void rmsprop_elem(float& th, float& ms, float graw, f
     ms = mi;
     th = clip_to(th - (gi * lr) / sqrtf(mi + eps), clip);
 }
+template <bool AVG>
 __global__ void rmsprop_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ ms, long long n, float* state,
-                               float rho, float eps, float clip, float gscale) {
+                               float rho, float eps, float clip, float gscale, float* __restrict__ avg, float avg_rate) {
     const float lr = state[0];
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         rmsprop_elem(th[i], ms[i], g[i], gscale, rho, eps, lr, clip, state + 3);
+        if constexpr (AVG) avg[i] = avg_elem(avg[i], th[i], avg_rate);
+    }
 }
 // pack_kernel + rmsprop_kernel in one launch: adam_packed_kernel's layout (pointer table in the arguments, grid.y = tensor, 4-wide body
 // when the segment allows it, scalar otherwise); the flat bucket is still written.
+template <bool AVG>
 __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ flat, float* __restrict__ th, float* __restrict__ ms,
-                                      float* state, float rho, float eps, float clip, float gscale) {
+                                      float* state, float rho, float eps, float clip, float gscale, float* __restrict__ avg,
+                                      float avg_rate) {
     const float lr = state[0];
     const float* src = t.src[blockIdx.y];
     const long long off = t.dst_off[blockIdx.y], n = t.n[blockIdx.y];
@@ -141,6 +168,7 @@ __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ fla
         float4* f4 = reinterpret_cast<float4*>(flat + off);
         float4* th4 = reinterpret_cast<float4*>(th + off);
         float4* ms4 = reinterpret_cast<float4*>(ms + off);
+        float4* a4 = AVG ? reinterpret_cast<float4*>(avg + off) : nullptr;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
             const float4 gr = src ? src4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
             f4[i] = gr;
@@ -150,12 +178,20 @@ __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ fla
 #pragma unroll
             for (int k = 0; k < 4; ++k) rmsprop_elem(tp[k], mp[k], gv[k], gscale, rho, eps, lr, clip, state + 3);
             ms4[i] = mm; th4[i] = tt;
+            if constexpr (AVG) {
+                float4 aa = a4[i];
+                float* ap = &aa.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ap[k] = avg_elem(ap[k], tp[k], avg_rate);
+                a4[i] = aa;
+            }
         }
     } else {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
             const float gr = src ? src[i] : 0.f;
             flat[off + i] = gr;
             rmsprop_elem(th[off + i], ms[off + i], gr, gscale, rho, eps, lr, clip, state + 3);
+            if constexpr (AVG) avg[off + i] = avg_elem(avg[off + i], th[off + i], avg_rate);
         }
     }
 }
@@ -416,17 +452,112 @@ __global__ void rng_advance_kernel(uint64_t* ctr, uint64_t by) {
     if (threadIdx.x == 0 && blockIdx.x == 0) ctr[0] += by;
 }
 
+// Swap the contents of two equal-length buffers in place (FlatAdam's weights <-> their average, Trainer.averaged()): every address a
+// captured graph or a data_ptr-keyed filter cache has seen stays valid, and no third buffer is needed.  VEC (both pointers 16-byte
+// aligned): n / 4 float4 items, then the n % 4 elements behind them one by one; otherwise element by element.
+template <bool VEC>
+__global__ void exchange_kernel(float* __restrict__ a, float* __restrict__ b, long long n) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (VEC) {
+        float4* a4 = reinterpret_cast<float4*>(a); float4* b4 = reinterpret_cast<float4*>(b);
+        const long long n4 = n >> 2;
+        for (long long i = first; i < n4; i += stride) {
+            const float4 x = a4[i], y = b4[i];
+            a4[i] = y; b4[i] = x;
+        }
+        const long long i = (n4 << 2) + first;          // the tail: at most three elements, the first threads of the grid
+        if (i < n) { const float x = a[i], y = b[i]; a[i] = y; b[i] = x; }
+    } else {
+        for (long long i = first; i < n; i += stride) {
+            const float x = a[i], y = b[i];
+            a[i] = y; b[i] = x;
+        }
+    }
+}
+
+// Host side of the four update launches, one template each on "keeps an average" (the C entry points below forward here).
+inline bool avg_args_bad(const float* avg, float avg_rate) { return !avg || !(avg_rate > 0.f && avg_rate <= 1.f); }
+
+template <bool AVG>
+int adam_step_host(const char* what, float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2,
+                   float eps, float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
+    if (!theta || !g || !m || !v || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
+    if (n == 0) return CTGAN_OK;
+    hipLaunchKernelGGL(adam_kernel<AVG>, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, m,
+                       v, (long long)n, state, beta1, beta2, eps, grad_scale, avg, avg_rate);
+    return ctgan_check_launch(what);
+}
+// the pointer table of a packed update; 0 or the error
+int fill_pack_table(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                    PackTable& t, long long& mx) {
+    mx = 1;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (counts[i] < 0 || dst_offs[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: negative extent", what);
+        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs[i]; t.n[i] = counts[i];
+        if (t.n[i] > mx) mx = t.n[i];
+    }
+    return CTGAN_OK;
+}
+template <bool AVG>
+int adam_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                          float* flat, float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps,
+                          float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0)
+        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
+    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
+    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(m) |
+         reinterpret_cast<uintptr_t>(v) | (AVG ? reinterpret_cast<uintptr_t>(avg) : 0)) & 15)
+        return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: flat buffers must be 16-byte aligned", what);
+    PackTable t;
+    long long mx;
+    if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
+    hipLaunchKernelGGL(adam_packed_kernel<AVG>, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t,
+                       flat, theta, m, v, state, beta1, beta2, eps, grad_scale, avg, avg_rate);
+    return ctgan_check_launch(what);
+}
+template <bool AVG>
+int rmsprop_step_host(const char* what, float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                      float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
+    if (!theta || !g || !ms || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
+    if (n == 0) return CTGAN_OK;
+    hipLaunchKernelGGL(rmsprop_kernel<AVG>, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, ms,
+                       (long long)n, state, rho, eps, clip, grad_scale, avg, avg_rate);
+    return ctgan_check_launch(what);
+}
+template <bool AVG>
+int rmsprop_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                             float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
+                             float* avg, float avg_rate, ctgan_stream_t s) {
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0)
+        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
+    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
+    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(ms) |
+         (AVG ? reinterpret_cast<uintptr_t>(avg) : 0)) & 15)
+        return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: flat buffers must be 16-byte aligned", what);
+    PackTable t;
+    long long mx;
+    if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
+    hipLaunchKernelGGL(rmsprop_packed_kernel<AVG>, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s),
+                       t, flat, theta, ms, state, rho, eps, clip, grad_scale, avg, avg_rate);
+    return ctgan_check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
 
 int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
                     float beta2, float eps, float grad_scale, ctgan_stream_t s) {
-    if (!theta || !g || !m || !v || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "adam_step: bad argument");
-    if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL(adam_kernel, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, m,
-                       v, (long long)n, state, beta1, beta2, eps, grad_scale);
-    return ctgan_check_launch("adam_step");
+    return adam_step_host<false>("adam_step", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, s);
+}
+int ctgan_adam_step_avg(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
+                        float beta2, float eps, float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
+    return adam_step_host<true>("adam_step_avg", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, s);
 }
 int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                ctgan_stream_t s) {
@@ -453,49 +584,47 @@ int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr
 int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                            float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
                            ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0)
-        return ctgan_fail(CTGAN_E_BADARG, "adam_step_packed: bad argument");
-    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "adam_step_packed: more than %d tensors", PACK_MAX);
-    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(m) |
-         reinterpret_cast<uintptr_t>(v)) & 15)
-        return ctgan_fail(CTGAN_E_UNSUPPORTED, "adam_step_packed: flat buffers must be 16-byte aligned");
-    PackTable t;
-    long long mx = 1;
-    for (int i = 0; i < n_tensors; ++i) {
-        if (counts[i] < 0 || dst_offs[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "adam_step_packed: negative extent");
-        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs[i]; t.n[i] = counts[i];
-        if (t.n[i] > mx) mx = t.n[i];
-    }
-    hipLaunchKernelGGL(adam_packed_kernel, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t,
-                       flat, theta, m, v, state, beta1, beta2, eps, grad_scale);
-    return ctgan_check_launch("adam_step_packed");
+    return adam_step_packed_host<false>("adam_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2, eps,
+                                        grad_scale, nullptr, 0.f, s);
+}
+int ctgan_adam_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                               float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
+                               float* avg, float avg_rate, ctgan_stream_t s) {
+    return adam_step_packed_host<true>("adam_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2,
+                                       eps, grad_scale, avg, avg_rate, s);
 }
 int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
                        float grad_scale, ctgan_stream_t s) {
-    if (!theta || !g || !ms || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step: bad argument");
-    if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, ms,
-                       (long long)n, state, rho, eps, clip, grad_scale);
-    return ctgan_check_launch("rmsprop_step");
+    return rmsprop_step_host<false>("rmsprop_step", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, s);
+}
+int ctgan_rmsprop_step_avg(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                           float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
+    return rmsprop_step_host<true>("rmsprop_step_avg", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, s);
 }
 int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                               float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
                               ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0)
-        return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step_packed: bad argument");
-    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "rmsprop_step_packed: more than %d tensors", PACK_MAX);
-    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(ms)) & 15)
-        return ctgan_fail(CTGAN_E_UNSUPPORTED, "rmsprop_step_packed: flat buffers must be 16-byte aligned");
-    PackTable t;
-    long long mx = 1;
-    for (int i = 0; i < n_tensors; ++i) {
-        if (counts[i] < 0 || dst_offs[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "rmsprop_step_packed: negative extent");
-        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs[i]; t.n[i] = counts[i];
-        if (t.n[i] > mx) mx = t.n[i];
-    }
-    hipLaunchKernelGGL(rmsprop_packed_kernel, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s),
-                       t, flat, theta, ms, state, rho, eps, clip, grad_scale);
-    return ctgan_check_launch("rmsprop_step_packed");
+    return rmsprop_step_packed_host<false>("rmsprop_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps, clip,
+                                           grad_scale, nullptr, 0.f, s);
+}
+int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                                  float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale, float* avg,
+                                  float avg_rate, ctgan_stream_t s) {
+    return rmsprop_step_packed_host<true>("rmsprop_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps,
+                                          clip, grad_scale, avg, avg_rate, s);
+}
+int ctgan_exchange(float* a, float* b, int64_t n, ctgan_stream_t s) {
+    if (n < 0 || (n > 0 && (!a || !b))) return ctgan_fail(CTGAN_E_BADARG, "exchange: bad argument");
+    if (n == 0) return CTGAN_OK;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    if ((pa < pb ? pb - pa : pa - pb) < (uintptr_t)n * sizeof(float)) return ctgan_fail(CTGAN_E_BADARG, "exchange: the buffers overlap");
+    if (((pa | pb) & 15) == 0)
+        hipLaunchKernelGGL(exchange_kernel<true>, dim3(ctgan_blocks((n + 3) >> 2, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), a, b,
+                           (long long)n);
+    else
+        hipLaunchKernelGGL(exchange_kernel<false>, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), a, b,
+                           (long long)n);
+    return ctgan_check_launch("exchange");
 }
 int ctgan_adam_advance(float* state, float beta1, float beta2, ctgan_stream_t s) {
     if (!state) return ctgan_fail(CTGAN_E_BADARG, "adam_advance: null");

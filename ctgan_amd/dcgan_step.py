@@ -24,6 +24,7 @@ from . import functional as F
 from . import kernels as K
 from . import tflib as lib
 from .optim import FlatAdam, FlatRMSProp
+from .optim import averaged as averaged_weights
 from .rng import DeviceRNG
 
 
@@ -66,9 +67,12 @@ def mode_of(module):
 
 
 class DCGANTrainer:
-    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None):
+    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
-        real_prep, feat_shapes)."""
+        real_prep, feat_shapes).  g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights,
+        moved inside its update launch (optim.FlatAdam / FlatRMSProp avg_rate), whatever the mode's optimizer.  It is the RATE, 1 - decay:
+        g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it; the critic is never averaged.  0 (default): nothing differs
+        from a trainer built without the argument."""
         self.mod = module
         self.dev = lib._dev()
         self.rank, self.world, self.allreduce = rank, world_size, allreduce
@@ -79,11 +83,11 @@ class DCGANTrainer:
         self.disc_iters = self.mode.critic_iters or module.cfg.CRITIC_ITERS     # critic steps per iteration
         if self.mode.optimizer == 'rmsprop':
             self.d_opt = FlatRMSProp(self.d_named, clip=self.mode.clip)
-            self.g_opt = FlatRMSProp(self.g_named)
+            self.g_opt = FlatRMSProp(self.g_named, avg_rate=g_average)
         else:
             b1, b2 = self.mode.betas or getattr(module, 'ADAM_BETAS', (0.5, 0.9))
             self.d_opt = FlatAdam(self.d_named, b1, b2)
-            self.g_opt = FlatAdam(self.g_named, b1, b2)
+            self.g_opt = FlatAdam(self.g_named, b1, b2, avg_rate=g_average)
         # the clip op also covers the critic's non-trainable BatchNorm moving statistics; nothing else writes them (training-mode
         # statistics only), so clamping them once, at the first critic update, is exact
         self._stats_to_clip = [p for n, p in lib.named_params_with_name('Discriminator') if n in lib._non_trainable] if self.mode.clip else []
@@ -98,6 +102,11 @@ class DCGANTrainer:
         # (grad_scale); exact in fp32 (a power of two), a no-op for S = 1.
         self.loss_scale = float(getattr(module, 'LOSS_SCALE', 1.0))
         self._seed = None
+
+    def averaged(self):
+        """Context manager: inside it the generator's parameters hold their weight average (optim.averaged; ValueError when the
+        trainer was built with g_average = 0).  Sample and score inside; do not train inside."""
+        return averaged_weights(self.g_opt)
 
     def cost_seed(self):
         """grad_outputs of the final backward: a cached 0-dim tensor holding the loss scale (no fill kernel per step)."""
@@ -281,13 +290,18 @@ def build_params(module, device=None):
         module.Discriminator(x, u=[torch.full((2,) + tuple(s), 0.9, device=dev) for s in module.feat_shapes()])
 
 
-def sample_grid(module, noise):
+def sample_grid(module, noise, trainer=None, averaged=False):
     """generate_image of the scripts (TF/CT_gan_cifar.py:162-165, TF/CT_gan_mnist.py:211-216, TF/CT_gan_64x64.py:588-592): the fixed-noise
-    samples as the array tflib.save_images takes - [n, 28, 28] floats in [0, 1] (MNIST) or [n, 3, H, W] integer pixels."""
+    samples as the array tflib.save_images takes - [n, 28, 28] floats in [0, 1] (MNIST) or [n, 3, H, W] integer pixels.  averaged (with the
+    `trainer` that keeps it): from the generator's weight average (DCGANTrainer.averaged)."""
+    import contextlib
     import math
-    F.prepare_filters()
-    with torch.no_grad():
-        s = module.Generator(noise.shape[0], noise=noise)
+    if averaged and trainer is None:
+        raise ValueError('sample_grid: averaged=True needs the trainer that keeps the average')
+    with trainer.averaged() if averaged else contextlib.nullcontext():
+        F.prepare_filters()
+        with torch.no_grad():
+            s = module.Generator(noise.shape[0], noise=noise)
     n, d = s.shape
     if d % 3:
         side = int(round(math.sqrt(d)))
@@ -299,13 +313,14 @@ def sample_grid(module, noise):
 
 
 def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
-          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print):
+          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0):
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
     (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series (and `frechet`
     when it is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a manifold); the fixed-noise sample grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
-    `dev_every`-th.  Returns the trainer."""
+    `dev_every`-th.  `g_average` > 0 (NOT in the reference; DCGANTrainer): the generator's weight average is kept, scored after the live
+    generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  Returns the trainer."""
     import os
     import time
 
@@ -316,7 +331,7 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     cfg = module.cfg
     iters = cfg.ITERS if iters is None else iters
     build_params(module)
-    trainer = DCGANTrainer(module, seed=seed)
+    trainer = DCGANTrainer(module, seed=seed, g_average=g_average)
     start = checkpoint.load(resume, trainer) if resume else 0
     first = next_batch()
     eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)
@@ -334,6 +349,8 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
         series.add('time', time.time() - t0)
         if classifier is not None and score_every and iteration % score_every == score_every - 1:
             evaluate.record_score(ev, series, classifier)
+            if g_average:
+                evaluate.record_score(ev, series, classifier, averaged=True)
         if dev_batches is not None and dev_every and iteration % dev_every == dev_every - 1:
             dev = ev.dev_cost(dev_batches())
             if 'slope_real' in dev:
@@ -341,6 +358,9 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
             series.add('dev disc cost', dev['dev_cost'])
         if sample_every and iteration % sample_every == sample_every - 1:
             save_images.save_images(sample_grid(module, fixed_noise), os.path.join(out_dir, 'samples_%d.png' % iteration))
+            if g_average:
+                save_images.save_images(sample_grid(module, fixed_noise, trainer, averaged=True),
+                                        os.path.join(out_dir, 'samples_%d_avg.png' % iteration))
         if checkpoint_every and iteration % checkpoint_every == checkpoint_every - 1:
             checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, iteration + 1)
         if iteration < 5 or (dev_every and iteration % dev_every == dev_every - 1):

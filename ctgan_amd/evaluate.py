@@ -280,16 +280,22 @@ class Evaluator:
             return slopes.max()
 
     # ------------------------------------------------------------------ score samples
-    def score_draws(self, n, labels=None, chunk=None):
+    def score_draws(self, n, labels=None, chunk=None, averaged=False):
         """Yields (samples fp32 [m, OUTPUT_DIM] as the generator returns them, their labels int32 [m] - None for an unconditional
         generator) until `n` samples are out.  Samples are drawn on the evaluation stream in statistic groups of 100
         (samples_100 = Generator(100, ...)); `chunk` samples (a multiple of 100; None: DEFAULT_SCORE_CHUNK) share one generator call.
-        ResNet: `labels` [n] int32, or drawn uniformly in [0, 10) on the evaluation stream (:351)."""
+        ResNet: `labels` [n] int32, or drawn uniformly in [0, 10) on the evaluation stream (:351).  averaged (NOT in the reference): the
+        samples come from the generator's weight average - the whole iteration runs inside `trainer.averaged()`, which is left when
+        the iterator is exhausted or closed, so consume it to its end (or close it) before training on."""
         if self.name not in SCORE_SCALE:
             raise NotImplementedError('%s: the script scores no samples (no three-channel output)' % self.mod.__name__)
         chunk = DEFAULT_SCORE_CHUNK[self.name] if chunk is None else int(chunk)
         if chunk < SCORE_GROUP or chunk % SCORE_GROUP:
             raise ValueError('score samples: chunk must be a positive multiple of %d' % SCORE_GROUP)
+        if averaged:
+            with self.t.averaged():
+                yield from self.score_draws(n, labels, chunk)
+            return
         rng = self.rng
         F.prepare_filters()
         done = 0
@@ -313,51 +319,58 @@ class Evaluator:
             yield x.contiguous()[:m], (lab[:m] if lab is not None else None)
             done += m
 
-    def score_samples(self, n, labels=None, scale=255.99 / 2, chunk=None):
-        """Yields uint8 [m, H, W, 3] pixel tensors, trunc((sample + 1) * scale), of the samples of score_draws(n, labels, chunk)."""
+    def score_samples(self, n, labels=None, scale=255.99 / 2, chunk=None, averaged=False):
+        """Yields uint8 [m, H, W, 3] pixel tensors, trunc((sample + 1) * scale), of the samples of score_draws(n, labels, chunk, averaged)."""
         side = int(round(math.sqrt(self.mod.cfg.OUTPUT_DIM // 3)))
-        for x, _ in self.score_draws(n, labels, chunk):
+        for x, _ in self.score_draws(n, labels, chunk, averaged):
             yield K.pixels_u8(x, 3, scale).reshape(x.shape[0], side, side, 3)
 
-    def get_inception_score(self, n, classifier, splits=10, scale=None):
+    def get_inception_score(self, n, classifier, splits=10, scale=None, averaged=False):
         """(mean, std) of the score over `n` samples: `classifier` (a host callable) gets float32 [m, H, W, 3] arrays in [0, 255] and
-        returns class probabilities [m, n_classes] (tflib.inception_score).  `scale`: None = the script's literal (SCORE_SCALE)."""
+        returns class probabilities [m, n_classes] (tflib.inception_score).  `scale`: None = the script's literal (SCORE_SCALE).
+        averaged: the samples come from the generator's weight average (score_draws)."""
         from .tflib.inception_score import score_from_probabilities
         if classifier is None:
             raise ValueError('get_inception_score needs a classifier: none ships with this library')
         scale = SCORE_SCALE[self.name] if scale is None else scale
-        preds = [np.asarray(classifier(px.cpu().numpy().astype(np.float32))) for px in self.score_samples(n, scale=scale)]
+        preds = [np.asarray(classifier(px.cpu().numpy().astype(np.float32))) for px in self.score_samples(n, scale=scale, averaged=averaged)]
         return score_from_probabilities(np.concatenate(preds, 0), splits)
 
-    def get_classifier_score(self, n, scorer, splits=10):
+    def get_classifier_score(self, n, scorer, splits=10, averaged=False):
         """The score of `n` samples under `scorer` (a score_cifar.ClassifierScore), everything on the device: samples -> classifier
         input (kernels.score_input) -> logits -> streaming statistic -> {'mean', 'std', 'splits', 'hist', 'acc'}, one host copy; a scorer
-        with a reference adds 'frechet' from the same classifier passes."""
+        with a reference adds 'frechet' from the same classifier passes.  averaged: the samples come from the generator's weight average."""
+        if averaged:
+            return scorer.score_generator(self.t, n, splits=splits, averaged=True)
         return scorer.score_generator(self.t, n, splits=splits)
 
 
-def record_score(ev, series, classifier):
+def record_score(ev, series, classifier, averaged=False):
     """One scoring of the loops: the script's sample count through `classifier`, recorded under the script's series names.  A
     score_cifar.ClassifierScore takes the device path (get_classifier_score) and also records `score_acc` where the samples have labels
     and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it; when it has
     a manifold (ClassifierScore.set_manifold), `precision`, `recall` and `nn_dist`: the k-nearest-neighbour manifold estimate against it; when it has a class reference
     (ClassifierScore.set_class_reference), `intra_frechet`: the mean per-class Frechet distance to it; when it has a kernel reference
-    (ClassifierScore.set_kernel_reference), `kid`: the unbiased kernel distance to it."""
+    (ClassifierScore.set_kernel_reference), `kid`: the unbiased kernel distance to it.  averaged (NOT in the reference): the samples come
+    from the generator's weight average (trainer.averaged) and every series name gets the suffix `_avg` (`inception_50k_avg`,
+    `frechet_avg`, `kid_avg`, ...); the loops call it after the live scoring, on the next steps of the evaluation stream."""
     if ev.name not in SCORE_SERIES:
         return
     from .score_cifar import ClassifierScore
+    kw = {'averaged': True} if averaged else {}
+    sfx = '_avg' if averaged else ''
     if isinstance(classifier, ClassifierScore):
-        res = ev.get_classifier_score(SCORE_SAMPLES[ev.name], classifier)
+        res = ev.get_classifier_score(SCORE_SAMPLES[ev.name], classifier, **kw)
         for name, value in zip(SCORE_SERIES[ev.name], (res['mean'], res['std'])):
-            series.add(name, value)
+            series.add(name + sfx, value)
         if res['acc'] is not None:
-            series.add('score_acc', res['acc'])
+            series.add('score_acc' + sfx, res['acc'])
         if 'frechet' in res:
-            series.add('frechet', res['frechet'])
+            series.add('frechet' + sfx, res['frechet'])
         for name in ('precision', 'recall', 'nn_dist', 'intra_frechet', 'kid'):
             if name in res:
-                series.add(name, res[name])
+                series.add(name + sfx, res[name])
         return
-    score = ev.get_inception_score(SCORE_SAMPLES[ev.name], classifier)
+    score = ev.get_inception_score(SCORE_SAMPLES[ev.name], classifier, **kw)
     for name, value in zip(SCORE_SERIES[ev.name], score):
-        series.add(name, value)
+        series.add(name + sfx, value)

@@ -22,6 +22,7 @@ from . import functional as F
 from . import kernels as K
 from . import tflib as lib
 from .optim import FlatAdam
+from .optim import averaged as averaged_weights
 from .rng import DeviceRNG
 from .tflib.ops import batchnorm as _bn
 from .tflib.ops import cond_batchnorm as _cbn
@@ -457,7 +458,10 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
 class Trainer:
     """Owns the optimizers, the random streams and the D/G step (the session of the reference)."""
 
-    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None):
+    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0):
+        """g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights, moved inside its update
+        launch (optim.FlatAdam avg_rate).  It is the RATE, 1 - decay: g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it.
+        The critic is never averaged.  0 (default): nothing differs from a trainer built without the argument."""
         self.dev = lib._dev()
         self.rank, self.world = rank, world_size
         self.allreduce = allreduce            # callable(flat_tensor) -> None, sums across ranks (ddp.py)
@@ -466,7 +470,7 @@ class Trainer:
         self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
         self._opt_state = torch.zeros(8, dtype=torch.float32, device=self.dev)      # both optimizers' {lr, b1^t, b2^t, -}: set_lr()
         self.d_opt = FlatAdam(self.d_named, 0.0, 0.9, state=self._opt_state[0:4])
-        self.g_opt = FlatAdam(self.g_named, 0.0, 0.9, state=self._opt_state[4:8])
+        self.g_opt = FlatAdam(self.g_named, 0.0, 0.9, state=self._opt_state[4:8], avg_rate=g_average)
         self.d_params = [p for _, p in self.d_named]
         self.g_params = [p for _, p in self.g_named]
         self._one = None
@@ -742,22 +746,29 @@ class Trainer:
             out = self.d_step(data, labels, iteration=iteration, fake=fakes[i])
         return out
 
-    def generate_samples(self, noise, labels):
-        """fixed_noise_samples / generate_image :341-348: int pixels = ((s+1)*255/2) truncated."""
-        with torch.no_grad():
-            s = Generator(noise.shape[0], labels, noise=noise)
+    def averaged(self):
+        """Context manager: inside it the generator's parameters hold their weight average (optim.averaged; ValueError when the
+        trainer was built with g_average = 0).  Sample and score inside; do not train inside."""
+        return averaged_weights(self.g_opt)
+
+    def generate_samples(self, noise, labels, averaged=False):
+        """fixed_noise_samples / generate_image :341-348: int pixels = ((s+1)*255/2) truncated.  averaged: from the weight average."""
+        with self.averaged() if averaged else contextlib.nullcontext():
+            with torch.no_grad():
+                s = Generator(noise.shape[0], labels, noise=noise)
         return s, ((s + 1.) * (255. / 2)).to(torch.int32)
 
 
 def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100,
-          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None):
+          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0):
     """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434): CIFAR-10 generator factories, `time` /
     `cost` / `wgan` / `acgan` / `acc_real` / `acc_fake` series (train_log.Series), fixed-noise sample grids every
     `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
     every `dev_every` iterations (:421-427, evaluate.Evaluator.dev_cost) and - with a `classifier` (no Inception graph ships: the 2015
     graph needs a network) - `inception_50k` / `inception_50k_std` every `score_every` iterations (:414-418), and
     `frechet` when the classifier is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a
-    manifold (evaluate.record_score)."""
+    manifold (evaluate.record_score).  `g_average` > 0 (NOT in the reference; Trainer): the generator's weight average is kept, scored
+    after the live generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`."""
     import os
     import time
 
@@ -767,7 +778,7 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     from .train_log import Series
     iters = cfg.ITERS if iters is None else iters
     build_params()
-    trainer = Trainer(seed=seed)
+    trainer = Trainer(seed=seed, g_average=g_average)
     start = checkpoint.load(resume, trainer) if resume else 0
     eng = GraphedTrainer(trainer, use_graphs=use_graphs)
     ev = evaluate.Evaluator(trainer)
@@ -786,11 +797,16 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
         series.add('time', time.time() - t0)
         if classifier is not None and score_every and iteration % score_every == score_every - 1:
             evaluate.record_score(ev, series, classifier)
+            if g_average:
+                evaluate.record_score(ev, series, classifier, averaged=True)
         if dev_every and iteration % dev_every == dev_every - 1:
             series.add('dev_cost', ev.dev_cost(cifar10.prefetch_to_device(dev_gen(), trainer.dev))['dev_cost'])
         if iteration % sample_every == sample_every - 1:
             _, px = trainer.generate_samples(fixed_noise, fixed_labels)
             save_images.save_images(px.reshape(100, 3, 32, 32).cpu().numpy(), os.path.join(out_dir, 'samples_%d.png' % iteration))
+            if g_average:
+                _, px = trainer.generate_samples(fixed_noise, fixed_labels, averaged=True)
+                save_images.save_images(px.reshape(100, 3, 32, 32).cpu().numpy(), os.path.join(out_dir, 'samples_%d_avg.png' % iteration))
         if checkpoint_every and iteration % checkpoint_every == checkpoint_every - 1:
             checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, iteration + 1)
         if iteration < 500 or iteration % 1000 == 999:

@@ -1908,11 +1908,23 @@ def gan_loss_bwd(d, gout, B, kind):
 
 
 # ------------------------------------------------------------------------------- optimizer / rng
-def adam_step(theta, g, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0):
-    """In-place TF-Adam on flat fp32 buffers; `state` = device float[4] {lr, beta1^t, beta2^t, -}."""
+def _check_avg(avg, theta, avg_rate):
+    """The weight average of an update launch: laid out like theta; a rate in (0, 1] (the C entry refuses anything else)."""
+    _need_dev(avg)
+    assert avg.is_contiguous() and avg.dtype == torch.float32 and avg.numel() == theta.numel()
+    return float(avg_rate)
+
+
+def adam_step(theta, g, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0, avg=None, avg_rate=0.0):
+    """In-place TF-Adam on flat fp32 buffers; `state` = device float[4] {lr, beta1^t, beta2^t, -}.  `avg` (not in the reference): a
+    weight average moved in the same launch, avg <- avg + avg_rate (theta - avg) after the update (ctgan_adam_step_avg)."""
     _need_dev(theta, g, m, v, state)
     for t in (theta, g, m, v):
         assert t.is_contiguous() and t.numel() == theta.numel()
+    if avg is not None:
+        check(lib.ctgan_adam_step_avg(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps,
+                                      grad_scale, _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'adam_step_avg')
+        return
     check(lib.ctgan_adam_step(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps,
                               grad_scale, _stream()), 'adam_step')
 
@@ -1927,8 +1939,8 @@ def step_advance(state, beta1, beta2, rng_ctr=None, rng_by=1):
 ADAM_PACKED_MAX = 64
 
 
-def adam_step_packed(srcs, dst_offs, counts, flat, theta, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0):
-    """pack(srcs -> flat) + adam_step in one launch (len(srcs) <= ADAM_PACKED_MAX)."""
+def adam_step_packed(srcs, dst_offs, counts, flat, theta, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0, avg=None, avg_rate=0.0):
+    """pack(srcs -> flat) + adam_step in one launch (len(srcs) <= ADAM_PACKED_MAX); `avg`: as adam_step."""
     _need_dev(flat, theta, m, v, state, *[t for t in srcs if t is not None])
     n = len(srcs)
     assert n <= ADAM_PACKED_MAX
@@ -1937,21 +1949,30 @@ def adam_step_packed(srcs, dst_offs, counts, flat, theta, m, v, state, beta1, be
     P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
     O = (ctypes.c_int64 * n)(*dst_offs)
     C = (ctypes.c_int64 * n)(*counts)
+    if avg is not None:
+        check(lib.ctgan_adam_step_packed_avg(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps,
+                                             grad_scale, _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'adam_step_packed_avg')
+        return
     check(lib.ctgan_adam_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps, grad_scale,
                                      _stream()), 'adam_step_packed')
 
 
-def rmsprop_step(theta, g, ms, state, rho, eps, clip=0.0, grad_scale=1.0):
-    """In-place TF-RMSProp (+ clip to [-clip, clip] when clip > 0) on flat fp32 buffers; `state` = device float[4] {lr, -, -, skipped}."""
+def rmsprop_step(theta, g, ms, state, rho, eps, clip=0.0, grad_scale=1.0, avg=None, avg_rate=0.0):
+    """In-place TF-RMSProp (+ clip to [-clip, clip] when clip > 0) on flat fp32 buffers; `state` = device float[4] {lr, -, -, skipped}.
+    `avg`: as adam_step (the average sees the clipped weight)."""
     _need_dev(theta, g, ms, state)
     for t in (theta, g, ms):
         assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == theta.numel()
+    if avg is not None:
+        check(lib.ctgan_rmsprop_step_avg(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, _ptr(avg),
+                                         _check_avg(avg, theta, avg_rate), _stream()), 'rmsprop_step_avg')
+        return
     check(lib.ctgan_rmsprop_step(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, _stream()),
           'rmsprop_step')
 
 
-def rmsprop_step_packed(srcs, dst_offs, counts, flat, theta, ms, state, rho, eps, clip=0.0, grad_scale=1.0):
-    """pack(srcs -> flat) + rmsprop_step in one launch (len(srcs) <= ADAM_PACKED_MAX)."""
+def rmsprop_step_packed(srcs, dst_offs, counts, flat, theta, ms, state, rho, eps, clip=0.0, grad_scale=1.0, avg=None, avg_rate=0.0):
+    """pack(srcs -> flat) + rmsprop_step in one launch (len(srcs) <= ADAM_PACKED_MAX); `avg`: as adam_step."""
     _need_dev(flat, theta, ms, state, *[t for t in srcs if t is not None])
     n = len(srcs)
     assert n <= ADAM_PACKED_MAX
@@ -1960,8 +1981,19 @@ def rmsprop_step_packed(srcs, dst_offs, counts, flat, theta, ms, state, rho, eps
     P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
     O = (ctypes.c_int64 * n)(*dst_offs)
     C = (ctypes.c_int64 * n)(*counts)
+    if avg is not None:
+        check(lib.ctgan_rmsprop_step_packed_avg(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale,
+                                                _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'rmsprop_step_packed_avg')
+        return
     check(lib.ctgan_rmsprop_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale, _stream()),
           'rmsprop_step_packed')
+
+
+def exchange_(a, b):
+    """Swap the contents of two equal-length contiguous fp32 tensors in place, in one launch (ctgan_exchange)."""
+    _need_dev(a, b)
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    check(lib.ctgan_exchange(_ptr(a), _ptr(b), a.numel(), _stream()), 'exchange')
 
 
 def pack(srcs, dst_offs, counts, flat):

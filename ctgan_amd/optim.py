@@ -6,6 +6,8 @@ apply_gradients (TF/CT_gan_cifar_resnet.py:333-338; TF/CT_gan_cifar.py:153-154);
 TF/CT_gan_64x64.py:548-576), with the 'wgan' weight clip fused into its update.  The flat parameter /
 gradient buffers double as the all-reduce buckets of the batch-sharded step (ddp.py).
 """
+import contextlib
+
 import torch
 
 from . import kernels as K
@@ -15,9 +17,16 @@ from . import tflib as lib
 class FlatAdam:
     kind = 'adam'
 
-    def __init__(self, named_params, beta1, beta2, eps=1e-8, state=None):
+    def __init__(self, named_params, beta1, beta2, eps=1e-8, state=None, avg_rate=0.0):
         """named_params: [(name, Parameter)] - the trainable variable list, in registry order.  state: optional float[4] device
-        slice to keep {lr, beta1^t, beta2^t, -} in (two optimizers sharing one allocation take a common learning rate in one fill)."""
+        slice to keep {lr, beta1^t, beta2^t, -} in (two optimizers sharing one allocation take a common learning rate in one fill).
+        avg_rate > 0 (NOT in the reference; the GAN trainers' `g_average`): keep `avg`, an exponential moving average of the weights laid
+        out like `theta` - avg <- avg + avg_rate (theta - avg), moved by the update's own launch (csrc/optim_rng.hip avg_elem), so a rate
+        of 1e-4 is a decay of 0.9999 - starting at a COPY of the weights (FlatAdamTheano's starts at zeros, as its script's does).  0: no
+        average, and nothing differs from an optimizer built without the argument (launches, slots(), state_dict())."""
+        self.avg_rate = float(avg_rate)
+        if not 0.0 <= self.avg_rate <= 1.0:
+            raise ValueError('avg_rate must be in [0, 1] (it is the rate 1 - decay, e.g. 1e-4 for a decay of 0.9999): %r' % (avg_rate,))
         self.names = [n for n, _ in named_params]
         self.params = [p for _, p in named_params]
         if not self.params:
@@ -38,6 +47,9 @@ class FlatAdam:
                 self.theta[off:off + n].copy_(p.reshape(-1))
                 p.data = self.theta[off:off + n].view(p.shape)
                 off += n
+        # (the subclass FlatAdamTheano keeps an average of its own, from zeros: this one is only allocated when the rate came in HERE)
+        self._avg_own = self.avg_rate > 0
+        self.avg = self.theta.clone() if self._avg_own else None
         # {lr, beta1^t, beta2^t, skipped}; TF initialises the power accumulators to beta (t = 1).  skipped: elements the update
         # kernels left untouched because their gradient was not finite, accumulated over the run (skipped())
         init = torch.tensor([0.0, self.beta1, self.beta2, 0.0], dtype=torch.float32, device=dev)
@@ -98,8 +110,16 @@ class FlatAdam:
     def step(self, grad_scale=1.0, rng=None):
         """theta <- Adam(theta, grad); then ONE launch advances the beta-power accumulators and, with `rng`, that stream's step
         counter (DeviceRNG.end_step)."""
-        K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale)
+        if self._avg_own:
+            K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale,
+                        avg=self.avg, avg_rate=self.avg_rate)
+        else:
+            K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale)
         self._end(rng)
+
+    def avg_views(self):
+        """[(name, view of the average shaped like the parameter)]"""
+        return [(n, self.avg[o:o + s].view(p.shape)) for n, p, o, s in zip(self.names, self.params, self.offsets, self.sizes)]
 
     def _end(self, rng):
         K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1)
@@ -113,8 +133,12 @@ class FlatAdam:
             self.gather_grads(grads)
             return self.step(grad_scale, rng)
         srcs = [g.contiguous() if g is not None else None for g in grads]
-        K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
-                           self.eps, grad_scale)
+        if self._avg_own:
+            K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
+                               self.eps, grad_scale, avg=self.avg, avg_rate=self.avg_rate)
+        else:
+            K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
+                               self.eps, grad_scale)
         self._keepalive = srcs
         self._end(rng)
 
@@ -128,8 +152,24 @@ class FlatAdam:
         return norm
 
     def slots(self):
-        """The device tensors a step writes besides the weights: what a graph capture's warm-up steps must leave as they found them."""
-        return [self.m, self.v, self.state]
+        """The device tensors a step writes besides the weights: what a graph capture's warm-up steps must leave as they found them (the
+        average too: on a resumed run avg != theta, and a step at learning rate 0 still moves it)."""
+        return [self.m, self.v, self.state] + self._avg_slot()
+
+    def _avg_slot(self):
+        return [self.avg] if self._avg_own else []
+
+    def _avg_state(self, sd):
+        if self._avg_own:
+            sd['avg'] = self.avg.cpu().clone()
+        return sd
+
+    def _load_avg(self, sd):
+        """checkpoint.load restores the parameters BEFORE the optimizers, so `theta` already holds the loaded weights here: a state
+        without 'avg' (a checkpoint of a run that kept none) starts the average at them - averaging can be switched on at a resume.
+        A state with 'avg' loaded into an optimizer that keeps none ignores it."""
+        if self._avg_own:
+            self.avg.copy_(sd['avg'] if sd.get('avg') is not None else self.theta)
 
     def load_named_slots(self, m_by_name, v_by_name, t):
         """Overwrite the Adam slots from per-parameter tensors (teacher-forced parity tests, resume)."""
@@ -143,7 +183,8 @@ class FlatAdam:
         self.state[2] = self.beta2 ** (self.t + 1)
 
     def state_dict(self):
-        return {'kind': self.kind, 'm': self.m.cpu().clone(), 'v': self.v.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t}
+        return self._avg_state({'kind': self.kind, 'm': self.m.cpu().clone(), 'v': self.v.cpu().clone(), 'state': self.state.cpu().clone(),
+                                't': self.t})
 
     def _check_kind(self, sd):
         kind = sd.get('kind', 'adam')          # (checkpoints written before the tag are Adam's)
@@ -151,10 +192,34 @@ class FlatAdam:
             raise ValueError('optimizer state of a %s optimizer cannot be loaded into a %s optimizer (another MODE?)' % (kind, self.kind))
 
     def load_state_dict(self, sd):
+        """(Parameters first, then this: see _load_avg.)"""
         self._check_kind(sd)
         self.m.copy_(sd['m']); self.v.copy_(sd['v']); self.state.copy_(sd['state']); self.t = int(sd['t'])
+        self._load_avg(sd)
         self.state[3:4].zero_()            # skipped() counts THIS session's skips: a resumed run does not inherit the saved run's (ADVICE r5)
         self._lr_last = None
+
+
+@contextlib.contextmanager
+def averaged(opt):
+    """`with averaged(trainer.g_opt):` - inside, the network's parameters hold the weight average (`opt.avg`) instead of the live weights:
+    sample and score from it.  Entry and exit are ONE launch each (kernels.exchange_) that swaps the CONTENTS of `theta` and `avg`, so
+    every address a captured graph or a pointer-keyed derived-filter cache has seen stays valid and no third buffer is needed, and each
+    bumps the network's registry epoch, so no derived / packed filter image built from the other set of weights is served.  A pure
+    exchange: after the exit - also when the body raised - both buffers hold the bits they held before, and graph replay goes on as if
+    the context had never been entered.  Do not step the optimizer inside.  ValueError when the optimizer keeps no average; not inside a
+    stream capture (the swap must happen once, now, and not at every replay)."""
+    if not getattr(opt, '_avg_own', False):
+        raise ValueError('averaged(): this optimizer keeps no weight average (g_average = 0)')
+    if opt.theta.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('averaged(): not inside a stream capture')
+    K.exchange_(opt.theta, opt.avg)
+    lib.bump_epoch(opt.group)
+    try:
+        yield opt
+    finally:
+        K.exchange_(opt.theta, opt.avg)
+        lib.bump_epoch(opt.group)
 
 
 class FlatRMSProp(FlatAdam):
@@ -168,9 +233,9 @@ class FlatRMSProp(FlatAdam):
 
     kind = 'rmsprop'
 
-    def __init__(self, named_params, rho=0.9, eps=1e-10, clip=None, state=None):
+    def __init__(self, named_params, rho=0.9, eps=1e-10, clip=None, state=None, avg_rate=0.0):
         # (FlatAdam's flat buffers, gather and end-of-step launch; its beta powers stay 1, so step_advance only moves the Philox counter)
-        super().__init__(named_params, 1.0, 1.0, eps, state)
+        super().__init__(named_params, 1.0, 1.0, eps, state, avg_rate)
         self.rho, self.clip = float(rho), float(clip or 0.0)
 
     def _alloc_slots(self, total, dev):
@@ -179,10 +244,14 @@ class FlatRMSProp(FlatAdam):
     def slots(self):
         """The device tensors a step writes besides the weights - and the weights too when the update clips them (a step at learning
         rate 0, as in a graph capture's warm-up, still clips)."""
-        return [self.ms, self.state] + ([self.theta] if self.clip > 0 else [])
+        return [self.ms, self.state] + ([self.theta] if self.clip > 0 else []) + self._avg_slot()
 
     def step(self, grad_scale=1.0, rng=None):
-        K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale)
+        if self._avg_own:
+            K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale,
+                           avg=self.avg, avg_rate=self.avg_rate)
+        else:
+            K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale)
         self._end(rng)
 
     def update(self, grads, grad_scale=1.0, rng=None):
@@ -190,8 +259,12 @@ class FlatRMSProp(FlatAdam):
             self.gather_grads(grads)
             return self.step(grad_scale, rng)
         srcs = [g.contiguous() if g is not None else None for g in grads]
-        K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
-                              grad_scale)
+        if self._avg_own:
+            K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
+                                  grad_scale, avg=self.avg, avg_rate=self.avg_rate)
+        else:
+            K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
+                                  grad_scale)
         self._keepalive = srcs
         self._end(rng)
 
@@ -203,11 +276,12 @@ class FlatRMSProp(FlatAdam):
         self.t = int(t)
 
     def state_dict(self):
-        return {'kind': self.kind, 'ms': self.ms.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t}
+        return self._avg_state({'kind': self.kind, 'ms': self.ms.cpu().clone(), 'state': self.state.cpu().clone(), 't': self.t})
 
     def load_state_dict(self, sd):
         self._check_kind(sd)
         self.ms.copy_(sd['ms']); self.state.copy_(sd['state']); self.t = int(sd['t'])
+        self._load_avg(sd)
         self.state[3:4].zero_()
         self._lr_last = None
 
@@ -225,11 +299,7 @@ class FlatAdamTheano(FlatAdam):
     def __init__(self, named_params, beta1, beta2, eps=1e-8, avg_rate=0.0, state=None):
         super().__init__(named_params, beta1, beta2, eps, state)
         self.avg_rate = float(avg_rate)
-        self.avg = torch.zeros_like(self.theta) if self.avg_rate > 0 else None
-
-    def avg_views(self):
-        """[(name, view of the average shaped like the parameter)]"""
-        return [(n, self.avg[o:o + s].view(p.shape)) for n, p, o, s in zip(self.names, self.params, self.offsets, self.sizes)]
+        self.avg = torch.zeros_like(self.theta) if self.avg_rate > 0 else None          # (its own: the base class was given no rate)
 
     def step(self, grad_scale=1.0, rng=None):
         assert grad_scale == 1.0

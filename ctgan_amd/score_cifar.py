@@ -410,6 +410,12 @@ def kernel_distance(samples, reference, subset=None):
     return _kernel_result(host, s)
 
 
+def _avg_kw(averaged):
+    """Keyword of Evaluator.score_draws for samples of the generator's weight average (nothing is passed for the live generator: the
+    call is then the one it always was)."""
+    return {'averaged': True} if averaged else {}
+
+
 def _module(te):
     if te:
         from . import ct_cifar_te
@@ -802,13 +808,14 @@ class ClassifierScore:
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
         return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls, ker)
 
-    def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None):
+    def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None, averaged=False):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
         draws them - on the trainer's EVALUATION stream, in statistic groups of 100, `chunk` (a multiple of 100; None: 1000) per
         generator call, the ResNet's labels drawn there unless given - and quantised with the script's SCORE_SCALE as the saved pixels
         are: the training stream, the weights and the optimizers stay untouched.  The ResNet's labels feed the accuracy count.  With a
         reference set the result also holds 'frechet', with a manifold set 'precision', 'recall', 'nn_dist' and 'nn_zero', with a kernel
-        reference set 'kid', 'kid_std' and 'kid_blocks', all from the features of the same classifier passes."""
+        reference set 'kid', 'kid_std' and 'kid_blocks', all from the features of the same classifier passes.  averaged (NOT in the reference):
+        the samples come from the generator's weight average (the trainer's `averaged()`; ValueError when it keeps none)."""
         ev, scale = self._evaluator(gan_trainer, 'score_generator')
         cfg = self.cfg
         cls = self._begin_class(ev.resnet, 'score_generator')      # (only the ResNet's generator is conditional: score_draws yields its labels)
@@ -818,7 +825,7 @@ class ClassifierScore:
         ker = self._begin_kernel(n, man)
         labels = self._labels(labels, n)
         r0, with_labels = 0, False
-        for x, lab in ev.score_draws(n, labels, chunk):
+        for x, lab in ev.score_draws(n, labels, chunk, **_avg_kw(averaged)):
             lab = None if lab is None else lab.contiguous()
             logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab, ker)
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
@@ -856,14 +863,14 @@ class ClassifierScore:
             K.moments_accum(self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1], s1, s2)
         return self._statistics(buf.cpu().numpy(), n)
 
-    def statistics_generator(self, gan_trainer, n, labels=None, chunk=None):
+    def statistics_generator(self, gan_trainer, n, labels=None, chunk=None, averaged=False):
         """The FeatureStatistics of `n` generator samples, drawn and quantised exactly as `score_generator` draws them (the evaluation
         stream; the training stream, the weights and the optimizers stay untouched)."""
         ev, scale = self._evaluator(gan_trainer, 'statistics_generator')
         if n < 1:
             raise ValueError('ClassifierScore.statistics_generator: no samples')
         buf, s1, s2 = self._begin_moments()
-        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
+        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk, **_avg_kw(averaged)):
             K.moments_accum(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1], s1, s2)
         return self._statistics(buf.cpu().numpy(), n)
 
@@ -891,7 +898,7 @@ class ClassifierScore:
             K.class_moments_accum(feat, labels[r0:r0 + chunk], st['cnt'], st['s1'], st['s2'])
         return self._class_statistics(st['cnt'].cpu().numpy(), st['mom'].cpu().numpy(), n)
 
-    def class_statistics_generator(self, gan_trainer, n, labels=None, chunk=None):
+    def class_statistics_generator(self, gan_trainer, n, labels=None, chunk=None, averaged=False):
         """The ClassStatistics of `n` samples of a conditional generator under the labels they were generated from, drawn and quantised
         exactly as `statistics_generator` draws them (the evaluation stream; the training stream, the weights and the optimizers stay
         untouched).  An unconditional generator's samples have no labels: ValueError."""
@@ -901,7 +908,7 @@ class ClassifierScore:
         if not ev.resnet:
             raise ValueError('ClassifierScore.class_statistics_generator: %s samples have no labels' % ev.name)
         st = self._begin_class_moments()
-        for x, lab in ev.score_draws(n, self._labels(labels, n), chunk):
+        for x, lab in ev.score_draws(n, self._labels(labels, n), chunk, **_avg_kw(averaged)):
             feat = self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1]
             K.class_moments_accum(feat, lab.contiguous(), st['cnt'], st['s1'], st['s2'])
         return self._class_statistics(st['cnt'].cpu().numpy(), st['mom'].cpu().numpy(), n)
@@ -928,7 +935,7 @@ class ClassifierScore:
             out[r0:r0 + chunk].copy_(self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1])
         return FeatureSet(out, self.fingerprint())
 
-    def features_generator(self, gan_trainer, n, labels=None, chunk=None):
+    def features_generator(self, gan_trainer, n, labels=None, chunk=None, averaged=False):
         """The FeatureSet of `n` generator samples, drawn and quantised exactly as `statistics_generator` draws them (the evaluation
         stream; the training stream, the weights and the optimizers stay untouched)."""
         ev, scale = self._evaluator(gan_trainer, 'features_generator')
@@ -936,7 +943,7 @@ class ClassifierScore:
             raise ValueError('ClassifierScore.features_generator: no samples')
         out = torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
         r0 = 0
-        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk):
+        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk, **_avg_kw(averaged)):
             out[r0:r0 + x.shape[0]].copy_(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1])
             r0 += x.shape[0]
         return FeatureSet(out, self.fingerprint())

@@ -649,6 +649,25 @@ int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, co
  * (TF/CT_gan_cifar_resnet.py:335-336) without one copy per variable.                                   */
 int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
                float* flat, ctgan_stream_t stream);
+/* Generator weight averaging (build-only: NOT in the reference; Yazici et al. 2019).  The four update entry points above with the
+ * average fused into the same launch: after the update - after the clip, and also for an element whose non-finite gradient was
+ * skipped - avg = avg + avg_rate * (theta - avg), two fp32 roundings, identical in the plain and the packed form.  theta, the slots,
+ * the bucket and state come out bit-identical to the entry point without the suffix.  avg == NULL or avg_rate outside (0, 1]:
+ * CTGAN_E_BADARG; the packed forms also want avg 16-byte aligned (CTGAN_E_UNSUPPORTED).                                              */
+int ctgan_adam_step_avg(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
+                        float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
+int ctgan_adam_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                               float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
+                               float* avg, float avg_rate, ctgan_stream_t stream);
+int ctgan_rmsprop_step_avg(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                           float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
+int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                                  float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip,
+                                  float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
+/* Swap the contents of two disjoint fp32 buffers of n elements in one launch (16-byte accesses when both pointers are 16-byte
+ * aligned, with the n % 4 last elements one by one; element by element otherwise; n == 0: nothing is launched; overlapping
+ * buffers: CTGAN_E_BADARG): the weights and their average change places without either address changing.                         */
+int ctgan_exchange(float* a, float* b, int64_t n, ctgan_stream_t stream);
 
 /* ---- RNG: Philox4x32-10 counter-based streams (tf.random_uniform / tf.random_normal /
  *      dropout masks :157,202,277,319).  counter base is read from device memory
