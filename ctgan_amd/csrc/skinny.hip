@@ -123,9 +123,11 @@ int ctgan_small_linear_fwd(const ctgan_conv_desc* d, const float* x, const float
                            hipStream_t st) {
     if (d->K == 1 && d->xs[1] == 1 && d->C % 4 == 0 && d->C >= 1024 && d->xs[0] % 4 == 0 &&
         (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0) {
+        ctgan_set_last_kernel("linear_gemv_fwd");
         hipLaunchKernelGGL(linear_gemv_fwd_kernel, dim3(d->N), dim3(256), 0, st, x, w, bias, y, d->C, (long long)d->xs[0], (long long)d->ys[0], relu);
         return ctgan_check_launch("linear_gemv_fwd");
     }
+    ctgan_set_last_kernel("linear_small_fwd");
     hipLaunchKernelGGL(linear_small_fwd_kernel, dim3((d->N + 3) / 4), dim3(256), 0, st, x, w, bias, y, d->N, d->C, d->K,
                        (long long)d->xs[0], (long long)d->xs[1], (long long)d->ys[0], (long long)d->ys[1], relu);
     return ctgan_check_launch("linear_small_fwd");
