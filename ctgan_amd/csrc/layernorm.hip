@@ -334,6 +334,11 @@ int chunks_of(long long D) { return (int)((D + CHUNK - 1) / CHUNK); }
 
 bool ln_ok(long long D, int C) { return C > 0 && C % 4 == 0 && (NT * 4) % C == 0 && D % C == 0; }
 
+// N is the y extent of every launch grid and n_labels the z extent of the by-label reduction: the runtime refuses a grid with more
+// than 65535 workgroups along y or z (invalid configuration), so such a call is refused here, before any launch
+constexpr int GRID_YZ_MAX = 65535;
+bool ln_grid_ok(int N, int n_labels) { return N <= GRID_YZ_MAX && n_labels <= GRID_YZ_MAX; }
+
 size_t ln_ws_bytes(int N, long long D, int C) {
     const size_t ch = (size_t)chunks_of(D);
     return (size_t)N * ch * 5 * sizeof(double) + (size_t)2 * N * ch * C * sizeof(float);
@@ -352,8 +357,9 @@ void reduce_rows(const float* rows, int N, int ch, int C, int nv, const int* lab
 template <bool COND>
 int ln_fwd(const char* what, const float* x, const float* scale, const float* offset, const int* labels, int n_labels, float* y, float* mean,
            float* rstd, int N, long long D, int C, float eps, int relu, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!x || !scale || !offset || !y || !mean || !rstd || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (!x || !scale || !offset || !y || !mean || !rstd || !ws || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (!ln_grid_ok(N, n_labels)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: N=%d n_labels=%d above the %d rows of a launch grid", what, N, n_labels, GRID_YZ_MAX);
     if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
     const dim3 grid(chunks_of(D), N);
     double* part = (double*)ws;
@@ -366,9 +372,10 @@ template <bool COND>
 int ln_bwd(const char* what, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd, const float* ymask,
            const int* labels, int n_labels, float* gx, float* gscale, float* goffset, int N, long long D, int C, void* ws, size_t ws_bytes,
            hipStream_t st) {
-    if (!gy || !x || !scale || !mean || !rstd || !gx || N <= 0 || (!gscale) != (!goffset) || (COND && (!labels || n_labels <= 0)))
+    if (!gy || !x || !scale || !mean || !rstd || !gx || !ws || N <= 0 || (!gscale) != (!goffset) || (COND && (!labels || n_labels <= 0)))
         return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (!ln_grid_ok(N, n_labels)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: N=%d n_labels=%d above the %d rows of a launch grid", what, N, n_labels, GRID_YZ_MAX);
     if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
     const int ch = chunks_of(D);
     const dim3 grid(ch, N);
@@ -384,8 +391,9 @@ template <bool COND>
 int ln_bwd2(const char* what, const float* u, const float* gy, const float* x, const float* scale, const float* mean, const float* rstd,
             const float* ymask, const int* labels, int n_labels, float* cot_gy, float* cot_x, float* cot_scale, int N, long long D, int C,
             void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!u || !gy || !x || !scale || !mean || !rstd || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (!u || !gy || !x || !scale || !mean || !rstd || !ws || N <= 0 || (COND && (!labels || n_labels <= 0))) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (!ln_ok(D, C)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: D=%lld C=%d outside the fused kernels", what, D, C);
+    if (!ln_grid_ok(N, n_labels)) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: N=%d n_labels=%d above the %d rows of a launch grid", what, N, n_labels, GRID_YZ_MAX);
     if (ws_bytes < ln_ws_bytes(N, D, C)) return ctgan_fail(CTGAN_E_BADARG, "%s: workspace too small", what);
     const int ch = chunks_of(D);
     const dim3 grid(ch, N);
@@ -455,6 +463,8 @@ int ctgan_layernorm_rows_gather(const float* table, const int32_t* labels, int32
 int ctgan_layernorm_rows_sum_by_label(const float* rows, const int32_t* labels, int32_t n_labels, float* out, int32_t N, int32_t C,
                                       ctgan_stream_t stream) {
     if (!rows || !labels || !out || N <= 0 || C <= 0 || n_labels <= 0) return ctgan_fail(CTGAN_E_BADARG, "layernorm_rows_sum_by_label: bad argument");
+    if (!ln_grid_ok(0, n_labels))
+        return ctgan_fail(CTGAN_E_UNSUPPORTED, "layernorm_rows_sum_by_label: n_labels=%d above the %d rows of a launch grid", n_labels, GRID_YZ_MAX);
     reduce_rows(rows, N, 1, C, 1, labels, n_labels, out, out, (hipStream_t)stream);
     return ctgan_check_launch("layernorm_rows_sum_by_label");
 }

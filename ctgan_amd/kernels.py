@@ -1304,9 +1304,14 @@ def _ln_dims(x):
     return None
 
 
+LN_MAX_SAMPLES = 65535          # GRID_YZ_MAX of csrc/layernorm.hip: N is the y extent of its launch grids
+
+
 def layernorm_supported(x):
+    """Whether the fused kernels take x; past LN_MAX_SAMPLES samples the entry points refuse and the caller composes the operator.  (A label
+    table of more than 65535 rows is refused by the fused and by the composed operator alike: it is the z extent of the by-label reduction.)"""
     d = _ln_dims(x)
-    return d is not None and bool(lib.ctgan_layernorm_supported(d[1], d[2]))
+    return d is not None and d[0] <= LN_MAX_SAMPLES and bool(lib.ctgan_layernorm_supported(d[1], d[2]))
 
 
 def _ln_ws(N, D, C, dev):

@@ -203,7 +203,8 @@ int ctgan_conv2d_repack_filter(const ctgan_conv_desc* d, const float* w, float* 
  *         given the cotangent u of gx returns the cotangents of gy, x and scale (NULL = not wanted)
  * Supported when C % 4 == 0 and 1024 % C == 0 (ctgan_layernorm_supported); otherwise CTGAN_E_UNSUPPORTED and the caller
  * composes the operator from ctgan_sample_sum / ctgan_mul / ctgan_rsqrt / ctgan_channel_affine.  ws: scratch of
- * ctgan_layernorm_workspace_bytes(N, D, C) bytes.                                                                       */
+ * ctgan_layernorm_workspace_bytes(N, D, C) bytes.  N (and, for the label-conditioned maps and the by-label row sum, n_labels)
+ * above 65535 is CTGAN_E_UNSUPPORTED too, returned before any launch: they are the y / z extents of the launch grids.      */
 int ctgan_layernorm_supported(int64_t D, int32_t C);
 size_t ctgan_layernorm_workspace_bytes(int32_t N, int64_t D, int32_t C);
 /* relu != 0: y = relu(Layernorm(x)) (the critics' Normalize -> nonlinearity, LS/wgan_LSUN_Bedrooms128.py:122-128) in the same

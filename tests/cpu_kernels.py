@@ -486,7 +486,8 @@ def layernorm_bwd2(u, gy, x, scale, mean, rstd, want_gy=True, want_x=True, want_
     # autograd through the double-precision restatement of layernorm_bwd as a function of (gy, x, scale)
     dims = tuple(range(1, x.dim()))
     cshp = [1, -1] + [1] * (x.dim() - 2)
-    eps = (1.0 / rstd.double() ** 2 - x.double().var(dim=dims, unbiased=False)).mean().item()
+    # per sample, so that var + eps is 1 / rstd^2 of that sample whatever the other samples' variances are (a constant one among them)
+    eps = (1.0 / rstd.double() ** 2 - x.double().var(dim=dims, unbiased=False)).reshape([-1] + [1] * (x.dim() - 1))
     with torch.enable_grad():
         gy_, x_, s_ = (t.detach().double().requires_grad_(True) for t in (gy, x, scale))
         m = x_.mean(dim=dims, keepdim=True)
