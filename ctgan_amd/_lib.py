@@ -11,7 +11,7 @@ import os
 # in the global symbol scope; loading ours first would bind the kernels to the system runtime and
 # leave the process with two HIP runtimes (streams / allocations of one are invalid in the other).
 import torch  # noqa: F401  (also the device-memory / stream provider of every wrapper)
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CTGAN_LIB') or os.path.join(_HERE, 'libctgan_hip.so')      # CTGAN_LIB: A/B builds (tools only)
@@ -275,6 +275,8 @@ SIGNATURES = {
     # all-pairs polynomial-kernel tile sums: the unbiased kernel distance (csrc/kid.hip)
     'ctgan_kernel_tile': (c_int, []),
     'ctgan_kernel_tile_sums': (c_int, [_p, c_int64, _p, c_int64, c_int32, c_double, c_double, c_int32, _p, _p]),
+    # differentiable augmentation of the critic's inputs, forward and adjoint (csrc/diffaug.hip)
+    'ctgan_diffaug': (c_int, [_p, _p, c_float, _p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_int32, c_uint64, c_uint64, _p, _p, _p]),
 }
 
 

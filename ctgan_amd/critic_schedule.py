@@ -95,14 +95,17 @@ EARLY_CONVS = ('Discriminator.1.Conv1', 'Discriminator.1.Conv2', 'Discriminator.
                'Discriminator.2.Shortcut')
 
 
-def critic_step(tr, R, real_int, labels, fake, early=None):
+def critic_step(tr, R, real_int, labels, fake, early=None, prep=None):
     """One critic step's losses AND parameter gradients -> (out, grads): `out` as Trainer.d_losses returns it, `grads` aligned with
     tr.d_params.  Must run inside torch.no_grad() and functional.deferred_wgrads() (the caller flushes the queue by leaving the latter).
 
     early (batch-sharded steps, SURVEY 5.7 / north star: "all-reduce overlapped with backward"): callable(dict name -> gradient).  The
     weight gradients of blocks 1-2 - a contiguous prefix of the flat bucket, 45 % of its bytes - are complete as soon as the
     penalty's double backward has left block 2, while six more launches of blocks 3-4 are still to come: with `early` they are flushed
-    there (functional.flush_partial: a grouped launch of their own) and handed over, so that their all-reduce can run under the rest."""
+    there (functional.flush_partial: a grouped launch of their own) and handed over, so that their all-reduce can run under the rest.
+
+    prep: the prepared (rf, interp, both) in place of the kernels.critic_prep launch - the trainer's augmented inputs
+    (Trainer.augmented_prep, which draws at the same two call sites)."""
     cfg = R.cfg
     B, D = cfg.BATCH_SIZE, cfg.DIM_D
     rng = tr.rng
@@ -111,7 +114,10 @@ def critic_step(tr, R, real_int, labels, fake, early=None):
     assert not torch.is_grad_enabled()
 
     # ------------------------------------------------------------------ phase A: forward (Trainer.d_losses' own launches)
-    rf, interp, both = K.critic_prep(real_int, fake, rng.seed, rng._sid(), rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
+    if prep is not None:
+        rf, interp, both = prep
+    else:
+        rf, interp, both = K.critic_prep(real_int, fake, rng.seed, rng._sid(), rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
     with F.tape_record() as trunk:
         R.DiscriminatorTrunk(both)
     y1, _c12, pool_x, h1, a2, _c22, h2 = trunk

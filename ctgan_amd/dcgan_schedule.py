@@ -42,8 +42,9 @@ def _dgrad(gy, w, g, N, out_strides=None):
     return K.conv_dgrad(gy, w, g, N, out_strides=out_strides, bias=None, wt=F._repacked(w, g))
 
 
-def critic_step(tr, real_in, fake):
-    """-> (out, grads aligned with tr.d_params); inside torch.no_grad() and functional.deferred_wgrads()."""
+def critic_step(tr, real_in, fake, real=None):
+    """-> (out, grads aligned with tr.d_params); inside torch.no_grad() and functional.deferred_wgrads().  real: the prepared reals
+    (the trainer's augmented ones) in place of real_prep(real_in)."""
     m, cfg = tr.mod, tr.mod.cfg
     c0, H = m.SCHEDULED_CRITIC['channels'], m.SCHEDULED_CRITIC['size']
     B, D = cfg.BATCH_SIZE, cfg.DIM
@@ -55,7 +56,8 @@ def critic_step(tr, real_in, fake):
     alpha_l, keep = 0.2, 0.5
 
     # ------------------------------------------------------------------ phase A
-    real = m.real_prep(real_in)
+    if real is None:
+        real = m.real_prep(real_in)
     alpha = rng.uniform(B, 1)
     interp = K.interpolate(real, fake, alpha)
     x4 = torch.cat([real, fake, real, interp], 0)                  # rows: real (masks A), fake (masks C), real (masks B) | x_hat

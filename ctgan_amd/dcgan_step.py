@@ -25,7 +25,7 @@ from . import kernels as K
 from . import tflib as lib
 from .optim import FlatAdam, FlatRMSProp
 from .optim import averaged as averaged_weights
-from .rng import DeviceRNG
+from .rng import AUG_FAKE, AUG_GEN, AUG_REAL, DeviceRNG
 
 
 import os as _os
@@ -58,6 +58,15 @@ def validate_mode(module_name, modes, mode):
         raise NotImplementedError('%s: MODE %r is not supported (supported: %s)' % (module_name, mode, ', '.join(sorted(modes))))
 
 
+def image_shape_of(module):
+    """(channels, height, width) of the flat NCHW images `module` trains on: SCHEDULED_CRITIC of the two DCGAN scripts, image_shape() of
+    the others."""
+    spec = getattr(module, 'SCHEDULED_CRITIC', None)
+    if spec is not None:
+        return (spec['channels'], spec['size'], spec['size'])
+    return tuple(module.image_shape())
+
+
 def mode_of(module):
     modes = getattr(module, 'MODES', None)
     if modes is None:                # the ResNet / LSUN scripts have no MODE switch: their CT objective
@@ -67,13 +76,20 @@ def mode_of(module):
 
 
 class DCGANTrainer:
-    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0):
+    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
         real_prep, feat_shapes).  g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights,
         moved inside its update launch (optim.FlatAdam / FlatRMSProp avg_rate), whatever the mode's optimizer.  It is the RATE, 1 - decay:
         g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it; the critic is never averaged.  0 (default): nothing differs
-        from a trainer built without the argument."""
+        from a trainer built without the argument.  augment (NOT in the reference): a Differentiable Augmentation policy (Zhao et al.
+        2020), a comma-separated subset of 'color,translation,cutout'; None / '': off, nothing differs.  The random transformation T
+        (kernels.diffaug) is applied to the reals and the fakes in front of the critic in the critic step - before the interpolation, so
+        the penalty is taken at the augmented x_hat - and to the samples in the generator step, whose gradient flows back through T.  Its
+        draws come from three reserved streams (rng.AUG_REAL / AUG_FAKE / AUG_GEN) at the trainer's own counter: no other draw of a step
+        moves, there is no state to checkpoint."""
         self.mod = module
+        self.aug_policy = K.diffaug_policy(augment)
+        self.aug_shape = image_shape_of(module) if self.aug_policy else None
         self.dev = lib._dev()
         self.rank, self.world, self.allreduce = rank, world_size, allreduce
         self.rng = DeviceRNG(seed, rank, self.dev)
@@ -129,6 +145,23 @@ class DCGANTrainer:
                     p.clamp_(-self.mode.clip, self.mode.clip)
             self._stats_to_clip = []
 
+    def aug_real(self, real_in):
+        """The critic step's reals: real_prep, then T on the stream AUG_REAL when augmenting (integer pixels: both in one launch)."""
+        m = self.mod
+        if not self.aug_policy:
+            return m.real_prep(real_in)
+        spec = self.rng.aug_spec(AUG_REAL)
+        denom = getattr(m, 'REAL_DENOM', None)
+        if denom is not None and real_in.dtype == torch.int32 and real_in.is_contiguous():
+            return K.diffaug(real_in, self.aug_shape, self.aug_policy, spec, denom=denom)       # bit-equal to the two launches below
+        return K.diffaug(m.real_prep(real_in).contiguous(), self.aug_shape, self.aug_policy, spec)
+
+    def aug_fake(self, fake):
+        """The critic step's (detached) fakes under T on the stream AUG_FAKE when augmenting."""
+        if not self.aug_policy:
+            return fake
+        return K.diffaug(fake.contiguous(), self.aug_shape, self.aug_policy, self.rng.aug_spec(AUG_FAKE))
+
     def _critic(self, x, u, groups):
         """The critic on rows made of `groups` reference calls (each its own BatchNorm statistics) - the non-CT objectives."""
         m = self.mod
@@ -141,9 +174,10 @@ class DCGANTrainer:
         with torch.no_grad():
             if fake is None:
                 fake = self._gen(B, rnd['z'] if rnd is not None else None)
-            real = m.real_prep(real_in)
+            real = self.aug_real(real_in)
+            fake_in = self.aug_fake(fake)
         u = [torch.cat([a, c], 0) for a, c in zip(rnd['u_real'], rnd['u_fake'])] if rnd is not None else None
-        d, _ = self._critic(torch.cat([real, fake], 0), u, 2 * self.towers)
+        d, _ = self._critic(torch.cat([real, fake_in], 0), u, 2 * self.towers)
         if self.mode.loss == 'wgan':
             cost = F.mean_diff(d, B, B, -1.0, 1.0)             # mean(D(fake)) - mean(D(real))
         else:
@@ -158,19 +192,20 @@ class DCGANTrainer:
         with torch.no_grad():
             if fake is None:        # `fake`: a batch drawn earlier from the same generator weights (generate_fakes)
                 fake = self._gen(B, rnd['z'] if rnd is not None else None)
-            real = m.real_prep(real_in)
+            real = self.aug_real(real_in)
+            fake_in = self.aug_fake(fake)       # (the samples themselves stay in out['fake'])
             alpha = rnd['alpha'] if rnd is not None else self.rng.uniform(B, 1)
-            interp = K.interpolate(real, fake, alpha)
+            interp = K.interpolate(real, fake_in, alpha)
         # rows of the batched passes: real (masks A), fake (masks C), real (masks B) - the order the fused loss heads read
         u = [torch.cat([a, c, b], 0) for a, b, c in zip(rnd['u_real'], rnd['u_real_'], rnd['u_fake'])] if rnd is not None else None
         if TRUNK_SHARE and hasattr(m, 'DiscriminatorTrunk') and getattr(m, 'critic_is_per_sample', lambda: True)():
             # the critic's layers before its first dropout are deterministic and per-sample: the two dropout passes over the real
             # batch share ONE evaluation of them - rows [real ; fake] through the trunk, rows [real, fake, real] through the tail
-            h = m.DiscriminatorTrunk(torch.cat([real, fake], 0))
+            h = m.DiscriminatorTrunk(torch.cat([real, fake_in], 0))
             h3 = F.rows_select(h, [(0, B), (B, 2 * B), (0, B)])
             d, f = m.DiscriminatorTail(h3, u=u, rng=None if rnd is not None else self.rng)
         else:
-            x3 = torch.cat([real, fake, real], 0)
+            x3 = torch.cat([real, fake_in, real], 0)
             # masks regenerated from the Philox stream inside the dropout kernels when none are injected: no uniform tensors
             d, f = m.Discriminator(x3, u=u) if rnd is not None else m.Discriminator(x3, rng=self.rng)
         interp.requires_grad_(True)
@@ -193,7 +228,11 @@ class DCGANTrainer:
                 fake = self._gen(self.mod.cfg.BATCH_SIZE, None)
         if DS.usable(self, rnd, fake, real_in):
             with torch.no_grad(), F.deferred_wgrads():
-                return DS.critic_step(self, real_in, fake)
+                if not self.aug_policy:
+                    return DS.critic_step(self, real_in, fake)
+                out, grads = DS.critic_step(self, real_in, self.aug_fake(fake), real=self.aug_real(real_in))
+                out['fake'] = fake
+                return out, grads
         out = self.d_losses(real_in, rnd, fake=fake)
         with F.deferred_wgrads():       # the queued weight gradients of the step: one grouped launch (functional._flush_groups)
             grads = torch.autograd.grad(out['cost'], self.d_params, grad_outputs=self.cost_seed().reshape(out['cost'].shape), allow_unused=True)
@@ -219,12 +258,14 @@ class DCGANTrainer:
     def g_losses(self, rnd=None):
         m, B = self.mod, self.mod.cfg.BATCH_SIZE
         x = self._gen(B, rnd['z'] if rnd is not None else None)
+        # the critic sees T(x) on the stream AUG_GEN when augmenting; the generator's gradient flows back through T (its adjoint launch)
+        xa = F.diffaug(x, self.aug_shape, self.aug_policy, self.rng.aug_spec(AUG_GEN)) if self.aug_policy else x
         with F.weight_grads(False):
             u = rnd['u_fake'] if rnd is not None else None
             if self.mode.loss == 'ct':
-                d, _ = m.Discriminator(x, u=u) if rnd is not None else m.Discriminator(x, rng=self.rng)
+                d, _ = m.Discriminator(xa, u=u) if rnd is not None else m.Discriminator(xa, rng=self.rng)
             else:
-                d, _ = self._critic(x, u, self.towers)
+                d, _ = self._critic(xa, u, self.towers)
         if self.mode.loss in ('ct', 'wgan'):
             cost = F.mean_diff(d, B, 0, -1.0, 0.0)                # -mean(D(fake))
         else:
@@ -313,14 +354,16 @@ def sample_grid(module, noise, trainer=None, averaged=False):
 
 
 def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
-          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0):
+          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None):
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
     (+ `slope_real` for gan_cifar); with a `classifier`, every `score_every` iterations the script's score series (and `frechet`
     when it is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a manifold); the fixed-noise sample grid every `sample_every`; checkpoints every `checkpoint_every`.  Flushed as the scripts do: the first five iterations and every
     `dev_every`-th.  `g_average` > 0 (NOT in the reference; DCGANTrainer): the generator's weight average is kept, scored after the live
-    generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  Returns the trainer."""
+    generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  `augment` (NOT in the reference; DCGANTrainer):
+    a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps; the dev cost, the sample
+    grids and the scores stay un-augmented.  Returns the trainer."""
     import os
     import time
 
@@ -331,7 +374,7 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     cfg = module.cfg
     iters = cfg.ITERS if iters is None else iters
     build_params(module)
-    trainer = DCGANTrainer(module, seed=seed, g_average=g_average)
+    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment)
     start = checkpoint.load(resume, trainer) if resume else 0
     first = next_batch()
     eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)

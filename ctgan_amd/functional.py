@@ -930,6 +930,42 @@ class FilterFoldFn(Function):
         return FilterSpreadFn.apply(g, ctx.scale, ctx.flip), None, None
 
 
+class DiffAugFn(Function):
+    """Differentiable augmentation T of flat NCHW images (kernels.diffaug; NOT in the reference).  T is affine per image, so its backward
+    is one more launch of the same kernel on the same draws: the adjoint, DiffAugAdjFn."""
+
+    @staticmethod
+    def forward(ctx, x, shape, policy, spec):
+        ctx.shape, ctx.policy, ctx.spec = shape, policy, spec
+        return K.diffaug(x.contiguous(), shape, policy, spec)
+
+    @staticmethod
+    def backward(ctx, g):
+        return DiffAugAdjFn.apply(g, ctx.shape, ctx.policy, ctx.spec), None, None, None
+
+
+class DiffAugAdjFn(Function):
+    """The adjoint of T's linear part.  Its own backward is that linear part - the forward with the brightness off - so gradients through
+    T are right under create_graph=True to any order."""
+
+    @staticmethod
+    def forward(ctx, g, shape, policy, spec):
+        ctx.shape, ctx.policy, ctx.spec = shape, policy, spec
+        return K.diffaug(g.contiguous(), shape, policy, spec, adjoint=True)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return DiffAugFn.apply(gg, ctx.shape, ctx.policy | K.DIFFAUG_NO_BRIGHTNESS, ctx.spec), None, None, None
+
+
+def diffaug(x, shape, policy, spec):
+    """T(x): x [n, c*h*w] flat NCHW (or [n, c, h, w]), shape = (c, h, w), policy the mask of kernels.diffaug_policy, spec = (seed, stream
+    id, step counter).  A mask of 0 returns x itself."""
+    if not policy:
+        return x
+    return DiffAugFn.apply(x, tuple(shape), int(policy), spec)
+
+
 def conv2d_mean_pool(x, w, b=None, resid=None, relu_in=False):
     """mean_pool2(conv2d(x, w) + b) [+ resid] as ONE stride-2 conv (TF/CT_gan_cifar_resnet.py:89-92)."""
     R, S, C, Kout = w.shape

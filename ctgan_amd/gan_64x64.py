@@ -76,9 +76,18 @@ def configure(**kw):
     return cfg
 
 
+# real_prep's divisor: with it the trainer's augmentation converts the integer pixels on load (kernels.diffaug, one launch for both)
+REAL_DENOM = 255.0
+
+
 def real_prep(real_data_int):
     """:483  2*((int/255.)-.5)"""
-    return K.real_prep(real_data_int, None, 255.0)
+    return K.real_prep(real_data_int, None, REAL_DENOM)
+
+
+def image_shape():
+    """(channels, height, width) of the flat NCHW images (the trainer's augmentation, kernels.diffaug)."""
+    return (3, 64, 64)
 
 
 def feat_shapes():

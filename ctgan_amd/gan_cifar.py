@@ -51,9 +51,13 @@ def LeakyReLU(x, alpha=0.2):
     return F.leaky_relu(x, alpha)
 
 
+# real_prep's divisor: with it the trainer's augmentation converts the integer pixels on load (kernels.diffaug, one launch for both)
+REAL_DENOM = 255.0
+
+
 def real_prep(real_data_int):
     """:103  2*((int/255.)-.5)"""
-    return K.real_prep(real_data_int, None, 255.0)
+    return K.real_prep(real_data_int, None, REAL_DENOM)
 
 
 def feat_shapes():

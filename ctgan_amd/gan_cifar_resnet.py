@@ -23,7 +23,7 @@ from . import kernels as K
 from . import tflib as lib
 from .optim import FlatAdam
 from .optim import averaged as averaged_weights
-from .rng import DeviceRNG
+from .rng import AUG_FAKE, AUG_GEN, AUG_REAL, DeviceRNG
 from .tflib.ops import batchnorm as _bn
 from .tflib.ops import cond_batchnorm as _cbn
 from .tflib.ops import conv2d as _conv2d
@@ -351,6 +351,11 @@ def build_params(device=None):
         Discriminator(x, lab, 1.0, 1.0, 1.0)
 
 
+def image_shape():
+    """(channels, height, width) of the flat NCHW images (the trainer's augmentation, kernels.diffaug)."""
+    return (3, 32, 32)
+
+
 def _cat_rows(a, b):
     return torch.cat([a, b], dim=0)
 
@@ -458,10 +463,17 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
 class Trainer:
     """Owns the optimizers, the random streams and the D/G step (the session of the reference)."""
 
-    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0):
+    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None):
         """g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights, moved inside its update
         launch (optim.FlatAdam avg_rate).  It is the RATE, 1 - decay: g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it.
-        The critic is never averaged.  0 (default): nothing differs from a trainer built without the argument."""
+        The critic is never averaged.  0 (default): nothing differs from a trainer built without the argument.
+        augment (NOT in the reference): a Differentiable Augmentation policy (Zhao et al. 2020), a comma-separated subset of
+        'color,translation,cutout'; None / '': off, nothing differs.  The random transformation T (kernels.diffaug) is applied to the
+        dequantised reals and to the fakes in front of the critic in the critic step - before the interpolation - and to the samples of
+        both towers in the generator step, whose gradient flows back through T.  Its draws come from three reserved streams
+        (rng.AUG_REAL / AUG_FAKE / AUG_GEN) at the trainer's own counter: no other draw moves, there is nothing to checkpoint."""
+        self.aug_policy = K.diffaug_policy(augment)
+        self.aug_shape = image_shape()
         self.dev = lib._dev()
         self.rank, self.world = rank, world_size
         self.allreduce = allreduce            # callable(flat_tensor) -> None, sums across ranks (ddp.py)
@@ -491,6 +503,21 @@ class Trainer:
         return self._one.reshape(cost.shape)
 
     # ------------------------------------------------------------------ losses
+    def augmented_prep(self, real_int, fake, rnd=None):
+        """The critic step's inputs with the augmentation on -> (rf [2B,d] = [T(real) ; T(fake)], interp [B,d], both [3B,d], the buffer they
+        are adjacent views of) - what kernels.critic_prep returns without it, unfused: dequantisation draw, real_prep, the two diffaug
+        launches, alpha draw, interpolate, one row copy.  The call sites are numbered as in d_losses' unfused branch (and as critic_prep's
+        two): dequantisation first, alpha second."""
+        B, rng = cfg.BATCH_SIZE, self.rng
+        deq = rnd['dequant'] if rnd is not None else rng.uniform(B, cfg.OUTPUT_DIM, lo=0.0, hi=1. / 128)
+        both = torch.empty(3 * B, cfg.OUTPUT_DIM, dtype=torch.float32, device=real_int.device)
+        rf, interp = both[:2 * B], both[2 * B:]
+        K.diffaug(K.real_prep(real_int, deq, 256.0), self.aug_shape, self.aug_policy, rng.aug_spec(AUG_REAL), out=both[:B])
+        K.diffaug(fake.contiguous(), self.aug_shape, self.aug_policy, rng.aug_spec(AUG_FAKE), out=both[B:2 * B])
+        alpha = rnd['alpha'] if rnd is not None else rng.uniform(B, 1)
+        interp.copy_(K.interpolate(both[:B], both[B:2 * B], alpha))
+        return rf, interp, both
+
     def d_losses(self, real_int, labels, rnd=None, fake=None):
         """Critic loss graph :194-305.  `rnd` (parity mode) injects every random draw; see
         oracle/steps.make_rnd_resnet_d for the keys and shapes."""
@@ -503,18 +530,25 @@ class Trainer:
                 fake = Generator(B, labels, noise=z, groups=2, rng=rng)
             if PREP_FUSION and rnd is None and cfg.OUTPUT_DIM % 4 == 0 and real_int.is_contiguous() and fake.is_contiguous():
                 # dequantised reals, x_hat and the [real ; fake] batch in one launch (same Philox call sites as below)
-                rf, interp, both = K.critic_prep(real_int, fake, rng.seed, rng._sid(), rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
+                if self.aug_policy:
+                    rf, interp, both = self.augmented_prep(real_int, fake)
+                else:
+                    rf, interp, both = K.critic_prep(real_int, fake, rng.seed, rng._sid(), rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
                 real = rf[:B]
                 if TRUNK_SHARE and not cfg.NORMALIZATION_D and _heads_fusable(rnd, rng):
                     # blocks 1-2 once for [real ; fake ; x_hat]: the two passes below replay rows of it (F.tape_record)
                     with F.tape_record() as tape:
                         DiscriminatorTrunk(both)
             else:
-                deq = rnd['dequant'] if rnd is not None else rng.uniform(B, cfg.OUTPUT_DIM, lo=0.0, hi=1. / 128)
-                real = K.real_prep(real_int, deq, 256.0)
-                alpha = rnd['alpha'] if rnd is not None else rng.uniform(B, 1)
-                interp = K.interpolate(real, fake, alpha)
-                rf = _cat_rows(real, fake)
+                if self.aug_policy:
+                    rf, interp, _ = self.augmented_prep(real_int, fake, rnd)
+                    real = rf[:B]
+                else:
+                    deq = rnd['dequant'] if rnd is not None else rng.uniform(B, cfg.OUTPUT_DIM, lo=0.0, hi=1. / 128)
+                    real = K.real_prep(real_int, deq, 256.0)
+                    alpha = rnd['alpha'] if rnd is not None else rng.uniform(B, 1)
+                    interp = K.interpolate(real, fake, alpha)
+                    rf = _cat_rows(real, fake)
 
         # gradient penalty :277-286, issued FIRST.  The critic is piecewise linear (no normalisation in D), so the penalty reaches the
         # weights only through the backward ops: skip the forward's own wgrads.  (The branch on a side stream - parallel hipGraph
@@ -617,7 +651,8 @@ class Trainer:
                 fake = Generator(cfg.BATCH_SIZE, labels, groups=2, rng=self.rng)
         if CS.usable(_this_module(), rnd, self.rng, real_int, fake):
             with torch.no_grad(), F.deferred_wgrads():
-                return CS.critic_step(self, _this_module(), real_int, labels, fake, early=early)
+                prep = self.augmented_prep(real_int, fake) if self.aug_policy else None
+                return CS.critic_step(self, _this_module(), real_int, labels, fake, early=early, prep=prep)
         out = self.d_losses(real_int, labels, rnd, fake=fake)
         with F.deferred_wgrads():
             grads = torch.autograd.grad(out['cost'], self.d_params, grad_outputs=self.cost_seed(out['cost']), allow_unused=True)
@@ -635,17 +670,19 @@ class Trainer:
             fake_labels = rng.labels(n, 10)
             z, u = None, None
         x = Generator(n, fake_labels, noise=z, groups=2, rng=rng)
+        # the critic sees T(x) - one call over both towers' rows - when augmenting; the generator's gradient flows back through T
+        xa = F.diffaug(x, self.aug_shape, self.aug_policy, rng.aug_spec(AUG_GEN)) if self.aug_policy else x
         use_ac = cfg.CONDITIONAL and cfg.ACGAN
         with F.weight_grads(False):                      # only dD/dx is needed from the critic
             if _heads_fusable(rnd, rng):
                 # mean + both Linear heads + the loss: two launches forward, one backward (F.gen_tail_heads)
-                y = DiscriminatorTailBody(DiscriminatorTrunk(x), 0.8, 0.5, 0.5, rng=rng, mask_done=True)
+                y = DiscriminatorTailBody(DiscriminatorTrunk(xa), 0.8, 0.5, 0.5, rng=rng, mask_done=True)
                 cost, _ = F.gen_tail_heads(y, lib.param('Discriminator.Output.W'), lib.param('Discriminator.Output.b'),
                                            lib.param('Discriminator.ACGANOutput.W') if use_ac else None,
                                            lib.param('Discriminator.ACGANOutput.b') if use_ac else None, fake_labels,
                                            cfg.ACGAN_SCALE_G if use_ac else 0.0, 1.0 / 0.5)
                 return {'cost': cost, 'samples': x}
-            d, _, a = Discriminator(x, fake_labels, 0.8, 0.5, 0.5, u=u, rng=rng)
+            d, _, a = Discriminator(xa, fake_labels, 0.8, 0.5, 0.5, u=u, rng=rng)
         cost = F.mean_diff(d, n, 0, -1.0, 0.0)
         if use_ac:
             ce, _ = F.softmax_cross_entropy(a, fake_labels)
@@ -760,7 +797,7 @@ class Trainer:
 
 
 def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100,
-          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0):
+          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0, augment=None):
     """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434): CIFAR-10 generator factories, `time` /
     `cost` / `wgan` / `acgan` / `acc_real` / `acc_fake` series (train_log.Series), fixed-noise sample grids every
     `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
@@ -768,7 +805,9 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     graph needs a network) - `inception_50k` / `inception_50k_std` every `score_every` iterations (:414-418), and
     `frechet` when the classifier is a score_cifar.ClassifierScore with a reference, `precision` / `recall` / `nn_dist` when it has a
     manifold (evaluate.record_score).  `g_average` > 0 (NOT in the reference; Trainer): the generator's weight average is kept, scored
-    after the live generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`."""
+    after the live generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  `augment` (NOT in the
+    reference; Trainer): a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps;
+    the dev cost, the sample grids and the scores stay un-augmented."""
     import os
     import time
 
@@ -778,7 +817,7 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     from .train_log import Series
     iters = cfg.ITERS if iters is None else iters
     build_params()
-    trainer = Trainer(seed=seed, g_average=g_average)
+    trainer = Trainer(seed=seed, g_average=g_average, augment=augment)
     start = checkpoint.load(resume, trainer) if resume else 0
     eng = GraphedTrainer(trainer, use_graphs=use_graphs)
     ev = evaluate.Evaluator(trainer)

@@ -57,9 +57,18 @@ def lr(iteration):
     return cfg.LR * (max(0.0, 1.0 - float(iteration) / cfg.ITERS) if cfg.DECAY else 1.0)
 
 
+# real_prep's divisor: with it the trainer's augmentation converts the integer pixels on load (kernels.diffaug, one launch for both)
+REAL_DENOM = 255.0
+
+
 def real_prep(real_data_int):
     """:221  2*((int/255.)-.5)"""
-    return K.real_prep(real_data_int, None, 255.0)
+    return K.real_prep(real_data_int, None, REAL_DENOM)
+
+
+def image_shape():
+    """(channels, height, width) of the flat NCHW images (the trainer's augmentation, kernels.diffaug)."""
+    return (3, 128, 128)
 
 
 def feat_shapes():

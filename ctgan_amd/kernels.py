@@ -2553,6 +2553,57 @@ def aug_gather(data, idx, lut, win, pad, spec=None, offset=None, flip=False, rot
     return out
 
 
+# ---------------------------------------------------------------- differentiable augmentation (csrc/diffaug.hip; NOT in the reference)
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
+DIFFAUG_BITS = {'color': DIFFAUG_COLOR, 'translation': DIFFAUG_TRANSLATION, 'cutout': DIFFAUG_CUTOUT}
+# kept Python-side (functional.DiffAugAdjFn): the forward WITHOUT its brightness - the linear part of T, the adjoint's own adjoint;
+# it reaches the library as adjoint = 2, never inside the policy mask
+DIFFAUG_NO_BRIGHTNESS = 8
+
+
+def diffaug_policy(policy):
+    """'color,translation,cutout' (any comma-separated subset, in any order; None / '' : nothing) -> the kernel's bit mask."""
+    mask = 0
+    for tok in (policy or '').split(','):
+        tok = tok.strip()
+        if not tok:
+            continue
+        if tok not in DIFFAUG_BITS:
+            raise ValueError('diffaug: unknown policy %r (known: %s)' % (tok, ', '.join(DIFFAUG_BITS)))
+        mask |= DIFFAUG_BITS[tok]
+    return mask
+
+
+def diffaug(x, shape, policy, spec, adjoint=False, denom=None, params=None, out=None):
+    """Differentiable augmentation of n flat NCHW images: x [n, c*h*w] (or [n, c, h, w]) with shape = (c, h, w), policy the bit mask of
+    diffaug_policy (| DIFFAUG_NO_BRIGHTNESS: the forward's linear part), spec = (seed, stream id, step counter) as aug_gather takes it:
+    image r is transformed by values 8r .. 8r+7 of that uniform stream.  adjoint: x is the gradient of the forward's result, the result
+    the gradient of its input.  x int32 with `denom`: pixels, converted on load as real_prep(x, None, denom) does (forward only).
+    params: optional float32 [n, 8] that receives the resolved (b, s, q, ty, tx, y0, x0, policy) per image.  -> out, shaped like x."""
+    _need_dev(x, params, out)
+    c, h, w = (int(v) for v in shape)
+    assert x.is_contiguous() and x.dim() in (2, 4) and x.numel() == x.shape[0] * c * h * w, 'x is [n, c*h*w] or [n, c, h, w], contiguous'
+    n = x.shape[0]
+    is_int = x.dtype == torch.int32
+    assert is_int or x.dtype == torch.float32
+    if is_int:
+        assert denom is not None and not adjoint, 'integer pixels need denom and are a forward input'
+    else:
+        assert denom is None, 'denom goes with integer pixels'
+    policy = int(policy)
+    mode = 1 if adjoint else (2 if policy & DIFFAUG_NO_BRIGHTNESS else 0)
+    seed, sid, ctr = spec
+    assert ctr is None or (ctr.is_cuda and ctr.dtype == torch.int64)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous() and out.data_ptr() != x.data_ptr()
+    if params is not None:
+        assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (n, 8)
+    check(lib.ctgan_diffaug(None if is_int else _ptr(x), _ptr(x) if is_int else None, float(denom) if is_int else 1.0, _ptr(out), n, c, h, w,
+                            policy & ~DIFFAUG_NO_BRIGHTNESS, mode, int(seed), int(sid), _ptr(ctr), _ptr(params), _stream()), 'diffaug')
+    return out
+
+
 # ---------------------------------------------------------------- temporal-ensembling classifier (csrc/ssl_te.hip; ct_cifar_te.py)
 def _te_head_args(logits, feat, labels, idx, targets, targets2, B):
     _need_dev(logits, feat, labels, idx, targets, targets2)

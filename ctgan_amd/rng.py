@@ -10,6 +10,13 @@ import torch
 from . import kernels as K
 
 
+# Reserved stream ids OUTSIDE the per-step call-site numbering (as ct_cifar.SID_AUG_LAB / SID_AUG_UNL): the draws of the differentiable
+# augmentation (kernels.diffaug) of the critic step's reals and fakes and of the generator step's samples.  _sid() never hands one out,
+# so switching the augmentation on moves no other draw of a step.
+AUG_REAL, AUG_FAKE, AUG_GEN = 0xFF00, 0xFF01, 0xFF02
+SID_RESERVED = 0xFF00          # first call-site index _sid() refuses
+
+
 class DeviceRNG:
     def __init__(self, seed=2024, rank=0, device=None):
         self.seed = int(seed)
@@ -21,9 +28,14 @@ class DeviceRNG:
     def _sid(self):
         s = self._site
         self._site += 1
-        if s >= (1 << 16):
+        if s >= SID_RESERVED:
             raise RuntimeError('too many random call sites in one step')
         return (self.rank << 16) | s
+
+    def aug_spec(self, sid):
+        """(seed, stream id, step counter) of one of the reserved augmentation streams AUG_REAL / AUG_FAKE / AUG_GEN on this rank."""
+        assert sid in (AUG_REAL, AUG_FAKE, AUG_GEN)
+        return (self.seed, (self.rank << 16) | sid, self.ctr)
 
     def begin_step(self):
         """Call-site numbering restarts with every step (keeps captured and eager runs aligned)."""

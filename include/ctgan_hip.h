@@ -920,6 +920,27 @@ int ctgan_kernel_tile(void);
 int ctgan_kernel_tile_sums(const float* a, int64_t m, const float* b, int64_t n, int32_t d, double gamma, double coef0, int32_t exclude_diag,
                            double* sums, ctgan_stream_t stream);
 
+/* ---- differentiable augmentation of the critic's inputs (csrc/diffaug.hip; Zhao et al. 2020 - NOT in the reference) --------------
+ * The policy `color,translation,cutout` on flat NCHW fp32 images [n, c, h, w], one workgroup per image.  Exactly one of x (fp32) and
+ * x_int (int32 pixels, forward only: converted on load as 2 (v / denom - .5), bit-equal to ctgan_real_prep followed by this call) is
+ * given.  policy is a bit mask: 1 colour, 2 translation, 4 cutout; 0 copies.  Image r takes values 8r .. 8r+7 of the uniform stream
+ * ctgan_rng_uniform(., seed, stream_id, ctr) writes: u0..u2 brightness b = u0 - .5, saturation s = 2 u1, contrast q = u2 + .5; u3, u4
+ * the shift ty = min(int((2 S_h + 1) u3), 2 S_h) - S_h with S_h = int(h/8 + .5) (tx: u4, w); u5, u6 the centre of the cut rectangle
+ * oy = min(int(n_h u5), n_h - 1), rows [oy - k_h/2, oy - k_h/2 + k_h) clipped to the image, k_h = int(h/2 + .5),
+ * n_h = h + (1 - k_h % 2) (columns: u6, w).  A bit that is off fixes its parameters at the identity.
+ * adjoint = 0, the forward: x1 = x + b; x2 = s x1 + (1-s) mean_c(x1); x3 = q x2 + (1-q) (mean(x) + b);
+ *   y[c,i,j] = x3[c,i-ty,j-tx] where that pixel exists and (i,j) is not cut, else 0.
+ * adjoint = 1 (input: the gradient g of y): gt[c,i,j] = g[c,i+ty,j+tx] where that pixel exists and is not cut, else 0;
+ *   gx = q (s gt + (1-s) mean_c(gt)) + (1-q) mean(gt).
+ * adjoint = 2: the forward without the brightness (b = 0) - the linear part of T, which is the adjoint of the adjoint.
+ * The image mean is summed in one fixed order (per lane serially, then an LDS tree; diffaug.hip's header): the same bits on every run.
+ * params (may be NULL) [n, 8] receives per image (b, s, q, ty, tx, y0, x0, policy): y0 / x0 the first cut row / column, h / w when
+ * nothing is cut.  A null y, both or neither of x / x_int, x_int with adjoint = 1, n, c, h, w < 1, c > 16, policy > 7,
+ * stream_id >= 2^32 or denom == 0: CTGAN_E_BADARG, nothing is launched.                                                           */
+int ctgan_diffaug(const float* x, const int32_t* x_int, float denom, float* y, int32_t n, int32_t c, int32_t h, int32_t w,
+                  uint32_t policy, int32_t adjoint, uint64_t seed, uint64_t stream_id, const uint64_t* ctr, float* params,
+                  ctgan_stream_t stream);
+
 
 #ifdef __cplusplus
 }
