@@ -6,6 +6,9 @@ is captured once into a hipGraph and replayed.  Replay-safety: every random draw
 step counter from device memory, Adam reads lr / beta powers from device memory, inputs live in
 static buffers.  With world_size > 1 the all-reduce and the Adam kernels stay outside the graph.
 """
+import os as _os
+import time
+
 import torch
 
 from . import functional as F
@@ -13,8 +16,6 @@ from . import kernels as K
 from . import gan_cifar_resnet as R
 from . import tflib as lib
 
-
-import os as _os
 # A/B switch: the whole iteration (G step + fake batches + N_CRITIC critic steps) as ONE hipGraph when world == 1
 ITERATION_GRAPH = _os.environ.get('CTGAN_ITERATION_GRAPH', '1') != '0'
 # world > 1: capture the gradient all-reduce (RCCL supports stream capture) and the Adam step INSIDE the step graphs, so that the
@@ -50,11 +51,98 @@ def quiesce_collectives():
     capture raised a HIP error in the watchdog thread on this stack even under THREAD_LOCAL mode (2 of 3 runs once the warm-up got
     shorter).  After a device synchronize every item is complete: one poll period later the list is empty and nothing is polled
     while capturing (collectives enqueued under capture are never put on that list)."""
-    import time
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and torch.cuda.is_available():
         torch.cuda.synchronize()
         time.sleep(0.35)
+
+
+def _capture_graphs(eng, warmup, opts, extra_bufs, bodies, warm=None, it_body=None):
+    """THE capture protocol of every Graphed* wrapper: `warmup` passes over the callables of `warm` (default: the bodies, in order) on one
+    side stream, then each (graph attribute, result attribute or None, body) of `bodies` captured in order and stored on `eng`, then
+    the optional whole-iteration graph `it_body` (-> eng.it_graph / it_out, or eng.it_graph_error).
+
+    Everything a body changes besides its outputs is restored afterwards (also when capture fails): the optimizers' slots and host step
+    counts, and `extra_bufs` - the Philox step counter, prediction tables, moving statistics - so a captured trainer continues exactly
+    where the eager one would (checkpoint resume, graph-vs-eager parity tests).
+
+    Each graph owns a PRIVATE memory pool.  The graphs are replayed in an order other than the capture order (g, f, then d x N_CRITIC)
+    and their outputs outlive other graphs' replays - `fake_all` is read by all N_CRITIC critic replays.  With one shared pool a block
+    freed while capturing graph A is handed to graph B as storage of a live OUTPUT, and A's next replay scribbles over it (round 1: the
+    fake batches of critic steps 2..5 were whatever the first critic replay left in that memory, hence a critic cost of -6e18).  A
+    private pool costs ~3 GB per graph of the 288 GB and makes an output valid until its own graph is replayed again."""
+    def capture(body):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, **_capture_kw()):
+            return g, body()
+    K.reset_capture_workspaces()
+    bufs = [b for o in opts for b in o.slots()] + extra_bufs
+    snap = [b.clone() for b in bufs]
+    steps = [o.t for o in opts]
+    for o in opts:
+        o.set_lr(0.0)       # warm-up / capture passes must not move the weights
+    try:
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                for body in warm or [b for _, _, b in bodies]:
+                    body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        quiesce_collectives()
+        for g_name, out_name, body in bodies:
+            g, out = capture(body)
+            setattr(eng, g_name, g)
+            if out_name is not None:
+                setattr(eng, out_name, out)
+        if it_body is not None:
+            # Seven graph launches per iteration leave ~150 us of idle GPU at each boundary (profiles/r02_steady_state_resnet_v2.txt:
+            # 1.07 ms of 20.5 ms; the DCGAN engine: ~20 gaps of 8-20 us, 4 % of the iteration); one graph per iteration has one boundary.
+            # Optional: if only this capture fails (one more private pool), the per-step graphs stay in use.
+            try:
+                eng.it_graph, eng.it_out = capture(it_body)
+            except Exception as e:
+                eng.it_graph = eng.it_out = None
+                eng.it_graph_error = '%s: %s' % (type(e).__name__, e)
+                torch.cuda.synchronize()
+                # an exception inside an active capture can leave the stream / pools in a bad state: prove the per-step graphs
+                # still replay (weights do not move: the learning rate is 0 here) before relying on them
+                for g_name, _, _ in bodies:
+                    getattr(eng, g_name).replay()
+                torch.cuda.synchronize()
+    finally:
+        torch.cuda.synchronize()
+        for b, sn in zip(bufs, snap):
+            b.copy_(sn)
+        for o, n in zip(opts, steps):
+            o.t, o._lr_last = n, None
+        torch.cuda.synchronize()
+
+
+def _capture_gan_graphs(eng, warmup, f_warm, d_body, g_body):
+    """_capture_graphs for the two GAN engines: the critic and generator graphs, then - when the fake batches of an iteration come from one
+    generator forward (warmed up by `f_warm`, ahead of the two steps) - the fake-batch graph and, with Adam inside the graphs, the
+    whole-iteration graph."""
+    t = eng.t
+    warm, bodies = [d_body, g_body], [('d_graph', 'd_out', d_body), ('g_graph', 'g_out', g_body)]
+    if eng.batch_fakes:
+        warm.insert(0, f_warm)
+        bodies.append(('f_graph', 'fake_all', eng._f_body))
+    it_body = eng._it_body if eng.batch_fakes and eng.adam_in_graph and ITERATION_GRAPH else None
+    _capture_graphs(eng, warmup, (t.d_opt, t.g_opt), [t.rng.ctr], bodies, warm, it_body)
+
+
+def _capture_or_fall_back(eng, warmup):
+    """The end of a wrapper's constructor: eng._capture(warmup), or - whatever it raised - eager launches with the reason in
+    eng.graph_error (bench.py reports it) and every graph handle and graph output of the class (`_HANDLES`) None again."""
+    try:
+        eng._capture(warmup)
+    except Exception as e:
+        eng.graph_error = '%s: %s' % (type(e).__name__, e)
+        for name in eng._HANDLES:
+            setattr(eng, name, None)
+        torch.cuda.synchronize()
 
 
 class GraphedTrainer:
@@ -85,13 +173,7 @@ class GraphedTrainer:
         self.graph_error = None
         self.it_graph_error = None    # only the whole-iteration graph failed to capture: the per-step graphs are in use (still `graphed`)
         if use_graphs:
-            try:
-                self._capture(warmup)
-            except Exception as e:      # fall back to eager launches; bench.py reports it
-                self.graph_error = '%s: %s' % (type(e).__name__, e)
-                self.d_graph = self.g_graph = self.f_graph = self.it_graph = None
-                self.fake_all = self.it_out = None
-                torch.cuda.synchronize()
+            _capture_or_fall_back(self, warmup)
 
     def _weights_moved(self, group=None):
         """A replay with Adam inside the graph changed the weights AFTER the graph's own rebuild of the derived / packed filter
@@ -170,71 +252,10 @@ class GraphedTrainer:
         self._finish(t.g_opt, grads)
         return {'cost': out['cost'].detach()}
 
-    def _capture(self, warmup):
-        """Warm-up + capture of the three graphs.  Everything a body changes besides its outputs is restored afterwards
-        (also when capture fails): Adam slots and step counts, the Philox step counter - so a captured trainer continues
-        exactly where the eager one would (checkpoint resume, graph-vs-eager parity tests).
+    _HANDLES = ('d_graph', 'g_graph', 'f_graph', 'it_graph', 'd_out', 'g_out', 'fake_all', 'it_out')
 
-        Each graph owns a PRIVATE memory pool.  The graphs are replayed in an order other than the capture order
-        (g, f, then d x N_CRITIC) and their outputs outlive other graphs' replays - `fake_all` is read by all N_CRITIC
-        critic replays.  With one shared pool a block freed while capturing graph A is handed to graph B as storage of a
-        live OUTPUT, and A's next replay scribbles over it (round 1: the fake batches of critic steps 2..5 were whatever the
-        first critic replay left in that memory, hence a critic cost of -6e18).  A private pool costs ~3 GB per graph of
-        the 288 GB and makes an output valid until its own graph is replayed again."""
-        t = self.t
-        from . import kernels as K
-        K.reset_capture_workspaces()
-        opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
-        snap = [b.clone() for b in bufs]
-        steps = [o.t for o in opts]
-        for o in opts:
-            o.set_lr(0.0)       # warm-up / capture passes must not move the weights
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    if self.batch_fakes:
-                        self._f_body()
-                    self._d_body()
-                    self._g_body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            quiesce_collectives()
-            self.d_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.d_graph, **_capture_kw()):
-                self.d_out = self._d_body()
-            self.g_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_graph, **_capture_kw()):
-                self.g_out = self._g_body()
-            if self.batch_fakes:
-                self.f_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.f_graph, **_capture_kw()):
-                    self.fake_all = self._f_body()
-                if self.adam_in_graph and ITERATION_GRAPH:
-                    # Seven graph launches per iteration leave ~150 us of idle GPU at each boundary (profiles/
-                    # r02_steady_state_resnet_v2.txt: 1.07 ms of 20.5 ms); one graph per iteration has one boundary.
-                    # Optional: if only this capture fails (a fourth private pool), the three per-step graphs stay in use.
-                    try:
-                        self.it_graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(self.it_graph, **_capture_kw()):
-                            self.it_out = self._it_body()
-                    except Exception as e:
-                        self.it_graph = self.it_out = None
-                        self.it_graph_error = '%s: %s' % (type(e).__name__, e)
-                        torch.cuda.synchronize()
-                        # an exception inside an active capture can leave the stream / pools in a bad state: prove the per-step graphs
-                        # still replay (weights do not move: the learning rate is 0 here) before relying on them
-                        self.d_graph.replay(); self.g_graph.replay(); self.f_graph.replay()
-                        torch.cuda.synchronize()
-        finally:
-            torch.cuda.synchronize()
-            for b, sn in zip(bufs, snap):
-                b.copy_(sn)
-            for o, n in zip(opts, steps):
-                o.t, o._lr_last = n, None
-            torch.cuda.synchronize()
+    def _capture(self, warmup):
+        _capture_gan_graphs(self, warmup, self._f_body, self._d_body, self._g_body)
 
     @property
     def graphed(self):
@@ -379,13 +400,7 @@ class GraphedDCGANTrainer:
         self.d_out = self.g_out = None
         self.graph_error = None
         if use_graphs:
-            try:
-                self._capture(warmup)
-            except Exception as e:
-                self.graph_error = '%s: %s' % (type(e).__name__, e)
-                self.d_graph = self.g_graph = self.f_graph = self.it_graph = None
-                self.fake_all = self.it_out = None
-                torch.cuda.synchronize()
+            _capture_or_fall_back(self, warmup)
 
     def _it_body(self):
         g_out = self._body('g')
@@ -419,56 +434,11 @@ class GraphedDCGANTrainer:
             t.rng.end_step()
         return {k: out[k].detach() for k in ('cost', 'wgan_only', 'ct', 'gp') if out.get(k) is not None}
 
+    _HANDLES = GraphedTrainer._HANDLES
+
     def _capture(self, warmup):
-        t = self.t
-        from . import kernels as K
-        K.reset_capture_workspaces()
-        opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr]
-        snap = [b.clone() for b in bufs]
-        steps = [o.t for o in opts]
-        for o in opts:
-            o.set_lr(0.0)
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    if self.batch_fakes:
-                        self.fake.copy_(self._f_body()[0])      # (a real fake batch, not the zeros the static buffer starts with)
-                    self._body('d')
-                    self._body('g')
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            quiesce_collectives()
-            self.d_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.d_graph, **_capture_kw()):
-                self.d_out = self._body('d')
-            self.g_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_graph, **_capture_kw()):
-                self.g_out = self._body('g')
-            if self.batch_fakes:
-                self.f_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.f_graph, **_capture_kw()):
-                    self.fake_all = self._f_body()
-                if self.adam_in_graph and ITERATION_GRAPH:
-                    try:
-                        self.it_graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(self.it_graph, **_capture_kw()):
-                            self.it_out = self._it_body()
-                    except Exception as e:      # only this capture failed: the per-step graphs stay in use
-                        self.it_graph = self.it_out = None
-                        self.it_graph_error = '%s: %s' % (type(e).__name__, e)
-                        torch.cuda.synchronize()
-                        self.d_graph.replay(); self.g_graph.replay(); self.f_graph.replay()      # (still replayable; lr is 0 here)
-                        torch.cuda.synchronize()
-        finally:
-            torch.cuda.synchronize()
-            for b, sn in zip(bufs, snap):
-                b.copy_(sn)
-            for o, n in zip(opts, steps):
-                o.t, o._lr_last = n, None
-            torch.cuda.synchronize()
+        # (the warm-up's critic steps read a real fake batch, not the zeros the static buffer starts with)
+        _capture_gan_graphs(self, warmup, lambda: self.fake.copy_(self._f_body()[0]), lambda: self._body('d'), lambda: self._body('g'))
 
     @property
     def graphed(self):
@@ -564,12 +534,7 @@ class GraphedSSLTrainer:
         self.d_out = self.g_out = None
         self.graph_error = None
         if use_graphs:
-            try:
-                self._capture(warmup)
-            except Exception as e:
-                self.graph_error = '%s: %s' % (type(e).__name__, e)
-                self.d_graph = self.g_graph = None
-                torch.cuda.synchronize()
+            _capture_or_fall_back(self, warmup)
 
     def _alloc_staging(self):
         """The fixed buffers the batches are staged into (what the captured steps read)."""
@@ -590,38 +555,12 @@ class GraphedSSLTrainer:
         """Further device buffers the bodies write, snapshotted and restored around the capture with the optimizers' slots."""
         return []
 
+    _HANDLES = ('d_graph', 'g_graph', 'd_out', 'g_out')
+
     def _capture(self, warmup):
         t = self.t
-        K.reset_capture_workspaces()
-        opts = (t.d_opt, t.g_opt)
-        bufs = [b for o in opts for b in o.slots()] + [t.rng.ctr] + self._extra_slots()
-        snap = [b.clone() for b in bufs]
-        steps = [o.t for o in opts]
-        for o in opts:
-            o.set_lr(0.0)
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    self._d_body()
-                    self._g_body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            quiesce_collectives()
-            self.d_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.d_graph, **_capture_kw()):
-                self.d_out = self._d_body()
-            self.g_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_graph, **_capture_kw()):
-                self.g_out = self._g_body()
-        finally:
-            torch.cuda.synchronize()
-            for b, sn in zip(bufs, snap):
-                b.copy_(sn)
-            for o, n in zip(opts, steps):
-                o.t, o._lr_last = n, None
-            torch.cuda.synchronize()
+        _capture_graphs(self, warmup, (t.d_opt, t.g_opt), [t.rng.ctr] + self._extra_slots(),
+                        [('d_graph', 'd_out', self._d_body), ('g_graph', 'g_out', self._g_body)])
 
     @property
     def graphed(self):
@@ -727,12 +666,7 @@ class GraphedScoreTrainer:
         self.step_out = None
         self.graph_error = None
         if use_graphs:
-            try:
-                self._capture(warmup)
-            except Exception as e:
-                self.graph_error = '%s: %s' % (type(e).__name__, e)
-                self.step_graph = self.stats_graph = None
-                torch.cuda.synchronize()
+            _capture_or_fall_back(self, warmup)
 
     def _step_body(self):
         lib.bump_epoch('InceptionScore')      # weights changed since the last replay: derived / packed filters are rebuilt in-graph
@@ -744,35 +678,12 @@ class GraphedScoreTrainer:
         F.prepare_filters()
         self.t.stats_body(self.x)
 
+    _HANDLES = ('step_graph', 'stats_graph', 'step_out')
+
     def _capture(self, warmup):
         t = self.t
-        K.reset_capture_workspaces()
-        bufs = t.opt.slots() + [p.data for _, p in t.moving_stats()] + [t.stats_iter]
-        snap = [b.clone() for b in bufs]
-        steps = t.opt.t
-        t.opt.set_lr(0.0)
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    self._step_body()
-                    self._stats_body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            quiesce_collectives()
-            self.step_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.step_graph, **_capture_kw()):
-                self.step_out = self._step_body()
-            self.stats_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.stats_graph, **_capture_kw()):
-                self._stats_body()
-        finally:
-            torch.cuda.synchronize()
-            for b, sn in zip(bufs, snap):
-                b.copy_(sn)
-            t.opt.t, t.opt._lr_last = steps, None
-            torch.cuda.synchronize()
+        _capture_graphs(self, warmup, (t.opt,), [p.data for _, p in t.moving_stats()] + [t.stats_iter],
+                        [('step_graph', 'step_out', self._step_body), ('stats_graph', None, self._stats_body)])
 
     @property
     def graphed(self):

@@ -3,7 +3,7 @@
 
 Round 1 timed a loop whose critic cost ran to -6e18: the three graphs shared one memory pool and were replayed in an order
 other than the capture order, so the fake batches of critic steps 2..5 were overwritten by the first critic replay
-(engine.GraphedTrainer._capture).  No test looked at a VALUE of the graphed loop.  These do:
+(engine._capture_graphs).  No test looked at a VALUE of the graphed loop.  These do:
   * every loss term of every critic step of the replayed loop equals the eager loop on the same Philox streams (same kernels
     in the same order - the comparison is tight), and stays in a sane band;
   * the fake batches the critic replays read are tanh outputs (|x| <= 1) - the direct symptom of the round-1 aliasing;
