@@ -84,6 +84,7 @@ DEBUG_SIGNATURES = {
     'ctgan_debug_x3_hk': (None, [c_int, c_int]),
     'ctgan_debug_x3_halo_always': (None, [c_int]),
     'ctgan_debug_clock_probe': (c_int, [c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
+    'ctgan_debug_optim_launches': (c_uint64, [c_int]),
 }
 
 # name -> (restype, argtypes); the single source the symbol-export test checks against include/ctgan_hip.h
@@ -217,6 +218,16 @@ SIGNATURES = {
     'ctgan_rmsprop_step_packed_avg': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float,
                                               c_float, c_float, c_float, _p, c_float, _p]),
     'ctgan_exchange': (c_int, [_p, _p, c_int64, _p]),
+    # dynamic loss scale: scan, the scaled updates (avg may be NULL), the scaled end of a step
+    'ctgan_grads_nonfinite_blocks': (ctypes.c_uint, [c_int64, c_int32]),
+    'ctgan_grads_nonfinite': (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, _p, _p]),
+    'ctgan_adam_step_scaled': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
+    'ctgan_adam_step_packed_scaled': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float,
+                                              c_float, c_float, c_float, _p, c_float, _p, _p]),
+    'ctgan_rmsprop_step_scaled': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
+    'ctgan_rmsprop_step_packed_scaled': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float,
+                                                 c_float, c_float, c_float, _p, c_float, _p, _p]),
+    'ctgan_step_advance_scaled': (c_int, [_p, c_float, c_float, _p, c_uint64, _p, c_int64, c_float, c_float, _p]),
     'ctgan_dropout_rng':(c_int, [_p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_dropout_rng_mask': (c_int, [_p, _p, _p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_lrelu_dropout_rng': (c_int, [_p, _p, _p, c_int64, c_float, c_float, c_uint64, c_uint64, _p, _p]),

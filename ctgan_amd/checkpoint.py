@@ -6,7 +6,9 @@ trivial: one file holds every parameter by its reference name and layout, both o
 beta-power state, or RMSProp ms - tagged with the optimizer kind, so a resume under another MODE fails clearly -, step count), the Philox step counter and the loop iteration - enough for a bit-exact
 continuation (tests/test_gpu_checkpoint.py).  The `rng` entry also holds the step counter of the evaluation stream (evaluate.eval_stream:
 `eval_ctr`), so that a resumed run logs the dev costs of the uninterrupted one; a file written before that entry existed loads with the
-counter at 0."""
+counter at 0.  A trainer with a dynamic loss scale (DCGANTrainer(loss_scale='dynamic')) adds the entry `loss_scaler` - the scale and its
+two counts; a run without one writes the keys it always wrote.  A file without the entry starts a dynamic trainer at its init_scale; a
+file with it loads into a trainer with a fixed scale, which ignores it."""
 import torch
 
 from . import tflib as lib
@@ -14,7 +16,9 @@ from .evaluate import eval_stream
 
 
 def save(path, trainer, iteration, extra=None):
+    scaler = getattr(trainer, 'scaler', None)
     torch.save({
+        **({'loss_scaler': scaler.state_dict()} if scaler is not None else {}),
         'format': 1,
         'iteration': int(iteration),
         'params': lib.state_dict(),
@@ -40,6 +44,8 @@ def load(path, trainer):
         trainer.rng.seed = ck['rng']['seed']
         trainer.rng.ctr.fill_(ck['rng']['ctr'])
         eval_stream(trainer).ctr.fill_(ck['rng'].get('eval_ctr', 0))
+    if getattr(trainer, 'scaler', None) is not None:
+        trainer.scaler.load_state_dict(ck.get('loss_scaler'))
     return ck['iteration']
 
 

@@ -32,15 +32,35 @@ __device__ __forceinline__ float avg_elem(float a, float th, float rate) {
     return a + rate * (th - a);
 }
 // Every update kernel is a template on "keeps an average": the AVG = false instantiation is the code without it (avg / avg_rate unused).
-template <bool AVG>
+//
+// ... and on SCALED, "under the dynamic loss scale" (not in the reference; optim.LossScaler).  scaler = device float[4] {S, found, good,
+// skipped}: S the power-of-two loss scale the step's backward was seeded with, found != 0 when nonfinite_scan_kernel saw a NaN / inf in
+// this step's gradients, good = updates applied in a row since S last changed, skipped = updates dropped so far.  The SCALED forms divide
+// the host's factor by S - exact for a power of two, so a good step has the bits of the static kernel called with gscale / S - and drop
+// the WHOLE update when `found` is set: when one element overflowed, the finite ones came out of the same overflowed intermediates.  A
+// dropped update changes no theta, m, v or ms; the RMSProp clip still clips and the average still follows the weights as they are, the
+// rules of the per-element skip, which stays in place behind it (it is what keeps an inf that appears only after the scaling, or a step
+// without a scaler, out of the slots).  The elements of a dropped update are not counted in state[3]: scaler[3] counts the update.
+// SCALED = false is the code without any of it (scaler unused).
+template <bool SCALED>
+__device__ __forceinline__ bool scaled_step(const float* __restrict__ scaler, float& gscale) {
+    if constexpr (SCALED) {
+#pragma clang fp contract(off)
+        gscale = gscale / scaler[0];
+        return scaler[1] != 0.f;
+    }
+    return false;
+}
+template <bool AVG, bool SCALED>
 __global__ void adam_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float* state, float b1, float b2,
-                            float eps, float gscale, float* __restrict__ avg, float avg_rate) {
+                            float eps, float gscale, float* __restrict__ avg, float avg_rate, const float* __restrict__ scaler) {
     const float lr = state[0], b1p = state[1], b2p = state[2];
     const float lr_t = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+    const bool drop = scaled_step<SCALED>(scaler, gscale);
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        adam_elem(th[i], m[i], v[i], g[i], gscale, b1, b2, eps, lr_t, state + 3);
+        if (!SCALED || !drop) adam_elem(th[i], m[i], v[i], g[i], gscale, b1, b2, eps, lr_t, state + 3);
         if constexpr (AVG) avg[i] = avg_elem(avg[i], th[i], avg_rate);
     }
 }
@@ -54,6 +74,28 @@ __global__ void adam_advance_kernel(float* state, float b1, float b2) {
 __global__ void step_advance_kernel(float* state, float b1, float b2, uint64_t* ctr, uint64_t by) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         state[1] *= b1; state[2] *= b2;
+        if (ctr) ctr[0] += by;
+    }
+}
+// The end of a step under the dynamic loss scale, still ONE one-thread launch.  A good step: the beta powers advance, good += 1, and at
+// `growth` good updates in a row S doubles (up to s_max) and the count starts again.  A dropped step: the beta powers stay (the update
+// they belong to did not happen), S halves (down to s_min), good = 0, skipped += 1.  Either way `found` is cleared for the next scan and
+// the Philox counter moves: every draw of a run keeps the number it has without the scaler.  The counts are floats (exact to 2^24).
+__global__ void step_advance_scaled_kernel(float* state, float b1, float b2, uint64_t* ctr, uint64_t by, float* scaler, float growth,
+                                           float s_min, float s_max) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const float S = scaler[0];
+        if (scaler[1] != 0.f) {
+            scaler[0] = fmaxf(S * 0.5f, s_min);
+            scaler[2] = 0.f;
+            scaler[3] += 1.f;
+        } else {
+            state[1] *= b1; state[2] *= b2;
+            const float good = scaler[2] + 1.f;
+            if (good >= growth) { scaler[0] = fminf(S * 2.f, s_max); scaler[2] = 0.f; }
+            else scaler[2] = good;
+        }
+        scaler[1] = 0.f;
         if (ctr) ctr[0] += by;
     }
 }
@@ -80,15 +122,43 @@ __global__ void pack_kernel(const PackTable t, float* __restrict__ flat) {
         flat[off + i] = src ? src[i] : 0.f;
 }
 
+// Any NaN / inf among a step's gradients -> scaler[1] = 1, ahead of the SCALED update (the next kernel on the stream reads it).  The
+// sources are a pack table (dst_off unused; a null source is all zeros: nothing to read) or, as a table of one, the flat bucket after
+// the all-reduce.  Bandwidth-bound: each tensor is read once, as 16-byte items between the elements in front of its first 16-byte
+// boundary and the n % 4 behind its last, which go one by one.  The test is on the raw bits (all exponent bits set), so +-FLT_MAX,
+// denormals and -0 pass.  A wave combines by ballot and makes ONE plain store; every writer stores the same value: no atomic.
+__device__ __forceinline__ bool nonfinite_bits(uint32_t u) { return (u & 0x7f800000u) == 0x7f800000u; }
+__global__ void nonfinite_scan_kernel(const PackTable t, float* __restrict__ scaler) {
+    const float* src = t.src[blockIdx.y];
+    const long long n = t.n[blockIdx.y];
+    if (!src || n <= 0) return;                  // (uniform over the workgroup)
+    const uint32_t* u = reinterpret_cast<const uint32_t*>(src);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 2;
+    if (head > n) head = n;
+    const long long n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
+    bool bad = false;
+    const uint4* u4 = reinterpret_cast<const uint4*>(u + head);
+    for (long long i = first; i < n4; i += stride) {
+        const uint4 q = u4[i];
+        bad |= nonfinite_bits(q.x) | nonfinite_bits(q.y) | nonfinite_bits(q.z) | nonfinite_bits(q.w);
+    }
+    if (first < head) bad |= nonfinite_bits(u[first]);                            // at most three elements each side: the grid's first threads
+    if (first < n - tail0) bad |= nonfinite_bits(u[tail0 + first]);
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) scaler[1] = 1.f;
+}
+
 // pack_kernel + adam_kernel in one launch (single-rank steps: nothing happens between the gather and the update).
 // The flat bucket is still written - it is the gradient the caller reports and the tests read.  Same per-element arithmetic as
 // adam_kernel on the packed bucket (bit-identical results).
-template <bool AVG>
+template <bool AVG, bool SCALED>
 __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, float* __restrict__ th, float* __restrict__ m,
                                    float* __restrict__ v, float* state, float b1, float b2, float eps, float gscale,
-                                   float* __restrict__ avg, float avg_rate) {
+                                   float* __restrict__ avg, float avg_rate, const float* __restrict__ scaler) {
     const float lr = state[0], b1p = state[1], b2p = state[2];
     const float lr_t = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+    const bool drop = scaled_step<SCALED>(scaler, gscale);
     const float* src = t.src[blockIdx.y];
     const long long off = t.dst_off[blockIdx.y], n = t.n[blockIdx.y];
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -107,8 +177,9 @@ __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, 
             const float gv[4] = {gr.x, gr.y, gr.z, gr.w};
             float* mp = &mm.x; float* vp = &vv.x; float* tp = &tt.x;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) adam_elem(tp[k], mp[k], vp[k], gv[k], gscale, b1, b2, eps, lr_t, state + 3);
-            m4[i] = mm; v4[i] = vv; th4[i] = tt;
+            for (int k = 0; k < 4; ++k)
+                if (!SCALED || !drop) adam_elem(tp[k], mp[k], vp[k], gv[k], gscale, b1, b2, eps, lr_t, state + 3);
+            if (!SCALED || !drop) { m4[i] = mm; v4[i] = vv; th4[i] = tt; }
             if constexpr (AVG) {
                 float4 aa = a4[i];
                 float* ap = &aa.x;
@@ -121,7 +192,7 @@ __global__ void adam_packed_kernel(const PackTable t, float* __restrict__ flat, 
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
             const float gr = src ? src[i] : 0.f;
             flat[off + i] = gr;
-            adam_elem(th[off + i], m[off + i], v[off + i], gr, gscale, b1, b2, eps, lr_t, state + 3);
+            if (!SCALED || !drop) adam_elem(th[off + i], m[off + i], v[off + i], gr, gscale, b1, b2, eps, lr_t, state + 3);
             if constexpr (AVG) avg[off + i] = avg_elem(avg[off + i], th[off + i], avg_rate);
         }
     }
@@ -142,23 +213,33 @@ __device__ __forceinline__ void rmsprop_elem(float& th, float& ms, float graw, f
     ms = mi;
     th = clip_to(th - (gi * lr) / sqrtf(mi + eps), clip);
 }
-template <bool AVG>
+// (a dropped update of the SCALED forms: only the clip)
+template <bool SCALED>
+__device__ __forceinline__ void rmsprop_elem_or_drop(bool drop, float& th, float& ms, float graw, float gscale, float rho, float eps, float lr,
+                                                     float clip, float* skipped) {
+    if (SCALED && drop) th = clip_to(th, clip);
+    else rmsprop_elem(th, ms, graw, gscale, rho, eps, lr, clip, skipped);
+}
+template <bool AVG, bool SCALED>
 __global__ void rmsprop_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ ms, long long n, float* state,
-                               float rho, float eps, float clip, float gscale, float* __restrict__ avg, float avg_rate) {
+                               float rho, float eps, float clip, float gscale, float* __restrict__ avg, float avg_rate,
+                               const float* __restrict__ scaler) {
     const float lr = state[0];
+    const bool drop = scaled_step<SCALED>(scaler, gscale);
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        rmsprop_elem(th[i], ms[i], g[i], gscale, rho, eps, lr, clip, state + 3);
+        rmsprop_elem_or_drop<SCALED>(drop, th[i], ms[i], g[i], gscale, rho, eps, lr, clip, state + 3);
         if constexpr (AVG) avg[i] = avg_elem(avg[i], th[i], avg_rate);
     }
 }
 // pack_kernel + rmsprop_kernel in one launch: adam_packed_kernel's layout (pointer table in the arguments, grid.y = tensor, 4-wide body
 // when the segment allows it, scalar otherwise); the flat bucket is still written.
-template <bool AVG>
+template <bool AVG, bool SCALED>
 __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ flat, float* __restrict__ th, float* __restrict__ ms,
                                       float* state, float rho, float eps, float clip, float gscale, float* __restrict__ avg,
-                                      float avg_rate) {
+                                      float avg_rate, const float* __restrict__ scaler) {
     const float lr = state[0];
+    const bool drop = scaled_step<SCALED>(scaler, gscale);
     const float* src = t.src[blockIdx.y];
     const long long off = t.dst_off[blockIdx.y], n = t.n[blockIdx.y];
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -176,7 +257,7 @@ __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ fla
             const float gv[4] = {gr.x, gr.y, gr.z, gr.w};
             float* mp = &mm.x; float* tp = &tt.x;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) rmsprop_elem(tp[k], mp[k], gv[k], gscale, rho, eps, lr, clip, state + 3);
+            for (int k = 0; k < 4; ++k) rmsprop_elem_or_drop<SCALED>(drop, tp[k], mp[k], gv[k], gscale, rho, eps, lr, clip, state + 3);
             ms4[i] = mm; th4[i] = tt;
             if constexpr (AVG) {
                 float4 aa = a4[i];
@@ -190,7 +271,7 @@ __global__ void rmsprop_packed_kernel(const PackTable t, float* __restrict__ fla
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
             const float gr = src ? src[i] : 0.f;
             flat[off + i] = gr;
-            rmsprop_elem(th[off + i], ms[off + i], gr, gscale, rho, eps, lr, clip, state + 3);
+            rmsprop_elem_or_drop<SCALED>(drop, th[off + i], ms[off + i], gr, gscale, rho, eps, lr, clip, state + 3);
             if constexpr (AVG) avg[off + i] = avg_elem(avg[off + i], th[off + i], avg_rate);
         }
     }
@@ -478,15 +559,21 @@ __global__ void exchange_kernel(float* __restrict__ a, float* __restrict__ b, lo
 
 // Host side of the four update launches, one template each on "keeps an average" (the C entry points below forward here).
 inline bool avg_args_bad(const float* avg, float avg_rate) { return !avg || !(avg_rate > 0.f && avg_rate <= 1.f); }
+// ... and on "under the dynamic loss scale" (scaler = device float[4], see adam_kernel).  Launches per kind since the library was loaded
+// (ctgan_debug_optim_launches): what a test reads to see that a run without a scaler launches none of the scaled forms.
+unsigned long long g_optim_launches[5];
+enum { LAUNCH_UPDATE = 0, LAUNCH_ADVANCE = 1, LAUNCH_SCAN = 2, LAUNCH_UPDATE_SCALED = 3, LAUNCH_ADVANCE_SCALED = 4 };
+template <bool SCALED> inline void count_update() { ++g_optim_launches[SCALED ? LAUNCH_UPDATE_SCALED : LAUNCH_UPDATE]; }
 
-template <bool AVG>
+template <bool AVG, bool SCALED>
 int adam_step_host(const char* what, float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2,
-                   float eps, float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    if (!theta || !g || !m || !v || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+                   float eps, float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (!theta || !g || !m || !v || !state || n < 0 || (SCALED && !scaler)) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
     if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL(adam_kernel<AVG>, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, m,
-                       v, (long long)n, state, beta1, beta2, eps, grad_scale, avg, avg_rate);
+    hipLaunchKernelGGL((adam_kernel<AVG, SCALED>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, m,
+                       v, (long long)n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
+    count_update<SCALED>();
     return ctgan_check_launch(what);
 }
 // the pointer table of a packed update; 0 or the error
@@ -500,11 +587,11 @@ int fill_pack_table(const char* what, const float* const* srcs, const int64_t* d
     }
     return CTGAN_OK;
 }
-template <bool AVG>
+template <bool AVG, bool SCALED>
 int adam_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
                           float* flat, float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps,
-                          float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0)
+                          float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0 || (SCALED && !scaler))
         return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
     if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
@@ -514,25 +601,27 @@ int adam_step_packed_host(const char* what, const float* const* srcs, const int6
     PackTable t;
     long long mx;
     if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
-    hipLaunchKernelGGL(adam_packed_kernel<AVG>, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t,
-                       flat, theta, m, v, state, beta1, beta2, eps, grad_scale, avg, avg_rate);
+    hipLaunchKernelGGL((adam_packed_kernel<AVG, SCALED>), dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0,
+                       static_cast<hipStream_t>(s), t, flat, theta, m, v, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
+    count_update<SCALED>();
     return ctgan_check_launch(what);
 }
-template <bool AVG>
+template <bool AVG, bool SCALED>
 int rmsprop_step_host(const char* what, float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                      float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    if (!theta || !g || !ms || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+                      float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (!theta || !g || !ms || !state || n < 0 || (SCALED && !scaler)) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
     if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL(rmsprop_kernel<AVG>, dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, ms,
-                       (long long)n, state, rho, eps, clip, grad_scale, avg, avg_rate);
+    hipLaunchKernelGGL((rmsprop_kernel<AVG, SCALED>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g,
+                       ms, (long long)n, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
+    count_update<SCALED>();
     return ctgan_check_launch(what);
 }
-template <bool AVG>
+template <bool AVG, bool SCALED>
 int rmsprop_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
                              float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                             float* avg, float avg_rate, ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0)
+                             float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0 || (SCALED && !scaler))
         return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
     if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
     if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
@@ -542,8 +631,9 @@ int rmsprop_step_packed_host(const char* what, const float* const* srcs, const i
     PackTable t;
     long long mx;
     if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
-    hipLaunchKernelGGL(rmsprop_packed_kernel<AVG>, dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s),
-                       t, flat, theta, ms, state, rho, eps, clip, grad_scale, avg, avg_rate);
+    hipLaunchKernelGGL((rmsprop_packed_kernel<AVG, SCALED>), dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0,
+                       static_cast<hipStream_t>(s), t, flat, theta, ms, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
+    count_update<SCALED>();
     return ctgan_check_launch(what);
 }
 
@@ -553,11 +643,11 @@ extern "C" {
 
 int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
                     float beta2, float eps, float grad_scale, ctgan_stream_t s) {
-    return adam_step_host<false>("adam_step", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, s);
+    return adam_step_host<false, false>("adam_step", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, nullptr, s);
 }
 int ctgan_adam_step_avg(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
                         float beta2, float eps, float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    return adam_step_host<true>("adam_step_avg", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, s);
+    return adam_step_host<true, false>("adam_step_avg", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, nullptr, s);
 }
 int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                ctgan_stream_t s) {
@@ -579,40 +669,103 @@ int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t*
 int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, ctgan_stream_t s) {
     if (!state) return ctgan_fail(CTGAN_E_BADARG, "step_advance: null");
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by);
+    ++g_optim_launches[LAUNCH_ADVANCE];
     return ctgan_check_launch("step_advance");
 }
 int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                            float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
                            ctgan_stream_t s) {
-    return adam_step_packed_host<false>("adam_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2, eps,
-                                        grad_scale, nullptr, 0.f, s);
+    return adam_step_packed_host<false, false>("adam_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2,
+                                               eps, grad_scale, nullptr, 0.f, nullptr, s);
 }
 int ctgan_adam_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                                float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
                                float* avg, float avg_rate, ctgan_stream_t s) {
-    return adam_step_packed_host<true>("adam_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2,
-                                       eps, grad_scale, avg, avg_rate, s);
+    return adam_step_packed_host<true, false>("adam_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
+                                              beta2, eps, grad_scale, avg, avg_rate, nullptr, s);
 }
 int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
                        float grad_scale, ctgan_stream_t s) {
-    return rmsprop_step_host<false>("rmsprop_step", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, s);
+    return rmsprop_step_host<false, false>("rmsprop_step", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, nullptr, s);
 }
 int ctgan_rmsprop_step_avg(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
                            float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    return rmsprop_step_host<true>("rmsprop_step_avg", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, s);
+    return rmsprop_step_host<true, false>("rmsprop_step_avg", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, nullptr, s);
 }
 int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                               float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
                               ctgan_stream_t s) {
-    return rmsprop_step_packed_host<false>("rmsprop_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps, clip,
-                                           grad_scale, nullptr, 0.f, s);
+    return rmsprop_step_packed_host<false, false>("rmsprop_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps,
+                                                  clip, grad_scale, nullptr, 0.f, nullptr, s);
 }
 int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                                   float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale, float* avg,
                                   float avg_rate, ctgan_stream_t s) {
-    return rmsprop_step_packed_host<true>("rmsprop_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps,
-                                          clip, grad_scale, avg, avg_rate, s);
+    return rmsprop_step_packed_host<true, false>("rmsprop_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho,
+                                                 eps, clip, grad_scale, avg, avg_rate, nullptr, s);
 }
+// ---- the dynamic loss scale: scan, the four scaled updates (avg == NULL: without the average), the scaled end of a step
+unsigned ctgan_grads_nonfinite_blocks(int64_t max_count, int32_t n_tensors) {
+    // one table entry (the flat bucket) gets the grid of the plain update kernels; a table the grid of the packed ones, in 16-byte items
+    return n_tensors == 1 ? ctgan_blocks((max_count + 3) >> 2, 256, 2048) : ctgan_blocks((max_count + 3) >> 2, 256, 512);
+}
+int ctgan_grads_nonfinite(const float* const* srcs, const int64_t* counts, int32_t n_tensors, float* scaler, ctgan_stream_t s) {
+    if (!srcs || !counts || !scaler || n_tensors <= 0) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: bad argument");
+    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "grads_nonfinite: more than %d tensors", PACK_MAX);
+    PackTable t;
+    long long mx = 1;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (counts[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: negative extent");
+        if (reinterpret_cast<uintptr_t>(srcs[i]) & 3) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: source %d is not 4-byte aligned", i);
+        t.src[i] = srcs[i]; t.dst_off[i] = 0; t.n[i] = counts[i];
+        if (srcs[i] && t.n[i] > mx) mx = t.n[i];
+    }
+    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(ctgan_grads_nonfinite_blocks(mx, n_tensors), n_tensors), dim3(256), 0,
+                       static_cast<hipStream_t>(s), t, scaler);
+    ++g_optim_launches[LAUNCH_SCAN];
+    return ctgan_check_launch("grads_nonfinite");
+}
+int ctgan_adam_step_scaled(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
+                           float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (avg) return adam_step_host<true, true>("adam_step_scaled", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler, s);
+    return adam_step_host<false, true>("adam_step_scaled", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, scaler, s);
+}
+int ctgan_adam_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                                  float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
+                                  float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (avg)
+        return adam_step_packed_host<true, true>("adam_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
+                                                 beta2, eps, grad_scale, avg, avg_rate, scaler, s);
+    return adam_step_packed_host<false, true>("adam_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
+                                              beta2, eps, grad_scale, nullptr, 0.f, scaler, s);
+}
+int ctgan_rmsprop_step_scaled(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                              float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (avg) return rmsprop_step_host<true, true>("rmsprop_step_scaled", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler, s);
+    return rmsprop_step_host<false, true>("rmsprop_step_scaled", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, scaler, s);
+}
+int ctgan_rmsprop_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                                     float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
+                                     float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    if (avg)
+        return rmsprop_step_packed_host<true, true>("rmsprop_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state,
+                                                    rho, eps, clip, grad_scale, avg, avg_rate, scaler, s);
+    return rmsprop_step_packed_host<false, true>("rmsprop_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho,
+                                                 eps, clip, grad_scale, nullptr, 0.f, scaler, s);
+}
+static bool pow2(float x) { int e; return x > 0.f && x <= 3.0e38f && frexpf(x, &e) == 0.5f; }
+int ctgan_step_advance_scaled(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler,
+                              int64_t growth_interval, float min_scale, float max_scale, ctgan_stream_t s) {
+    if (!state || !scaler) return ctgan_fail(CTGAN_E_BADARG, "step_advance_scaled: null");
+    if (growth_interval < 1 || !pow2(min_scale) || !pow2(max_scale) || min_scale > max_scale)
+        return ctgan_fail(CTGAN_E_BADARG, "step_advance_scaled: growth_interval < 1, or a bound that is no power of two, or min > max");
+    hipLaunchKernelGGL(step_advance_scaled_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by,
+                       scaler, (float)growth_interval, min_scale, max_scale);
+    ++g_optim_launches[LAUNCH_ADVANCE_SCALED];
+    return ctgan_check_launch("step_advance_scaled");
+}
+uint64_t ctgan_debug_optim_launches(int kind) { return kind >= 0 && kind < 5 ? g_optim_launches[kind] : 0; }
+
 int ctgan_exchange(float* a, float* b, int64_t n, ctgan_stream_t s) {
     if (n < 0 || (n > 0 && (!a || !b))) return ctgan_fail(CTGAN_E_BADARG, "exchange: bad argument");
     if (n == 0) return CTGAN_OK;

@@ -23,7 +23,7 @@ import torch
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
-from .optim import FlatAdam, FlatRMSProp
+from .optim import FlatAdam, FlatRMSProp, LossScaler
 from .optim import averaged as averaged_weights
 from .rng import AUG_FAKE, AUG_GEN, AUG_REAL, DeviceRNG
 
@@ -76,7 +76,7 @@ def mode_of(module):
 
 
 class DCGANTrainer:
-    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None):
+    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, loss_scale=None):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
         real_prep, feat_shapes).  g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights,
         moved inside its update launch (optim.FlatAdam / FlatRMSProp avg_rate), whatever the mode's optimizer.  It is the RATE, 1 - decay:
@@ -86,7 +86,10 @@ class DCGANTrainer:
         (kernels.diffaug) is applied to the reals and the fakes in front of the critic in the critic step - before the interpolation, so
         the penalty is taken at the augmented x_hat - and to the samples in the generator step, whose gradient flows back through T.  Its
         draws come from three reserved streams (rng.AUG_REAL / AUG_FAKE / AUG_GEN) at the trainer's own counter: no other draw of a step
-        moves, there is no state to checkpoint."""
+        moves, there is no state to checkpoint.  loss_scale (NOT in the reference; for kernels.set_mma_dtype('f16')): None - the
+        module's LOSS_SCALE, or 1, as before; a float - that fixed power-of-two scale; 'dynamic' or an optim.LossScaler - a dynamic scale
+        kept on the device (`scaler`; both optimizers share it): the backward is seeded with it, an update whose gradients hold a NaN /
+        inf is dropped as a whole and halves it, growth_interval applied updates in a row double it."""
         self.mod = module
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape_of(module) if self.aug_policy else None
@@ -97,13 +100,23 @@ class DCGANTrainer:
         self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
         self.mode = mode_of(module)
         self.disc_iters = self.mode.critic_iters or module.cfg.CRITIC_ITERS     # critic steps per iteration
+        # Power-of-two loss scale for the fp16 matrix-core mode (kernels.set_mma_dtype('f16')): the backward passes are linear in the
+        # seed, so the cost gradient is seeded with S instead of 1 - every first-order gradient TENSOR the fp16 kernels round is S
+        # times larger, away from fp16's subnormals (per-pixel gradients shrink with 1 / (B H W)) - and Adam divides it out again
+        # (grad_scale); exact in fp32 (a power of two), a no-op for S = 1.  Dynamic: S lives in `scaler.state`, the static factor stays 1.
+        if isinstance(loss_scale, str) and loss_scale != 'dynamic':
+            raise ValueError("loss_scale: None, a number, 'dynamic' or an optim.LossScaler (got %r)" % (loss_scale,))
+        self.scaler = LossScaler(device=self.dev) if isinstance(loss_scale, str) else loss_scale if isinstance(loss_scale, LossScaler) else None
+        if self.scaler is not None and self.scaler.state.device.type != torch.device(self.dev).type:
+            raise ValueError('loss_scale: the LossScaler lives on %s, the trainer on %s' % (self.scaler.state.device, self.dev))
+        kw = {'scaler': self.scaler} if self.scaler is not None else {}
         if self.mode.optimizer == 'rmsprop':
-            self.d_opt = FlatRMSProp(self.d_named, clip=self.mode.clip)
-            self.g_opt = FlatRMSProp(self.g_named, avg_rate=g_average)
+            self.d_opt = FlatRMSProp(self.d_named, clip=self.mode.clip, **kw)
+            self.g_opt = FlatRMSProp(self.g_named, avg_rate=g_average, **kw)
         else:
             b1, b2 = self.mode.betas or getattr(module, 'ADAM_BETAS', (0.5, 0.9))
-            self.d_opt = FlatAdam(self.d_named, b1, b2)
-            self.g_opt = FlatAdam(self.g_named, b1, b2, avg_rate=g_average)
+            self.d_opt = FlatAdam(self.d_named, b1, b2, **kw)
+            self.g_opt = FlatAdam(self.g_named, b1, b2, avg_rate=g_average, **kw)
         # the clip op also covers the critic's non-trainable BatchNorm moving statistics; nothing else writes them (training-mode
         # statistics only), so clamping them once, at the first critic update, is exact
         self._stats_to_clip = [p for n, p in lib.named_params_with_name('Discriminator') if n in lib._non_trainable] if self.mode.clip else []
@@ -112,12 +125,23 @@ class DCGANTrainer:
         self.iteration = 0
         self.d_params = [p for _, p in self.d_named]
         self.g_params = [p for _, p in self.g_named]
-        # Power-of-two loss scale for the fp16 matrix-core mode (kernels.set_mma_dtype('f16')): the backward passes are linear in the
-        # seed, so the cost gradient is seeded with S instead of 1 - every first-order gradient TENSOR the fp16 kernels round is S
-        # times larger, away from fp16's subnormals (per-pixel gradients shrink with 1 / (B H W)) - and Adam divides it out again
-        # (grad_scale); exact in fp32 (a power of two), a no-op for S = 1.
-        self.loss_scale = float(getattr(module, 'LOSS_SCALE', 1.0))
+        if self.scaler is not None:
+            self._loss_scale = 1.0
+        else:
+            self._loss_scale = float(getattr(module, 'LOSS_SCALE', 1.0) if loss_scale is None else loss_scale)
         self._seed = None
+
+    @property
+    def loss_scale(self):
+        """The STATIC loss scale, the factor the host folds into grad_scale: the fixed scale, or 1.0 under a dynamic one (whose value is
+        on the device: scaler.scale())."""
+        return self._loss_scale
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        if self.scaler is not None:
+            raise AttributeError('loss_scale cannot be assigned on a trainer with a dynamic loss scale (it lives in trainer.scaler)')
+        self._loss_scale = float(value)
 
     def averaged(self):
         """Context manager: inside it the generator's parameters hold their weight average (optim.averaged; ValueError when the
@@ -125,7 +149,10 @@ class DCGANTrainer:
         return averaged_weights(self.g_opt)
 
     def cost_seed(self):
-        """grad_outputs of the final backward: a cached 0-dim tensor holding the loss scale (no fill kernel per step)."""
+        """grad_outputs of the final backward: a cached 0-dim tensor holding the loss scale (no fill kernel per step); under a dynamic
+        scale the device view of it (LossScaler.seed)."""
+        if self.scaler is not None:
+            return self.scaler.seed()
         if self._seed is None or float(self._seed_val) != self.loss_scale:
             self._seed = torch.full((), self.loss_scale, dtype=torch.float32, device=self.dev)
             self._seed_val = self.loss_scale
@@ -284,7 +311,10 @@ class DCGANTrainer:
             self.allreduce.wait()
         opt.step(grad_scale=scale, rng=self.rng)
 
-    def _unscaled(self, grads):
+    def _unscaled(self, grads, seed=None):
+        """`seed`: under a dynamic scale, a COPY of the scale the gradients were taken at (the end of the step may have changed it)."""
+        if seed is not None:
+            return [None if g is None else g / seed for g in grads]
         if self.loss_scale == 1.0:
             return grads
         return [None if g is None else g / self.loss_scale for g in grads]
@@ -292,9 +322,10 @@ class DCGANTrainer:
     def d_step(self, real_in, rnd=None, fake=None):
         self.rng.begin_step()
         out, grads = self.d_grads(real_in, rnd, fake=fake)
+        seed = self.scaler.seed().clone() if self.scaler is not None else None
         self._apply(self.d_opt, grads)          # (the weight clip of MODE 'wgan' is fused into the update, on every rank)
         self.clip_stats()
-        out['grads'] = dict(zip([n for n, _ in self.d_named], self._unscaled(grads)))
+        out['grads'] = dict(zip([n for n, _ in self.d_named], self._unscaled(grads, seed)))
         return out
 
     def g_step(self, rnd=None):
@@ -302,8 +333,9 @@ class DCGANTrainer:
         out = self.g_losses(rnd)
         with F.deferred_wgrads():
             grads = torch.autograd.grad(out['cost'], self.g_params, grad_outputs=self.cost_seed().reshape(out['cost'].shape), allow_unused=True)
+        seed = self.scaler.seed().clone() if self.scaler is not None else None
         self._apply(self.g_opt, grads)
-        out['grads'] = dict(zip([n for n, _ in self.g_named], self._unscaled(grads)))
+        out['grads'] = dict(zip([n for n, _ in self.g_named], self._unscaled(grads, seed)))
         return out
 
     def train_iteration(self, iteration, next_batch):
@@ -354,7 +386,7 @@ def sample_grid(module, noise, trainer=None, averaged=False):
 
 
 def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
-          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None):
+          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None, loss_scale=None):
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
@@ -363,7 +395,8 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     `dev_every`-th.  `g_average` > 0 (NOT in the reference; DCGANTrainer): the generator's weight average is kept, scored after the live
     generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  `augment` (NOT in the reference; DCGANTrainer):
     a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps; the dev cost, the sample
-    grids and the scores stay un-augmented.  Returns the trainer."""
+    grids and the scores stay un-augmented.  `loss_scale` (NOT in the reference; DCGANTrainer): None, a fixed scale, or 'dynamic' / an
+    optim.LossScaler - then the series `loss_scale` and `skipped_steps` are added at every flush.  Returns the trainer."""
     import os
     import time
 
@@ -374,7 +407,7 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     cfg = module.cfg
     iters = cfg.ITERS if iters is None else iters
     build_params(module)
-    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment)
+    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment, loss_scale=loss_scale)
     start = checkpoint.load(resume, trainer) if resume else 0
     first = next_batch()
     eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)
@@ -407,6 +440,9 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
         if checkpoint_every and iteration % checkpoint_every == checkpoint_every - 1:
             checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, iteration + 1)
         if iteration < 5 or (dev_every and iteration % dev_every == dev_every - 1):
+            if trainer.scaler is not None:
+                series.add('loss_scale', trainer.scaler.scale())
+                series.add('skipped_steps', trainer.scaler.skipped_steps())
             series.flush()
         series.tick()
     return trainer

@@ -7,6 +7,7 @@ TF/CT_gan_64x64.py:548-576), with the 'wgan' weight clip fused into its update. 
 gradient buffers double as the all-reduce buckets of the batch-sharded step (ddp.py).
 """
 import contextlib
+import math
 
 import torch
 
@@ -14,16 +15,85 @@ from . import kernels as K
 from . import tflib as lib
 
 
+def _power_of_two(name, x):
+    x = float(x)
+    if not (x > 0 and math.isfinite(x) and math.frexp(x)[0] == 0.5 and 2.0 ** -126 <= x <= 2.0 ** 127):
+        raise ValueError('%s must be a power of two (an fp32 one: dividing by it must stay exact): %r' % (name, x))
+    return x
+
+
+class LossScaler:
+    """Dynamic loss scale of the fp16 matrix-core mode, kept on the device (NOT in the reference).  `state` = device float[4]
+    {S, found, good, skipped}: S the power-of-two scale, found the flag the gradient scan of a step sets on a NaN / inf, good the updates
+    applied in a row since S last changed, skipped the updates dropped so far.  The backward of a step is seeded with S read FROM THE
+    DEVICE (`seed()`), the update kernels divide it out again and drop the whole update when `found` is set, the end-of-step launch
+    halves S after a dropped update (down to min_scale) and doubles it after growth_interval applied ones in a row (up to max_scale):
+    no host code between a step's backward and its update, so a captured graph carries the scheme.  One scaler serves both optimizers of
+    a trainer: growth_interval counts updates of either network.  The counts are floats, exact to 2^24: a growth_interval beyond that is
+    never reached (a way to hold the scale)."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_interval=2000, min_scale=1.0, max_scale=2.0 ** 24, device=None):
+        self.init_scale = _power_of_two('init_scale', init_scale)
+        self.min_scale = _power_of_two('min_scale', min_scale)
+        self.max_scale = _power_of_two('max_scale', max_scale)
+        if not self.min_scale <= self.init_scale <= self.max_scale:
+            raise ValueError('min_scale <= init_scale <= max_scale does not hold: %r, %r, %r' % (min_scale, init_scale, max_scale))
+        if int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError('growth_interval must be a positive integer: %r' % (growth_interval,))
+        self.growth_interval = int(growth_interval)
+        self.state = torch.tensor([self.init_scale, 0.0, 0.0, 0.0], dtype=torch.float32, device=device if device is not None else lib._dev())
+
+    @property
+    def consts(self):
+        """(growth_interval, min_scale, max_scale): they ride in the end-of-step launch's arguments."""
+        return (self.growth_interval, self.min_scale, self.max_scale)
+
+    def seed(self):
+        """The 0-dim device VIEW of the scale: the backward's seed.  A view, so a captured graph reads the value current at each replay."""
+        return self.state[0]
+
+    def scale(self):
+        """The current scale as a float.  Reads device memory: outside captured regions, at logging cadence."""
+        return float(self.state[0].item())
+
+    def skipped_steps(self):
+        """Updates (of either network) dropped so far because their gradients held a NaN / inf.  Reads device memory, as scale()."""
+        return int(self.state[3].item())
+
+    def good_steps(self):
+        """Updates applied in a row since the scale last changed.  Reads device memory, as scale()."""
+        return int(self.state[2].item())
+
+    def state_dict(self):
+        return {'state': self.state.cpu().clone()}
+
+    def load_state_dict(self, sd):
+        """sd None (a checkpoint of a run without a dynamic scale): start over at init_scale."""
+        if sd is None:
+            self.state.copy_(torch.tensor([self.init_scale, 0.0, 0.0, 0.0]))
+            return
+        st = sd['state'].to(torch.float32)
+        _power_of_two('the saved scale', st[0].item())
+        self.state.copy_(st)
+        self.state[1:2].zero_()           # (the flag lives within one step)
+
+
 class FlatAdam:
     kind = 'adam'
 
-    def __init__(self, named_params, beta1, beta2, eps=1e-8, state=None, avg_rate=0.0):
+    def __init__(self, named_params, beta1, beta2, eps=1e-8, state=None, avg_rate=0.0, scaler=None):
         """named_params: [(name, Parameter)] - the trainable variable list, in registry order.  state: optional float[4] device
         slice to keep {lr, beta1^t, beta2^t, -} in (two optimizers sharing one allocation take a common learning rate in one fill).
         avg_rate > 0 (NOT in the reference; the GAN trainers' `g_average`): keep `avg`, an exponential moving average of the weights laid
         out like `theta` - avg <- avg + avg_rate (theta - avg), moved by the update's own launch (csrc/optim_rng.hip avg_elem), so a rate
         of 1e-4 is a decay of 0.9999 - starting at a COPY of the weights (FlatAdamTheano's starts at zeros, as its script's does).  0: no
-        average, and nothing differs from an optimizer built without the argument (launches, slots(), state_dict())."""
+        average, and nothing differs from an optimizer built without the argument (launches, slots(), state_dict()).
+        scaler (NOT in the reference): a LossScaler, shared with the trainer's other optimizer - update() and step() then run scan ->
+        scaled update -> scaled end of step (kernels.grads_nonfinite, the `scaler=` forms), one launch more than without; the
+        grad_scale they are given is the host's factor only (1 / world), the division by the scale happens on the device.  None: nothing
+        differs.  `t` counts ATTEMPTED updates on the host, dropped ones included: with a scaler the beta powers on the device (state[1],
+        state[2]) are what knows how many were applied."""
+        self.scaler = scaler
         self.avg_rate = float(avg_rate)
         if not 0.0 <= self.avg_rate <= 1.0:
             raise ValueError('avg_rate must be in [0, 1] (it is the rate 1 - decay, e.g. 1e-4 for a decay of 0.9999): %r' % (avg_rate,))
@@ -110,19 +180,28 @@ class FlatAdam:
     def step(self, grad_scale=1.0, rng=None):
         """theta <- Adam(theta, grad); then ONE launch advances the beta-power accumulators and, with `rng`, that stream's step
         counter (DeviceRNG.end_step)."""
-        if self._avg_own:
-            K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale,
-                        avg=self.avg, avg_rate=self.avg_rate)
-        else:
-            K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale)
+        if self.scaler is not None:
+            K.grads_nonfinite(self.grad, self.scaler.state)         # (the bucket after the all-reduce: every rank sees the same bits)
+        K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale, **self._extras())
         self._end(rng)
+
+    def _extras(self):
+        """The keywords of an update launch beyond the static one's: each is OMITTED when its feature is off."""
+        kw = {'avg': self.avg, 'avg_rate': self.avg_rate} if self._avg_own else {}
+        if self.scaler is not None:
+            kw['scaler'] = self.scaler.state
+        return kw
 
     def avg_views(self):
         """[(name, view of the average shaped like the parameter)]"""
         return [(n, self.avg[o:o + s].view(p.shape)) for n, p, o, s in zip(self.names, self.params, self.offsets, self.sizes)]
 
     def _end(self, rng):
-        K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1)
+        if self.scaler is not None:
+            K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1, scaler=self.scaler.state,
+                           scaler_consts=self.scaler.consts)
+        else:
+            K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1)
         self.t += 1
         lib.bump_epoch(self.group)    # this network's weights changed: its derived-filter caches are stale
 
@@ -133,18 +212,18 @@ class FlatAdam:
             self.gather_grads(grads)
             return self.step(grad_scale, rng)
         srcs = [g.contiguous() if g is not None else None for g in grads]
-        if self._avg_own:
-            K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
-                               self.eps, grad_scale, avg=self.avg, avg_rate=self.avg_rate)
-        else:
-            K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
-                               self.eps, grad_scale)
+        if self.scaler is not None:
+            K.grads_nonfinite(srcs, self.scaler.state)
+        K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
+                           self.eps, grad_scale, **self._extras())
         self._keepalive = srcs
         self._end(rng)
 
     def update_clipped(self, grads, clip_norm, rng=None):
         """gather_grads, tf.clip_by_global_norm over the whole bucket (LS/tflib/train_loop_2.py:76-79), step.  Returns the norm BEFORE
         the clip as a float32 device scalar [1]; nothing crosses to the host (kernels.global_norm / clip_by_norm_)."""
+        if self.scaler is not None:
+            raise NotImplementedError('update_clipped: not under a dynamic loss scale (the norm would be the scaled gradient\'s)')
         self.gather_grads(grads)
         norm = K.global_norm(self.grad)
         K.clip_by_norm_(self.grad, norm, clip_norm)
@@ -153,11 +232,13 @@ class FlatAdam:
 
     def slots(self):
         """The device tensors a step writes besides the weights: what a graph capture's warm-up steps must leave as they found them (the
-        average too: on a resumed run avg != theta, and a step at learning rate 0 still moves it)."""
+        average too: on a resumed run avg != theta, and a step at learning rate 0 still moves it; the state of the loss scaler too: a
+        warm-up step that overflows must not halve the scale of the real run)."""
         return [self.m, self.v, self.state] + self._avg_slot()
 
     def _avg_slot(self):
-        return [self.avg] if self._avg_own else []
+        """(and the scaler's state: the tail of every slots() list)"""
+        return ([self.avg] if self._avg_own else []) + ([self.scaler.state] if self.scaler is not None else [])
 
     def _avg_state(self, sd):
         if self._avg_own:
@@ -233,9 +314,9 @@ class FlatRMSProp(FlatAdam):
 
     kind = 'rmsprop'
 
-    def __init__(self, named_params, rho=0.9, eps=1e-10, clip=None, state=None, avg_rate=0.0):
+    def __init__(self, named_params, rho=0.9, eps=1e-10, clip=None, state=None, avg_rate=0.0, scaler=None):
         # (FlatAdam's flat buffers, gather and end-of-step launch; its beta powers stay 1, so step_advance only moves the Philox counter)
-        super().__init__(named_params, 1.0, 1.0, eps, state, avg_rate)
+        super().__init__(named_params, 1.0, 1.0, eps, state, avg_rate, scaler)
         self.rho, self.clip = float(rho), float(clip or 0.0)
 
     def _alloc_slots(self, total, dev):
@@ -247,11 +328,9 @@ class FlatRMSProp(FlatAdam):
         return [self.ms, self.state] + ([self.theta] if self.clip > 0 else []) + self._avg_slot()
 
     def step(self, grad_scale=1.0, rng=None):
-        if self._avg_own:
-            K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale,
-                           avg=self.avg, avg_rate=self.avg_rate)
-        else:
-            K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale)
+        if self.scaler is not None:
+            K.grads_nonfinite(self.grad, self.scaler.state)
+        K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale, **self._extras())
         self._end(rng)
 
     def update(self, grads, grad_scale=1.0, rng=None):
@@ -259,12 +338,10 @@ class FlatRMSProp(FlatAdam):
             self.gather_grads(grads)
             return self.step(grad_scale, rng)
         srcs = [g.contiguous() if g is not None else None for g in grads]
-        if self._avg_own:
-            K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
-                                  grad_scale, avg=self.avg, avg_rate=self.avg_rate)
-        else:
-            K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
-                                  grad_scale)
+        if self.scaler is not None:
+            K.grads_nonfinite(srcs, self.scaler.state)
+        K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
+                              grad_scale, **self._extras())
         self._keepalive = srcs
         self._end(rng)
 
@@ -296,7 +373,9 @@ class FlatAdamTheano(FlatAdam):
 
     kind = 'adam_theano'
 
-    def __init__(self, named_params, beta1, beta2, eps=1e-8, avg_rate=0.0, state=None):
+    def __init__(self, named_params, beta1, beta2, eps=1e-8, avg_rate=0.0, state=None, scaler=None):
+        if scaler is not None:
+            raise ValueError('FlatAdamTheano takes no loss scaler: the classifiers it trains have no 16-bit mode with a loss scale')
         super().__init__(named_params, beta1, beta2, eps, state)
         self.avg_rate = float(avg_rate)
         self.avg = torch.zeros_like(self.theta) if self.avg_rate > 0 else None          # (its own: the base class was given no rate)

@@ -669,6 +669,36 @@ int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_o
  * aligned, with the n % 4 last elements one by one; element by element otherwise; n == 0: nothing is launched; overlapping
  * buffers: CTGAN_E_BADARG): the weights and their average change places without either address changing.                         */
 int ctgan_exchange(float* a, float* b, int64_t n, ctgan_stream_t stream);
+/* Dynamic loss scale of the fp16 matrix-core mode, kept on the device (build-only: NOT in the reference).  scaler = device float[4]
+ * {S, found, good, skipped}: S the power-of-two scale the step's backward is seeded with (the caller reads scaler[0] as the seed),
+ * found != 0 once this step's gradients held a NaN / inf, good = updates applied in a row since S last changed, skipped = updates dropped
+ * so far (float counts, exact to 2^24).  A step is three launches - scan, update, end of step - all stream-ordered, none reads the host:
+ *   ctgan_grads_nonfinite: scaler[1] = 1 if any element of the n_tensors (<= 64) sources is NaN or +-inf (raw bits: +-FLT_MAX, denormals
+ *     and -0 are finite); a NULL source is all zeros.  One source = the flat bucket after the all-reduce.  16-byte loads between a
+ *     source's first and last 16-byte boundary.  ctgan_grads_nonfinite_blocks: grid.x of that launch (its workgroups hold 256 threads,
+ *     each reads one 16-byte item per trip; grid.y = n_tensors), for the largest count and the number of sources.
+ *   ctgan_*_step*_scaled: the update entry points above (avg == NULL: without the weight average) with grad_scale / scaler[0] for
+ *     grad_scale - exact, S being a power of two: bit-identical to the static entry point called with that quotient - and, when
+ *     scaler[1] != 0, the WHOLE update dropped: no theta, m, v, ms changes (the RMSProp clip still clips, the average still moves towards
+ *     the weights as they are, the packed forms still write the bucket) and state[3] does not count its elements.  The per-element skip
+ *     of ctgan_adam_step stays in place on the steps that are applied.
+ *   ctgan_step_advance_scaled: ctgan_step_advance for such a step.  Applied: the beta powers advance, good += 1, and at growth_interval
+ *     in a row S = min(2 S, max_scale), good = 0.  Dropped: the beta powers stay, S = max(S / 2, min_scale), good = 0, skipped += 1.
+ *     Either way found = 0 and rng_ctr advances.  min_scale / max_scale: powers of two, min <= max (CTGAN_E_BADARG otherwise).        */
+unsigned ctgan_grads_nonfinite_blocks(int64_t max_count, int32_t n_tensors);
+int ctgan_grads_nonfinite(const float* const* srcs, const int64_t* counts, int32_t n_tensors, float* scaler, ctgan_stream_t stream);
+int ctgan_adam_step_scaled(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
+                           float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
+int ctgan_adam_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
+                                  float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
+                                  float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
+int ctgan_rmsprop_step_scaled(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
+                              float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
+int ctgan_rmsprop_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                                     float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
+                                     float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
+int ctgan_step_advance_scaled(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler,
+                              int64_t growth_interval, float min_scale, float max_scale, ctgan_stream_t stream);
 
 /* ---- RNG: Philox4x32-10 counter-based streams (tf.random_uniform / tf.random_normal /
  *      dropout masks :157,202,277,319).  counter base is read from device memory
