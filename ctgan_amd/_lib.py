@@ -286,6 +286,11 @@ SIGNATURES = {
     # all-pairs polynomial-kernel tile sums: the unbiased kernel distance (csrc/kid.hip)
     'ctgan_kernel_tile': (c_int, []),
     'ctgan_kernel_tile_sums': (c_int, [_p, c_int64, _p, c_int64, c_int32, c_double, c_double, c_int32, _p, _p]),
+    # the same per class of class-sorted operands, one launch for every class, and the fixed-order segment sums (csrc/knn.hip, csrc/kid.hip)
+    'ctgan_knn_radii_seg': (c_int, [_p, _p, c_int32, c_int64, c_int32, c_int32, _p, _p]),
+    'ctgan_knn_cover_seg': (c_int, [_p, _p, c_int64, _p, _p, c_int64, c_int32, c_int32, _p, _p, _p, _p, _p]),
+    'ctgan_kernel_tile_sums_seg': (c_int, [_p, _p, c_int64, _p, _p, c_int64, c_int32, c_int32, c_double, c_double, c_int32, _p, _p, _p]),
+    'ctgan_segment_sums': (c_int, [_p, _p, c_int32, _p, _p]),
     # differentiable augmentation of the critic's inputs, forward and adjoint (csrc/diffaug.hip)
     'ctgan_diffaug': (c_int, [_p, _p, c_float, _p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_int32, c_uint64, c_uint64, _p, _p, _p]),
 }

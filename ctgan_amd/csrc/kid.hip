@@ -32,6 +32,7 @@ constexpr int FILL = 512;         // workgroups asked for at least, when b has t
 constexpr int SLAB_MAX = 8;       // tiles of b per workgroup at most: the tail of a large launch stays a few percent of it
 constexpr long long GRID_Y_MAX = 65535;
 constexpr long long ROWS_MAX = 1LL << 30;
+constexpr int SEG_MAX_CLASSES = 32;      // the grouped kernel: moments.hip's limit
 static_assert(TM == TN, "a tile of sums is square: the same tile size names the rows of both operands");
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -40,105 +41,71 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 8))) void kernel_tile_sums_kernel(
     const float* __restrict__ a, long long m, const float* __restrict__ b, long long n, int d, double gamma, double coef0, bool exclude_diag,
     bool vec4, int slab, double* __restrict__ sums) {
-    __shared__ __attribute__((aligned(16))) float stage[TN][LDB];
-    __shared__ double wsum[WAVES];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
-    const long long row0 = (long long)blockIdx.x * TM + 16 * wave;
-    const long long arow = row0 + lc;                   // the row of a this lane loads as the A operand
-    const bool arow_ok = arow < m;
-    const float* ap = a + (arow_ok ? arow : m - 1) * d;      // a row past m reads the last one and is masked
+#define KID_BLK (long long)blockIdx.x
+#define KID_SLAB (long long)blockIdx.y
+#include "kid_tile_loop.h"
+#undef KID_BLK
+#undef KID_SLAB
+}
 
-    const int nchunk = (d + DK - 1) / DK;
-    const long long ntile = (n + TN - 1) / TN;
-    const long long tile0 = (long long)blockIdx.y * slab;
-    const long long tile1 = tile0 + slab < ntile ? tile0 + slab : ntile;      // the host launches no empty slab: tile0 < ntile
-    // the next chunk in registers: float4 e = tid + TPB u of the [TN][DK / 4] chunk of b (a row of the chunk per 16 lanes) and this lane's A
-    // operands of the chunk's 16 steps.  A chunk wholly inside b, with 16-byte aligned rows, is loaded without a test per element.
-    float pre[PRE], apre[DK / 4], acur[DK / 4];
-    auto fetch = [&](long long tile, int c) {
-        const bool k_full = (c + 1) * DK <= d;
-        if (vec4 && k_full && (tile + 1) * TN <= n) {
-            const float* src = b + (tile * TN + (tid >> 4)) * d + c * DK + 4 * (tid & 15);
-#pragma unroll
-            for (int u = 0; u < PRE / 4; ++u) {
-                const float4 v = *reinterpret_cast<const float4*>(src + (long long)(TPB / 16) * u * d);
-                pre[4 * u] = v.x, pre[4 * u + 1] = v.y, pre[4 * u + 2] = v.z, pre[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < PRE; ++u) {
-                const int e = tid + TPB * (u / 4);
-                const long long j = tile * TN + (e >> 4);
-                const int kg = c * DK + 4 * (e & 15) + (u & 3);
-                pre[u] = (j < n && kg < d) ? b[j * d + kg] : 0.f;
-            }
-        }
-        if (k_full) {
-#pragma unroll
-            for (int u = 0; u < DK / 4; ++u) apre[u] = ap[c * DK + 4 * u + lq];
-        } else {
-#pragma unroll
-            for (int u = 0; u < DK / 4; ++u) {
-                const int kg = c * DK + 4 * u + lq;
-                apre[u] = kg < d ? ap[kg] : 0.f;
-            }
-        }
-    };
-    fetch(tile0, 0);
-    for (long long tile = tile0; tile < tile1; ++tile) {
-        double4_t acc[SUB];
-#pragma unroll
-        for (int s = 0; s < SUB; ++s) acc[s] = double4_t{0., 0., 0., 0.};
-        for (int c = 0; c < nchunk; ++c) {
-            __syncthreads();      // the previous chunk's reads (and the previous tile's read of wsum) are done
-#pragma unroll
-            for (int u = 0; u < PRE / 4; ++u) {
-                const int e = tid + TPB * u;
-                *reinterpret_cast<float4*>(&stage[e >> 4][4 * (e & 15)]) = make_float4(pre[4 * u], pre[4 * u + 1], pre[4 * u + 2], pre[4 * u + 3]);
-            }
-#pragma unroll
-            for (int u = 0; u < DK / 4; ++u) acur[u] = arow_ok ? apre[u] : 0.f;
-            __syncthreads();
-            if (c + 1 < nchunk) fetch(tile, c + 1);
-            else if (tile + 1 < tile1) fetch(tile + 1, 0);
-            const int left = d - c * DK;      // a step past d adds exactly 0 and may be left out
-#pragma unroll
-            for (int u = 0; u < DK / 4; ++u) {
-                if (4 * u < left) {
-                    const int kk = 4 * u;
-                    const double av = (double)acur[u];
-                    double bv[SUB];
-#pragma unroll
-                    for (int s = 0; s < SUB; ++s) bv[s] = (double)stage[16 * s + lc][kk + lq];
-#pragma unroll
-                    for (int s = 0; s < SUB; ++s) acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[s], acc[s], 0, 0, 0);
-                }
-            }
-        }
+// ---- the grouped (per-class) kernel: class-sorted operands with device-resident segment starts seg[classes + 1] ----------------------
+// Segment start c of an operand of `rows` rows, clamped into [0, rows]: whatever the array holds, no row outside the operand is touched.
+__device__ __forceinline__ long long seg_at(const int* __restrict__ seg, int c, long long rows) {
+    const long long v = seg[c];
+    return v < 0 ? 0 : (v > rows ? rows : v);
+}
 
-        // this lane's 16 kernel values, masked by index, in the order (C tile, register)
-        const long long jt = tile * TN;
-        double part = 0.;
-#pragma unroll
-        for (int s = 0; s < SUB; ++s) {
-            const long long j = jt + 16 * s + lc;
-            const bool j_ok = j < n;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long long i = row0 + lq + 4 * r;
-                const double v = gamma * acc[s][r] + coef0;
-                const double k3 = (v * v) * v;
-                const bool keep = j_ok && i < m && !(exclude_diag && i == j);
-                part += keep ? k3 : 0.;
-            }
+// One launch for every class.  grid.x = ceil(m / 64) + classes >= sum_c ceil(m_c / 64): workgroup x -> (class, tile of the class's rows of a)
+// by a scan of seg_a (at most 33 scalar loads, uniform over the workgroup); grid.y = the slabs at the pooled bound ceil(n / 64).  A surplus
+// workgroup, and one whose slab starts past its class's tiles of b, returns before the loop's first barrier.  The pooled kernel's loop
+// (kid_tile_loop.h, the same text) then runs on the segment's bases and counts into the class's tile matrix at sums + toff[c]: the bits
+// kernel_tile_sums_kernel leaves from the gathered rows, for every slab length.  toff is the caller's (the exclusive prefix sums of
+// ceil(m_c / 64) ceil(n_c / 64)).  157 VGPRs, no scratch: the pooled kernel's three waves per SIMD.
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 8))) void kernel_tile_sums_seg_kernel(
+    const float* __restrict__ a, const int* __restrict__ seg_a, long long m, const float* __restrict__ b, const int* __restrict__ seg_b, long long n,
+    int classes, int d, double gamma, double coef0, bool exclude_diag, bool vec4, int slab, const long long* __restrict__ toff,
+    double* __restrict__ sums) {
+    const long long wg = blockIdx.x;
+    long long first = 0, a0 = seg_at(seg_a, 0, m), ma = 0, seg_tile = 0;
+    int cls = -1;
+    for (int c = 0; c < classes; ++c) {
+        const long long a1 = seg_at(seg_a, c + 1, m);
+        const long long cnt = a1 > a0 ? a1 - a0 : 0;
+        const long long t = (cnt + TM - 1) / TM;
+        if (wg < first + t) {
+            cls = c, seg_tile = wg - first, ma = cnt;
+            break;
         }
-        // the wave's 64 lanes: every lane ends with the same sum; then the four waves in order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-        if (lane == 0) wsum[wave] = part;
-        __syncthreads();
-        if (tid == 0) sums[(long long)blockIdx.x * ntile + tile] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        first += t;
+        a0 = a1 > a0 ? a1 : a0;
     }
+    if (cls < 0) return;
+    const long long b0 = seg_at(seg_b, cls, n), b1 = seg_at(seg_b, cls + 1, n);
+    const long long nb = b1 > b0 ? b1 - b0 : 0;
+    if ((long long)blockIdx.y * slab >= (nb + TN - 1) / TN) return;
+    a += a0 * d, b += b0 * d, m = ma, n = nb, sums += toff[cls];
+#define KID_BLK seg_tile
+#define KID_SLAB (long long)blockIdx.y
+#include "kid_tile_loop.h"
+#undef KID_BLK
+#undef KID_SLAB
+}
+
+// out[s] = the fp64 sum of vals[off[s] : off[s + 1]]: one workgroup per segment, thread t adds elements t, t + 256, ... in index order, then
+// an LDS tree in a fixed order.  Nothing of the order depends on the grid: the same bits on every run.  An empty segment gives 0.
+constexpr int SEG_TPB = 256;
+__global__ __launch_bounds__(SEG_TPB) void segment_sums_kernel(const double* __restrict__ vals, const long long* __restrict__ off, double* __restrict__ out) {
+    __shared__ double part[SEG_TPB];
+    const long long lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
+    double acc = 0.;
+    for (long long i = lo + threadIdx.x; i < hi; i += SEG_TPB) acc += vals[i];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = SEG_TPB / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = part[0];
 }
 
 inline hipStream_t S(ctgan_stream_t s) { return static_cast<hipStream_t>(s); }
@@ -179,6 +146,33 @@ int ctgan_kernel_tile_sums(const float* a, int64_t m, const float* b, int64_t n,
     hipLaunchKernelGGL(kernel_tile_sums_kernel, dim3((unsigned)mt, (unsigned)((nt + slab - 1) / slab)), dim3(TPB), 0, S(stream), a, (long long)m, b,
                        (long long)n, d, gamma, coef0, exclude_diag != 0, rows_vec4(b, d), slab, sums);
     return ctgan_check_launch("kernel_tile_sums");
+}
+
+int ctgan_kernel_tile_sums_seg(const float* a, const int32_t* seg_a, int64_t m, const float* b, const int32_t* seg_b, int64_t n, int32_t classes,
+                               int32_t d, double gamma, double coef0, int32_t exclude_diag, const int64_t* toff, double* sums, ctgan_stream_t stream) {
+    if (classes > SEG_MAX_CLASSES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "kernel_tile_sums_seg: %d classes (at most %d)", classes, SEG_MAX_CLASSES);
+    if (d > DMAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "kernel_tile_sums_seg: %d features (at most %d)", d, DMAX);
+    if (classes < 1 || d < 1 || m < 1 || n < 1 || m > ROWS_MAX || n > ROWS_MAX)
+        return ctgan_fail(CTGAN_E_BADARG, "kernel_tile_sums_seg: bad argument (classes %d m %lld n %lld d %d)", classes, (long long)m, (long long)n, d);
+    if (exclude_diag && (a != b || seg_a != seg_b || m != n))
+        return ctgan_fail(CTGAN_E_BADARG, "kernel_tile_sums_seg: exclude_diag is for a set against itself (the same operand and segments twice)");
+    if (!a || !b || !seg_a || !seg_b || !toff || !sums) return ctgan_fail(CTGAN_E_BADARG, "kernel_tile_sums_seg: a null pointer");
+    if (misaligned8(sums) || misaligned8(toff)) return ctgan_fail(CTGAN_E_BADARG, "kernel_tile_sums_seg: sums or toff not 8-byte aligned");
+    const long long mt = (m + TM - 1) / TM + classes, nt = (n + TN - 1) / TN;
+    const int slab = slab_length(mt, nt);
+    hipLaunchKernelGGL(kernel_tile_sums_seg_kernel, dim3((unsigned)mt, (unsigned)((nt + slab - 1) / slab)), dim3(TPB), 0, S(stream), a, seg_a, (long long)m, b,
+                       seg_b, (long long)n, classes, d, gamma, coef0, exclude_diag != 0, rows_vec4(b, d), slab,
+                       reinterpret_cast<const long long*>(toff), sums);
+    return ctgan_check_launch("kernel_tile_sums_seg");
+}
+
+int ctgan_segment_sums(const double* vals, const int64_t* off, int32_t segments, double* out, ctgan_stream_t stream) {
+    if (segments < 0) return ctgan_fail(CTGAN_E_BADARG, "segment_sums: %d segments", segments);
+    if (segments == 0) return CTGAN_OK;
+    if (!vals || !off || !out) return ctgan_fail(CTGAN_E_BADARG, "segment_sums: a null pointer");
+    if (misaligned8(vals) || misaligned8(off) || misaligned8(out)) return ctgan_fail(CTGAN_E_BADARG, "segment_sums: arrays not 8-byte aligned");
+    hipLaunchKernelGGL(segment_sums_kernel, dim3((unsigned)segments), dim3(SEG_TPB), 0, S(stream), vals, reinterpret_cast<const long long*>(off), out);
+    return ctgan_check_launch("segment_sums");
 }
 
 }  // extern "C"

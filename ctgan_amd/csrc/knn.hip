@@ -31,6 +31,7 @@ constexpr int LDB = DK + 4;       // row stride of the staged tile in floats: ba
 constexpr int PRE = TN * DK / TPB;
 constexpr int DMAX = 1024;
 constexpr int KNN_MAX_K = 8;
+constexpr int SEG_MAX_CLASSES = 32;      // the grouped kernels: moments.hip's limit
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -44,9 +45,12 @@ __device__ __forceinline__ void insert_sorted(double (&top)[KNN_MAX_K], double v
         }
 }
 
-// RADII: b == a, n == m, r2out [m].  Otherwise: r2b [n] or null, covered / nn_d2 / nn_idx [m].
-template <bool RADII>
-__device__ __forceinline__ void knn_body(const float* __restrict__ a, long long m, const float* __restrict__ b, long long n, int d, int k, bool vec4,
+// RADII: b == a, n == m, r2out [m].  Otherwise: r2b [n] or null, covered / nn_d2 / nn_idx [m].  The workgroup owns tile blockIdx.x of
+// 64 rows of a; SEG (the grouped kernels): tile blk inside a class's segment, with the segment's bases and counts as a, m, b, n and the
+// outputs.  The flag is a template parameter so that the pooled kernels compile to the instructions they had before it existed.
+// n == 0 (cover, SEG only): nothing of b or r2b is read and the selection stays at its start - not covered, +inf, -1.
+template <bool RADII, bool SEG = false>
+__device__ __forceinline__ void knn_body(long long blk, const float* __restrict__ a, long long m, const float* __restrict__ b, long long n, int d, int k, bool vec4,
                                          const double* __restrict__ r2b, double* __restrict__ r2out, int* __restrict__ covered,
                                          double* __restrict__ nn_d2, int* __restrict__ nn_idx) {
     __shared__ __attribute__((aligned(16))) float stage[TN][LDB];
@@ -56,7 +60,7 @@ __device__ __forceinline__ void knn_body(const float* __restrict__ a, long long 
     __shared__ int mrg_j[RADII ? 1 : WAVES][64][4];
     __shared__ int mrg_c[RADII ? 1 : WAVES][64][4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
-    const long long row0 = (long long)blockIdx.x * TM + 16 * wave;
+    const long long row0 = (SEG ? blk : (long long)blockIdx.x) * TM + 16 * wave;
     const long long arow = row0 + lc;                   // the row of a this lane loads as the A operand
     const bool arow_ok = arow < m;
     const float* ap = a + (arow_ok ? arow : m - 1) * d;      // a row past m reads the last one and is masked
@@ -251,13 +255,64 @@ __device__ __forceinline__ void knn_body(const float* __restrict__ a, long long 
 // Two entry kernels over one body.  Both compile to two waves per SIMD (the radii kernel by itself: 213 VGPRs + 40 AGPRs with its 64
 // registers of sorted top-k state; the cover kernel is held to it: 179 VGPRs), no scratch, 34 KB of LDS.
 __global__ __launch_bounds__(TPB) void knn_radii_kernel(const float* __restrict__ f, long long n, int d, int k, bool vec4, double* __restrict__ r2) {
-    knn_body<true>(f, n, f, n, d, k, vec4, nullptr, r2, nullptr, nullptr, nullptr);
+    knn_body<true>(0, f, n, f, n, d, k, vec4, nullptr, r2, nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 8))) void knn_cover_kernel(
     const float* __restrict__ a, long long m, const float* __restrict__ b, long long n, int d, bool vec4, const double* __restrict__ r2b,
     int* __restrict__ covered, double* __restrict__ nn_d2, int* __restrict__ nn_idx) {
-    knn_body<false>(a, m, b, n, d, 0, vec4, r2b, nullptr, covered, nn_d2, nn_idx);
+    knn_body<false>(0, a, m, b, n, d, 0, vec4, r2b, nullptr, covered, nn_d2, nn_idx);
+}
+
+// ---- the grouped (per-class) kernels: class-sorted operands with device-resident segment starts seg[classes + 1] ----------------------
+// Segment start c of an operand of `rows` rows, clamped into [0, rows]: whatever the array holds, no row outside the operand is touched.
+__device__ __forceinline__ long long seg_at(const int* __restrict__ seg, int c, long long rows) {
+    const long long v = seg[c];
+    return v < 0 ? 0 : (v > rows ? rows : v);
+}
+
+// Workgroup wg of a grid of ceil(rows / TM) + classes -> its class and its tile of TM rows inside the class's segment, by a scan of the
+// segment starts (at most 33 scalar loads; uniform over the workgroup).  false: a surplus workgroup, sum_c ceil(rows_c / TM) <= wg.
+__device__ __forceinline__ bool seg_locate(const int* __restrict__ seg, int classes, long long rows, long long wg, int& cls, long long& tile,
+                                           long long& start, long long& count) {
+    long long first = 0, s0 = seg_at(seg, 0, rows);
+    for (int c = 0; c < classes; ++c) {
+        const long long s1 = seg_at(seg, c + 1, rows);
+        const long long cnt = s1 > s0 ? s1 - s0 : 0;
+        const long long t = (cnt + TM - 1) / TM;
+        if (wg < first + t) {
+            cls = c, tile = wg - first, start = s0, count = cnt;
+            return true;
+        }
+        first += t;
+        s0 = s1 > s0 ? s1 : s0;
+    }
+    return false;
+}
+
+// One launch for every class: workgroup -> (class, tile of the class's rows), then the pooled body on the segment's bases and counts, so
+// class c receives the bits knn_radii_kernel / knn_cover_kernel leave from the gathered rows.  A surplus workgroup returns before the
+// body's first barrier.  Two waves per SIMD as the pooled kernels, no scratch: 249 VGPRs (radii), 179 (cover); DESIGN 27.
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 8))) void knn_radii_seg_kernel(
+    const float* __restrict__ f, const int* __restrict__ seg, int classes, long long n, int d, int k, bool vec4, double* __restrict__ r2) {
+    int cls;
+    long long tile, s0, cnt;
+    if (!seg_locate(seg, classes, n, blockIdx.x, cls, tile, s0, cnt)) return;
+    const float* base = f + s0 * d;
+    knn_body<true, true>(tile, base, cnt, base, cnt, d, k, vec4, nullptr, r2 + s0, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 8))) void knn_cover_seg_kernel(
+    const float* __restrict__ a, const int* __restrict__ seg_a, long long m, const float* __restrict__ b, const int* __restrict__ seg_b,
+    long long n, int classes, int d, bool vec4, const double* __restrict__ r2b, int* __restrict__ covered, double* __restrict__ nn_d2,
+    int* __restrict__ nn_idx) {
+    int cls;
+    long long tile, a0, ma;
+    if (!seg_locate(seg_a, classes, m, blockIdx.x, cls, tile, a0, ma)) return;
+    const long long b0 = seg_at(seg_b, cls, n), b1 = seg_at(seg_b, cls + 1, n);
+    const long long nb = b1 > b0 ? b1 - b0 : 0;
+    knn_body<false, true>(tile, a + a0 * d, ma, b + b0 * d, nb, d, 0, vec4, r2b ? r2b + b0 : nullptr, nullptr, covered ? covered + a0 : nullptr,
+                    nn_d2 + a0, nn_idx + a0);
 }
 
 inline hipStream_t S(ctgan_stream_t s) { return static_cast<hipStream_t>(s); }
@@ -294,6 +349,33 @@ int ctgan_knn_cover(const float* a, int64_t m, const float* b, int64_t n, int32_
     hipLaunchKernelGGL(knn_cover_kernel, dim3((unsigned)((m + TM - 1) / TM)), dim3(TPB), 0, S(stream), a, (long long)m, b, (long long)n, d, rows_vec4(b, d), r2_b,
                        r2_b ? covered : (int*)nullptr, nn_d2, nn_idx);
     return ctgan_check_launch("knn_cover");
+}
+
+int ctgan_knn_radii_seg(const float* f, const int32_t* seg, int32_t classes, int64_t n, int32_t d, int32_t k, double* r2, ctgan_stream_t stream) {
+    if (classes > SEG_MAX_CLASSES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "knn_radii_seg: %d classes (at most %d)", classes, SEG_MAX_CLASSES);
+    if (d > DMAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "knn_radii_seg: %d features (at most %d)", d, DMAX);
+    if (k > KNN_MAX_K) return ctgan_fail(CTGAN_E_UNSUPPORTED, "knn_radii_seg: k = %d (at most %d)", k, KNN_MAX_K);
+    if (classes < 1 || k < 1 || d < 1 || n < 0 || n > 0x7fffffffLL)
+        return ctgan_fail(CTGAN_E_BADARG, "knn_radii_seg: bad argument (classes %d n %lld d %d k %d)", classes, (long long)n, d, k);
+    if (n == 0) return CTGAN_OK;
+    if (!f || !seg || !r2 || misaligned8(r2)) return ctgan_fail(CTGAN_E_BADARG, "knn_radii_seg: a null pointer, or radii not 8-byte aligned");
+    hipLaunchKernelGGL(knn_radii_seg_kernel, dim3((unsigned)((n + TM - 1) / TM + classes)), dim3(TPB), 0, S(stream), f, seg, classes, (long long)n, d, k,
+                       rows_vec4(f, d), r2);
+    return ctgan_check_launch("knn_radii_seg");
+}
+
+int ctgan_knn_cover_seg(const float* a, const int32_t* seg_a, int64_t m, const float* b, const int32_t* seg_b, int64_t n, int32_t classes, int32_t d,
+                        const double* r2_b, int32_t* covered, double* nn_d2, int32_t* nn_idx, ctgan_stream_t stream) {
+    if (classes > SEG_MAX_CLASSES) return ctgan_fail(CTGAN_E_UNSUPPORTED, "knn_cover_seg: %d classes (at most %d)", classes, SEG_MAX_CLASSES);
+    if (d > DMAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "knn_cover_seg: %d features (at most %d)", d, DMAX);
+    if (classes < 1 || d < 1 || m < 0 || n < 0 || m > 0x7fffffffLL || n > 0x7fffffffLL)
+        return ctgan_fail(CTGAN_E_BADARG, "knn_cover_seg: bad argument (classes %d m %lld n %lld d %d)", classes, (long long)m, (long long)n, d);
+    if (m == 0) return CTGAN_OK;
+    if (!a || !seg_a || !seg_b || (n > 0 && !b) || !nn_d2 || !nn_idx || (r2_b && !covered)) return ctgan_fail(CTGAN_E_BADARG, "knn_cover_seg: a null pointer");
+    if (misaligned8(r2_b) || misaligned8(nn_d2)) return ctgan_fail(CTGAN_E_BADARG, "knn_cover_seg: fp64 arrays not 8-byte aligned");
+    hipLaunchKernelGGL(knn_cover_seg_kernel, dim3((unsigned)((m + TM - 1) / TM + classes)), dim3(TPB), 0, S(stream), a, seg_a, (long long)m, b, seg_b,
+                       (long long)n, classes, d, rows_vec4(b, d), r2_b, r2_b ? covered : (int*)nullptr, nn_d2, nn_idx);
+    return ctgan_check_launch("knn_cover_seg");
 }
 
 }  // extern "C"

@@ -351,7 +351,8 @@ def record_score(ev, series, classifier, averaged=False):
     and, when the scorer has a reference (ClassifierScore.set_reference), `frechet`: the classifier Frechet distance to it; when it has
     a manifold (ClassifierScore.set_manifold), `precision`, `recall` and `nn_dist`: the k-nearest-neighbour manifold estimate against it; when it has a class reference
     (ClassifierScore.set_class_reference), `intra_frechet`: the mean per-class Frechet distance to it; when it has a kernel reference
-    (ClassifierScore.set_kernel_reference), `kid`: the unbiased kernel distance to it.  averaged (NOT in the reference): the samples come
+    (ClassifierScore.set_kernel_reference), `kid`: the unbiased kernel distance to it; when it has a class manifold or a class kernel
+    reference (set_class_manifold, set_class_kernel_reference), `intra_precision` and `intra_recall`, or `intra_kid`.  averaged (NOT in the reference): the samples come
     from the generator's weight average (trainer.averaged) and every series name gets the suffix `_avg` (`inception_50k_avg`,
     `frechet_avg`, `kid_avg`, ...); the loops call it after the live scoring, on the next steps of the evaluation stream."""
     if ev.name not in SCORE_SERIES:
@@ -367,7 +368,7 @@ def record_score(ev, series, classifier, averaged=False):
             series.add('score_acc' + sfx, res['acc'])
         if 'frechet' in res:
             series.add('frechet' + sfx, res['frechet'])
-        for name in ('precision', 'recall', 'nn_dist', 'intra_frechet', 'kid'):
+        for name in ('precision', 'recall', 'nn_dist', 'intra_frechet', 'kid', 'intra_precision', 'intra_recall', 'intra_kid'):
             if name in res:
                 series.add(name + sfx, res[name])
         return

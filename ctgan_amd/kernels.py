@@ -2881,3 +2881,115 @@ def kernel_tile_sums(a, b, gamma=None, coef0=1.0, exclude_diag=False, out=None):
     check(lib.ctgan_kernel_tile_sums(_ptr(a), m, _ptr(b), n, d, 1.0 / d if gamma is None else float(gamma), float(coef0), int(bool(exclude_diag)),
                                      _ptr(out), _stream()), 'kernel_tile_sums')
     return out
+
+
+# ---------------------------------------------------------------- the same per class: class-sorted operands (csrc/knn.hip, csrc/kid.hip)
+SEG_MAX_CLASSES = 32
+
+
+def class_segments(labels, classes):
+    """int labels [n] -> (perm int64 [n], seg int32 [classes + 1]) on the labels' device, with torch alone and no count on the host: perm
+    is the stable sort by class - feat.index_select(0, perm) has the rows of class 0 first, then class 1, ..., in their original order
+    inside a class, and the rows with a label outside [0, classes) behind them all - and class c is rows [seg[c], seg[c + 1]) of it."""
+    assert labels.dim() == 1 and not labels.dtype.is_floating_point and 1 <= classes <= SEG_MAX_CLASSES, 'int labels [n], 1 to 32 classes expected'
+    key = labels.to(torch.int64)
+    key = torch.where((key < 0) | (key >= classes), torch.full_like(key, classes), key)
+    perm = torch.argsort(key, stable=True)
+    seg = torch.searchsorted(key.index_select(0, perm), torch.arange(classes + 1, dtype=torch.int64, device=labels.device))
+    return perm, seg.to(torch.int32)
+
+
+def _seg(seg, what):
+    if not seg.is_cuda:
+        raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % seg.device)
+    assert seg.dtype == torch.int32 and seg.dim() == 1 and seg.is_contiguous() and 2 <= seg.numel() <= SEG_MAX_CLASSES + 1, \
+        '%s: contiguous int32 segment starts [classes + 1], 1 to %d classes, expected' % (what, SEG_MAX_CLASSES)
+    return seg.numel() - 1
+
+
+def knn_radii_seg(feat, seg, k, out=None):
+    """knn_radii per class, in one launch: feat fp32 [n, D] CLASS-SORTED (class_segments), seg int32 [K + 1] its segment starts on the
+    device -> fp64 [n] in sorted order: the squared distance from every row to its k-th nearest other row of ITS OWN class - the bits
+    knn_radii gives on the class's rows alone; +inf where the class has fewer than k + 1 rows; rows at or behind seg[K] are not written.
+    No count comes to the host.  K <= 32, 1 <= k <= KNN_MAX_K, D <= 1024."""
+    _need_dev(feat)
+    n, d = _rows2d(feat)
+    classes = _seg(seg, 'knn_radii_seg')
+    out = _knn_out(out, n, torch.float64, 'knn_radii_seg', feat.device)
+    check(lib.ctgan_knn_radii_seg(_ptr(feat), _ptr(seg), classes, n, d, int(k), _ptr(out), _stream()), 'knn_radii_seg')
+    return out
+
+
+def knn_cover_seg(a, seg_a, b, seg_b, r2_b=None, covered=None, nn_d2=None, nn_idx=None):
+    """knn_cover per class, in one launch: class-sorted a fp32 [m, D] and b fp32 [n, D] with their segment starts seg_a, seg_b int32
+    [K + 1], the radii r2_b fp64 [n] in b's sorted order (None: nearest neighbours only) -> (covered, nn_d2, nn_idx) as knn_cover, row
+    i of class c against the rows of class c of b only - the bits knn_cover gives on the two classes' rows alone; nn_idx counts from the
+    start of the class's segment of b.  A class without rows in b: (0, +inf, -1).  Rows of a at or behind seg_a[K] are not written."""
+    _need_dev(a, b)
+    if r2_b is not None and not r2_b.is_cuda:
+        raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % r2_b.device)
+    m, d = _rows2d(a)
+    n, db = _rows2d(b)
+    assert d == db, 'knn_cover_seg: %d and %d features' % (d, db)
+    classes = _seg(seg_a, 'knn_cover_seg')
+    assert _seg(seg_b, 'knn_cover_seg') == classes, 'knn_cover_seg: the two operands have different class counts'
+    assert r2_b is None or (r2_b.dtype == torch.float64 and r2_b.is_contiguous() and r2_b.numel() == n), 'knn_cover_seg: fp64 radii [n] expected'
+    covered = None if r2_b is None else _knn_out(covered, m, torch.int32, 'knn_cover_seg', a.device)
+    nn_d2 = _knn_out(nn_d2, m, torch.float64, 'knn_cover_seg', a.device)
+    nn_idx = _knn_out(nn_idx, m, torch.int32, 'knn_cover_seg', a.device)
+    check(lib.ctgan_knn_cover_seg(_ptr(a), _ptr(seg_a), m, _ptr(b), _ptr(seg_b), n, classes, d, _ptr(r2_b), _ptr(covered), _ptr(nn_d2),
+                                  _ptr(nn_idx), _stream()), 'knn_cover_seg')
+    return covered, nn_d2, nn_idx
+
+
+def segment_tile_offsets(seg_a, seg_b):
+    """int64 [K + 1] on the device: the exclusive prefix sums of ceil(m_c / KERNEL_TILE) ceil(n_c / KERNEL_TILE) - where class c's tile
+    matrix starts in the sums of kernel_tile_sums_seg."""
+    t = KERNEL_TILE
+    tiles = lambda seg: (seg[1:].to(torch.int64) - seg[:-1].to(torch.int64) + (t - 1)) // t      # noqa: E731
+    toff = torch.zeros(seg_a.numel(), dtype=torch.int64, device=seg_a.device)
+    toff[1:] = torch.cumsum(tiles(seg_a) * tiles(seg_b), 0)
+    return toff
+
+
+def kernel_tile_sums_seg(a, seg_a, b, seg_b, gamma=None, coef0=1.0, exclude_diag=False, out=None):
+    """kernel_tile_sums per class, in one launch: class-sorted a fp32 [m, D] and b fp32 [n, D] with their segment starts
+    -> (sums fp64 [(ceil(m / 64) + K) (ceil(n / 64) + 1)] zero-filled - a bound from m, n and K alone, no count comes to the host -, toff
+    int64 [K + 1] on the device): class c's tile matrix [ceil(m_c / 64), ceil(n_c / 64)] of kernel_tile_sums on the two classes' rows
+    alone (the same bits) lies row-major at sums[toff[c]:toff[c + 1]]; what lies behind toff[K] stays 0.  exclude_diag: a set against
+    itself (pass b = a and seg_b = seg_a) without the pairs i == j of a class.  out: a caller's buffer of that size, zeroed here."""
+    _need_dev(a, b)
+    m, d = _rows2d(a)
+    n, db = _rows2d(b)
+    assert d == db, 'kernel_tile_sums_seg: %d and %d features' % (d, db)
+    classes = _seg(seg_a, 'kernel_tile_sums_seg')
+    assert _seg(seg_b, 'kernel_tile_sums_seg') == classes, 'kernel_tile_sums_seg: the two operands have different class counts'
+    assert not exclude_diag or (a.data_ptr() == b.data_ptr() and seg_a.data_ptr() == seg_b.data_ptr() and m == n), \
+        'kernel_tile_sums_seg: exclude_diag is for a set against itself (b = a, seg_b = seg_a)'
+    size = (-(-m // KERNEL_TILE) + classes) * (-(-n // KERNEL_TILE) + 1)
+    if out is None:
+        out = torch.zeros(size, dtype=torch.float64, device=a.device)
+    else:
+        if not out.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % out.device)
+        assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (size,), \
+            'kernel_tile_sums_seg: contiguous fp64 [%d] expected' % size
+        out.zero_()
+    toff = segment_tile_offsets(seg_a, seg_b)
+    check(lib.ctgan_kernel_tile_sums_seg(_ptr(a), _ptr(seg_a), m, _ptr(b), _ptr(seg_b), n, classes, d, 1.0 / d if gamma is None else float(gamma),
+                                         float(coef0), int(bool(exclude_diag)), _ptr(toff), _ptr(out), _stream()), 'kernel_tile_sums_seg')
+    return out, toff
+
+
+def segment_sums(vals, off, out=None):
+    """vals fp64 [L], off int64 [S + 1] on the device -> fp64 [S]: out[s] = the sum of vals[off[s]:off[s + 1]] in ONE fixed order that does
+    not depend on the grid (the same bits on every run); an empty segment gives 0."""
+    for t in (vals, off):
+        if not t.is_cuda:
+            raise RuntimeError('ctgan_amd kernels need HIP device tensors (got %s); there is no CPU fallback' % t.device)
+    assert vals.dtype == torch.float64 and vals.dim() == 1 and vals.is_contiguous(), 'segment_sums: contiguous fp64 [L] values expected'
+    assert off.dtype == torch.int64 and off.dim() == 1 and off.is_contiguous() and off.numel() >= 1, 'segment_sums: contiguous int64 [S + 1] offsets expected'
+    s = off.numel() - 1
+    out = _knn_out(out, s, torch.float64, 'segment_sums', vals.device)
+    check(lib.ctgan_segment_sums(_ptr(vals), _ptr(off), s, _ptr(out), _stream()), 'segment_sums')
+    return out

@@ -71,6 +71,20 @@ does not depend on either count, with `'kid_blocks'`, the same estimate on disjo
     tile sums -> estimate, blocks          fp64 torch reductions on the device, in the scoring's one device -> host copy
 A classifier-feature kernel distance under a self-trained 10-class network's 128 features: NOT comparable to published KID (Inception
 pool3, 2048 features).
+
+Per-class precision, recall and kernel distance.  The two distances above pool the ten classes as well: a conditional generator that
+drops modes inside class 3 keeps a good pooled recall, because the other nine classes cover the reference set.  With a class manifold
+(`class_manifold=` / `set_class_manifold`) or a class kernel reference (`class_kernel_reference=` / `set_class_kernel_reference`), LABELLED
+FeatureSets (`features(images, labels=...)`), `score` with labels and `score_generator` of a conditional generator also return
+`'precision_class'`, `'recall_class'`, `'nn_dist_class'`, `'nn_zero_class'`, `'intra_precision'`, `'intra_recall'`, or `'kid_class'` and
+`'intra_kid'`, with `'n_class'` and `'n_class_reference'` (class_precision_recall, class_kernel_distance).
+    features [n, D], labels [n] -> sorted by class   kernels.class_segments: torch on the device, the segment starts stay there
+    every class in one launch                        kernels.knn_cover_seg, knn_radii_seg, kernel_tile_sums_seg: the pooled kernels' bodies
+                                                     on a class's segment (the same bits as on its gathered rows), once, after the last chunk
+    ragged tile sums -> per-class totals             kernels.segment_sums: one fixed order
+    counts, medians                                  cumsum differences and sorts on the device, in the scoring's one device -> host copy
+No class count comes to the host before that copy.  Classifier statistics under a self-trained 10-class network once more: NOT
+comparable to published per-class precision / recall or intra-class KID.
 """
 import hashlib
 import os
@@ -233,9 +247,14 @@ def intra_frechet(a, b):
 class FeatureSet:
     """The feature rows themselves, fp32 [n, D], of a set under the classifier with hash `classifier` (None: synthetic), with the squared
     k-th-neighbour radii that `radii(k)` computes on the device once per k and keeps (and `save` writes with the features), and the set's
-    own kernel tile sums that `kernel_tiles()` computes once and keeps (and `save` writes once they exist)."""
+    own kernel tile sums that `kernel_tiles()` computes once and keeps (and `save` writes once they exist).
+    labels (int [n], with classes, 1 to MAX_CLASSES): the class of every row, for class_precision_recall and class_kernel_distance; a
+    label outside [0, classes) belongs to no class.  `by_class()` sorts the rows by class on the device once; `class_radii(k)` and
+    `class_kernel_totals()` are the per-class counterparts of `radii` and `kernel_tiles`, computed once, kept and saved.  A set without
+    labels holds, and saves, exactly what it did before labels existed."""
 
-    def __init__(self, features, classifier=None, radii=None, kernel_tiles=None):
+    def __init__(self, features, classifier=None, radii=None, kernel_tiles=None, labels=None, classes=None, class_radii=None,
+                 class_kernel_totals=None):
         f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32))
         if f.dim() != 2 or f.dtype != torch.float32 or f.shape[0] < 1 or f.shape[1] < 1:
             raise ValueError('FeatureSet: fp32 [n, D] features expected (got %s %s)' % (f.dtype, tuple(f.shape)))
@@ -254,6 +273,29 @@ class FeatureSet:
             if t.dtype != torch.float64 or tuple(t.shape) != (tiles, tiles):
                 raise ValueError('FeatureSet: kernel tile sums are not fp64 [%d, %d]' % (tiles, tiles))
             self._kernel_tiles = t.contiguous()
+        self.labels, self.classes = None, None
+        self._by_class, self._class_radii, self._class_kernel_totals = None, {}, None
+        if labels is None:
+            if classes is not None or class_radii or class_kernel_totals is not None:
+                raise ValueError('FeatureSet: classes, class radii or class kernel totals without labels')
+            return
+        lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+        if lab.dim() != 1 or lab.shape[0] != self.n or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+            raise ValueError('FeatureSet: int labels [%d] expected (got %s %s)' % (self.n, lab.dtype, tuple(lab.shape)))
+        if classes is None or int(classes) < 1 or int(classes) > MAX_CLASSES:
+            raise ValueError('FeatureSet: labels need classes= (1 to %d; got %s)' % (MAX_CLASSES, classes))
+        self.labels, self.classes = lab.detach().to(torch.int32).contiguous(), int(classes)
+        for k, r in (class_radii or {}).items():
+            r = r if isinstance(r, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(r, dtype=np.float64))
+            if r.dtype != torch.float64 or tuple(r.shape) != (self.n,):
+                raise ValueError('FeatureSet: class radii of k = %s are not fp64 [%d]' % (k, self.n))
+            self._class_radii[int(k)] = r.contiguous()
+        if class_kernel_totals is not None:
+            t = class_kernel_totals
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
+            if t.dtype != torch.float64 or tuple(t.shape) != (self.classes,):
+                raise ValueError('FeatureSet: class kernel totals are not fp64 [%d]' % self.classes)
+            self._class_kernel_totals = t.contiguous()
 
     @property
     def n(self):
@@ -293,12 +335,61 @@ class FeatureSet:
             self._kernel_tiles = self._kernel_tiles.to(dev)
         return self._kernel_tiles
 
+    def _need_labels(self, what):
+        if self.labels is None:
+            raise ValueError('FeatureSet.%s: the set has no labels' % what)
+
+    def by_class(self):
+        """-> (the features sorted by class fp32 [n, D], perm int64 [n], seg int32 [classes + 1]) on the device, made once: sorted =
+        features[perm], the stable sort by label (kernels.class_segments), class c its rows [seg[c], seg[c + 1]), the rows of no class
+        behind seg[classes].  Torch alone; no count comes to the host."""
+        self._need_labels('by_class')
+        if self._by_class is None:
+            f = self.device_features()
+            perm, seg = K.class_segments(self.labels.to(f.device), self.classes)
+            self._by_class = (f.index_select(0, perm).contiguous(), perm, seg)
+        return self._by_class
+
+    def class_radii(self, k):
+        """fp64 [n] on the device, in by_class() order: the squared distance of every row to its k-th nearest other row of its own class
+        (kernels.knn_radii_seg, once per k); +inf in a class of fewer than k + 1 rows."""
+        self._need_labels('class_radii')
+        k = int(k)
+        if k < 1 or k > K.KNN_MAX_K:
+            raise ValueError('FeatureSet: k = %d (1 to %d)' % (k, K.KNN_MAX_K))
+        if k not in self._class_radii:
+            f, _, seg = self.by_class()
+            self._class_radii[k] = K.knn_radii_seg(f, seg, k, out=torch.full((self.n,), float('inf'), dtype=torch.float64, device=f.device))
+        dev = lib._dev()
+        if self._class_radii[k].device != dev:
+            self._class_radii[k] = self._class_radii[k].to(dev)
+        return self._class_radii[k]
+
+    def class_kernel_totals(self):
+        """fp64 [classes] on the device: for every class the sum of (f_i . f_j / D + 1)^3 over the pairs i != j of its rows
+        (kernels.kernel_tile_sums_seg of the sorted set against itself, then kernels.segment_sums: one fixed order; once)."""
+        self._need_labels('class_kernel_totals')
+        if self._class_kernel_totals is None:
+            f, _, seg = self.by_class()
+            self._class_kernel_totals = K.segment_sums(*K.kernel_tile_sums_seg(f, seg, f, seg, exclude_diag=True))
+        dev = lib._dev()
+        if self._class_kernel_totals.device != dev:
+            self._class_kernel_totals = self._class_kernel_totals.to(dev)
+        return self._class_kernel_totals
+
     def save(self, path):
         """-> `path` (numpy .npz; the name is taken as given): the features, the classifier's hash, every radius computed so far and the
-        kernel tile sums if they have been computed."""
+        kernel tile sums if they have been computed; of a labelled set also the labels, the class count, every class radius computed so
+        far and the class kernel totals if they have been computed."""
         arrays = {'radii_%d' % k: r.cpu().numpy() for k, r in self._radii.items()}
         if self._kernel_tiles is not None:
             arrays['kernel_tiles'] = self._kernel_tiles.cpu().numpy()
+        if self.labels is not None:
+            arrays.update({'class_radii_%d' % k: r.cpu().numpy() for k, r in self._class_radii.items()})
+            arrays.update(labels=self.labels.cpu().numpy(), classes=np.int64(self.classes),
+                          class_radii_k=np.asarray(sorted(self._class_radii), dtype=np.int64))
+            if self._class_kernel_totals is not None:
+                arrays['class_kernel_totals'] = self._class_kernel_totals.cpu().numpy()
         with open(path, 'wb') as f:
             np.savez(f, features=self.features.cpu().numpy(), classifier=np.str_(self.classifier or ''),
                      radii_k=np.asarray(sorted(self._radii), dtype=np.int64), **arrays)
@@ -306,8 +397,13 @@ class FeatureSet:
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
+            kw = {}
+            if 'labels' in z.files:
+                kw = {'labels': z['labels'], 'classes': int(z['classes']),
+                      'class_radii': {int(k): z['class_radii_%d' % k] for k in z['class_radii_k']},
+                      'class_kernel_totals': z['class_kernel_totals'] if 'class_kernel_totals' in z.files else None}
             return cls(z['features'], str(z['classifier']) or None, {int(k): z['radii_%d' % k] for k in z['radii_k']},
-                       z['kernel_tiles'] if 'kernel_tiles' in z.files else None)
+                       z['kernel_tiles'] if 'kernel_tiles' in z.files else None, **kw)
 
 
 def _manifold_counts(samples, reference, k):
@@ -410,6 +506,118 @@ def kernel_distance(samples, reference, subset=None):
     return _kernel_result(host, s)
 
 
+def _class_sums(values, seg):
+    """Per-class sums of an integer-valued [rows] array in class-sorted order -> int64 [K]: differences of one cumsum at the segment
+    starts - exact, whatever the order.  What lies at or behind seg[K] is never counted."""
+    total = torch.zeros(values.numel() + 1, dtype=torch.int64, device=values.device)
+    total[1:] = torch.cumsum(values.to(torch.int64), 0)
+    at = total.index_select(0, seg.to(torch.int64))
+    return at[1:] - at[:-1]
+
+
+def _class_manifold_values(feat, seg, reference, k):
+    """The device half of class_precision_recall -> fp64 [7 K] on the device: per class the samples inside some ball of the class's
+    reference rows, the reference rows inside some ball of the class's samples, the samples at distance 0 from a reference row of
+    their class, the two row counts, and the two middle elements of the class's sorted squared nearest-reference distances (their
+    square roots, and the median, are the host's: a correctly rounded sqrt).
+    feat, seg: the samples' class-sorted features [m, D] and segment starts on the device; four grouped launches, no count on the host."""
+    m, dev = feat.shape[0], feat.device
+    ref, _, rseg = reference.by_class()
+    covered, nn_d2, _ = K.knn_cover_seg(feat, seg, ref, rseg, reference.class_radii(k), torch.zeros(m, dtype=torch.int32, device=dev),
+                                        torch.full((m,), float('inf'), dtype=torch.float64, device=dev))
+    r2 = K.knn_radii_seg(feat, seg, k, out=torch.full((m,), float('inf'), dtype=torch.float64, device=dev))
+    back, _, _ = K.knn_cover_seg(ref, rseg, feat, seg, r2, torch.zeros(ref.shape[0], dtype=torch.int32, device=dev))
+    seg64, rseg64 = seg.to(torch.int64), rseg.to(torch.int64)
+    cnt, rcnt = seg64[1:] - seg64[:-1], rseg64[1:] - rseg64[:-1]
+    # the class's distances in ascending order at its own rows: sort by value, then stably by class (the rows of no class hold +inf, last)
+    cls = torch.searchsorted(seg64[1:].contiguous(), torch.arange(m, dtype=torch.int64, device=dev), right=True)
+    by_value = torch.argsort(nn_d2)
+    ordered = nn_d2.index_select(0, by_value).index_select(0, torch.argsort(cls.index_select(0, by_value), stable=True))
+    lo = (seg64[:-1] + (cnt - 1).clamp(min=0) // 2).clamp(max=m - 1)
+    hi = (seg64[:-1] + cnt // 2).clamp(max=m - 1)
+    mid = torch.cat([ordered.index_select(0, lo), ordered.index_select(0, hi)])
+    counts = torch.cat([_class_sums(covered, seg), _class_sums(back, rseg), _class_sums(nn_d2 == 0, seg), cnt, rcnt])
+    return torch.cat([counts.to(torch.float64), mid])
+
+
+def _nanmean(values):
+    return float(np.nanmean(values)) if not np.isnan(values).all() else float('nan')
+
+
+def _class_manifold_result(host, classes, k):
+    nc = classes
+    cov, back, zero, n, nref = (host[i * nc:(i + 1) * nc].astype(np.int64) for i in range(5))
+    lo, hi = host[5 * nc:6 * nc], host[6 * nc:7 * nc]
+    nan = np.full(nc, np.nan)
+    precision = np.where((n > 0) & (nref >= k + 1), cov / np.maximum(n, 1), nan)
+    recall = np.where((nref > 0) & (n >= k + 1), back / np.maximum(nref, 1), nan)
+    with np.errstate(invalid='ignore'):
+        dist = np.where((n > 0) & (nref > 0), (np.sqrt(lo) + np.sqrt(hi)) / 2, nan)
+    return {'precision_class': precision, 'recall_class': recall, 'nn_dist_class': dist, 'nn_zero_class': np.where(nref > 0, zero, 0),
+            'n_class': n, 'n_class_reference': nref, 'intra_precision': _nanmean(precision), 'intra_recall': _nanmean(recall), 'k': int(k)}
+
+
+def _check_class_sets(samples, reference, what):
+    if samples.labels is None or reference.labels is None:
+        raise ValueError('%s: both feature sets need labels' % what)
+    if samples.width != reference.width:
+        raise ValueError('%s: %d and %d features' % (what, samples.width, reference.width))
+    if samples.classes != reference.classes:
+        raise ValueError('%s: %d and %d classes' % (what, samples.classes, reference.classes))
+    if samples.classifier is not None and reference.classifier is not None and samples.classifier != reference.classifier:
+        raise ValueError('%s: the two feature sets were computed under different classifiers' % what)
+
+
+def class_precision_recall(samples, reference, k=3):
+    """precision_recall per class between two LABELLED FeatureSets, on the device, every class in the same four launches
+    (kernels.knn_cover_seg, kernels.knn_radii_seg): the precision of class c is the share of the samples with label c that lie inside the
+    k-th-neighbour ball of some reference row of class c, the radii taken INSIDE the class; the recall is the mirror image.
+    -> {'precision_class', 'recall_class', 'nn_dist_class' (the per-class median distance to the nearest reference row of the class):
+    fp64 [K], NaN where undefined - precision where the class has no sample or its reference fewer than k + 1 rows, recall where it has
+    no reference row or fewer than k + 1 samples, nn_dist where either side is empty; 'nn_zero_class' int [K]; 'n_class',
+    'n_class_reference' int [K]; 'intra_precision', 'intra_recall': the means over the classes that are not NaN (NaN when none is);
+    'k'}.  One device -> host copy.  Unlabelled sets, different widths, class counts or recorded classifiers raise."""
+    k = int(k)
+    _check_class_sets(samples, reference, 'class_precision_recall')
+    if k < 1 or k > K.KNN_MAX_K:
+        raise ValueError('class_precision_recall: k = %d (1 to %d)' % (k, K.KNN_MAX_K))
+    feat, _, seg = samples.by_class()
+    host = _class_manifold_values(feat, seg, reference, k).cpu().numpy()
+    return _class_manifold_result(host, samples.classes, k)
+
+
+def _class_kernel_values(feat, seg, own, reference):
+    """The device half of class_kernel_distance -> fp64 [5 K] on the device: per class Sxx (own: the samples' own totals), Syy, Sxy and
+    the two row counts.  One grouped launch and one segment_sums here; the two sets' own totals once per set."""
+    ref, _, rseg = reference.by_class()
+    xy = K.segment_sums(*K.kernel_tile_sums_seg(feat, seg, ref, rseg))
+    seg64, rseg64 = seg.to(torch.int64), rseg.to(torch.int64)
+    return torch.cat([own, reference.class_kernel_totals(), xy, (seg64[1:] - seg64[:-1]).to(torch.float64),
+                      (rseg64[1:] - rseg64[:-1]).to(torch.float64)])
+
+
+def _class_kernel_result(host, classes):
+    nc = classes
+    xx, yy, xy = host[:nc], host[nc:2 * nc], host[2 * nc:3 * nc]
+    m, n = host[3 * nc:4 * nc], host[4 * nc:5 * nc]
+    ok = (m >= 2) & (n >= 2)
+    ms, ns = np.where(ok, m, 2.0), np.where(ok, n, 2.0)
+    kid = np.where(ok, xx / (ms * (ms - 1.0)) + yy / (ns * (ns - 1.0)) - 2.0 * xy / (ms * ns), np.nan)
+    return {'kid_class': kid, 'intra_kid': _nanmean(kid), 'n_class': m.astype(np.int64), 'n_class_reference': n.astype(np.int64)}
+
+
+def class_kernel_distance(samples, reference):
+    """kernel_distance per class between two LABELLED FeatureSets, on the device, every class in the same launch
+    (kernels.kernel_tile_sums_seg, then kernels.segment_sums: the per-class totals in one fixed order):
+    -> {'kid_class' fp64 [K]: Sxx_c / (m_c (m_c - 1)) + Syy_c / (n_c (n_c - 1)) - 2 Sxy_c / (m_c n_c) over the rows of class c, NaN
+    with fewer than 2 rows on a side; 'intra_kid': its mean over the classes that are not NaN; 'n_class', 'n_class_reference'}.  One
+    device -> host copy.  Unlabelled sets, different widths, class counts or recorded classifiers raise."""
+    _check_class_sets(samples, reference, 'class_kernel_distance')
+    feat, _, seg = samples.by_class()
+    host = _class_kernel_values(feat, seg, samples.class_kernel_totals(), reference).cpu().numpy()
+    return _class_kernel_result(host, samples.classes)
+
+
 def _avg_kw(averaged):
     """Keyword of Evaluator.score_draws for samples of the generator's weight average (nothing is passed for the live generator: the
     call is then the one it always was)."""
@@ -439,10 +647,14 @@ class ClassifierScore:
     (of a conditional generator) then also return `'frechet_class'`, `'intra_frechet'`, `'n_class'`, `'confusion'` and `'acc_class'`.
     kernel_reference: a FeatureSet, or the path of a saved one (see set_kernel_reference), kernel_subset: the block size of the error
     bar (None: kernel_subset's rule): `score` and `score_generator` then also return `'kid'`, `'kid_std'` and `'kid_blocks'`
-    (kernel_distance)."""
+    (kernel_distance).
+    class_manifold: a LABELLED FeatureSet, or the path of a saved one (see set_class_manifold), class_manifold_k: the neighbour count;
+    class_kernel_reference: a labelled FeatureSet, or the path of a saved one (see set_class_kernel_reference): `score` (with labels) and
+    `score_generator` (of a conditional generator) then also return the keys of class_precision_recall / class_kernel_distance."""
 
     def __init__(self, trainer=None, weights=None, data_dir=None, epochs=None, te=False, reference=None, manifold=None, manifold_k=3,
-                 class_reference=None, kernel_reference=None, kernel_subset=None, **train_kw):
+                 class_reference=None, kernel_reference=None, kernel_subset=None, class_manifold=None, class_manifold_k=3,
+                 class_kernel_reference=None, **train_kw):
         if (trainer is None) == (weights is None):
             raise ValueError('ClassifierScore: pass a trainer or weights=PATH')
         self.trainer = trainer
@@ -470,6 +682,9 @@ class ClassifierScore:
         if class_reference is not None:
             self.set_class_reference(class_reference)
         self.set_kernel_reference(kernel_reference, kernel_subset)
+        self.class_manifold, self.class_manifold_k = None, int(class_manifold_k)
+        self.set_class_manifold(class_manifold, class_manifold_k)
+        self.set_class_kernel_reference(class_kernel_reference)
 
     # ---- construction
     @staticmethod
@@ -623,6 +838,45 @@ class ClassifierScore:
                 raise ValueError('ClassifierScore: a kernel reference of %d rows (at least 2)' % ref.n)
         self.kernel_reference, self.kernel_subset = ref, None if subset is None else int(subset)
 
+    # ---- the labelled sets of the per-class precision, recall and kernel distance
+    def _check_class_set(self, ref, what):
+        if ref.labels is None:
+            raise ValueError('ClassifierScore: the %s features have no labels' % what)
+        if ref.classifier is None:
+            raise ValueError('ClassifierScore: the %s features do not record the classifier they were computed under' % what)
+        if ref.classifier != self.fingerprint():
+            raise ValueError('ClassifierScore: the %s features were computed under another classifier (%s..., this one is %s...)'
+                             % (what, ref.classifier[:12], self.fingerprint()[:12]))
+        if ref.width != self.cfg.D_WIDTHS[-1]:
+            raise ValueError('ClassifierScore: %d %s features, %d in the classifier' % (ref.width, what, self.cfg.D_WIDTHS[-1]))
+        if ref.classes != self.cfg.N_CLASSES:
+            raise ValueError('ClassifierScore: %d %s classes, %d in the classifier' % (ref.classes, what, self.cfg.N_CLASSES))
+
+    def set_class_manifold(self, features_or_path, k=None):
+        """The LABELLED FeatureSet (or the path of a saved one; None: none) that `score` / `score_generator` measure the per-class precision
+        and recall against (class_precision_recall), with `k` neighbours (None: as it is).  It must have been computed under this
+        classifier's averaged parameters, at its width and class count - checked here and again at every scoring."""
+        ref = features_or_path
+        if ref is not None and not isinstance(ref, FeatureSet):
+            ref = FeatureSet.load(ref)
+        k = self.class_manifold_k if k is None else int(k)
+        if k < 1 or k > K.KNN_MAX_K:
+            raise ValueError('ClassifierScore: class_manifold_k = %d (1 to %d)' % (k, K.KNN_MAX_K))
+        if ref is not None:
+            self._check_class_set(ref, 'class manifold')
+        self.class_manifold, self.class_manifold_k = ref, k
+
+    def set_class_kernel_reference(self, features_or_path):
+        """The LABELLED FeatureSet (or the path of a saved one; None: none) that `score` / `score_generator` measure the per-class kernel
+        distance to (class_kernel_distance), under the checks of set_class_manifold.  Its own per-class totals are computed at the first
+        scoring unless it carries them (FeatureSet.class_kernel_totals, saved with it)."""
+        ref = features_or_path
+        if ref is not None and not isinstance(ref, FeatureSet):
+            ref = FeatureSet.load(ref)
+        if ref is not None:
+            self._check_class_set(ref, 'class kernel reference')
+        self.class_kernel_reference = ref
+
     # ---- samples in internal form -> logits
     def _forward(self, x, features=False):
         """-> logits [m, K]; features: (logits, the pooled features [m, D]) of the same pass."""
@@ -685,7 +939,7 @@ class ClassifierScore:
         d = self.cfg.D_WIDTHS[-1]
         return FeatureStatistics.from_moments(n, host[:d], host[d:].reshape(d, d), self.fingerprint())
 
-    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None, cls=None, ker=None):
+    def _finish(self, acc, cnt, n, splits, with_labels, moments=None, man=None, cls=None, ker=None, cset=None):
         nc = self.cfg.N_CLASSES
         out = K.score_finish(acc, n, splits)
         parts = [out, cnt.to(torch.float64)] + ([] if moments is None else [moments])
@@ -698,7 +952,26 @@ class ClassifierScore:
             tail = parts[-1].numel()
         if man is not None:                                  # three launches over all n samples, once, after the last chunk
             parts.append(_manifold_counts(man['feat'], self.manifold, self.manifold_k))
+        if cset is not None:                                 # the grouped launches over all n samples, once, after the last chunk
+            perm, seg = K.class_segments(cset['lab'], nc)
+            feat = cset['feat'].index_select(0, perm)
+            if self.class_manifold is not None:
+                parts.append(_class_manifold_values(feat, seg, self.class_manifold, self.class_manifold_k))
+            if self.class_kernel_reference is not None:
+                own = K.segment_sums(*K.kernel_tile_sums_seg(feat, seg, feat, seg, exclude_diag=True))
+                parts.append(_class_kernel_values(feat, seg, own, self.class_kernel_reference))
         host = torch.cat(parts).cpu().numpy()                # the scoring's one device -> host copy (counts < 2^53: exact)
+        extra = {}
+        if cset is not None:
+            if self.class_kernel_reference is not None:
+                extra.update(_class_kernel_result(host[-5 * nc:], nc))
+                host = host[:-5 * nc]
+            if self.class_manifold is not None:
+                extra.update(_class_manifold_result(host[-7 * nc:], nc, self.class_manifold_k))
+                del extra['k']
+                host = host[:-7 * nc]
+            if int(extra['n_class'].sum()) != n:
+                raise ValueError('ClassifierScore: %d of %d rows have a label in [0, %d)' % (int(extra['n_class'].sum()), n, nc))
         counts = host[2 + splits:2 + splits + 2 * nc].astype(np.int64)
         res = {'mean': float(host[0]), 'std': float(host[1]), 'splits': host[2:2 + splits].copy(), 'hist': counts[:nc].copy(),
                'acc': float(counts[nc:].sum()) / n if with_labels else None}
@@ -720,14 +993,19 @@ class ClassifierScore:
         if ker is not None:
             res.update(_kernel_result(host[-tail:], ker['subset']))
             del res['subset']
+        res.update(extra)
         return res
 
-    def _score_chunk(self, x, mom, man=None, r0=0, cls=None, lab=None, ker=None):
+    def _score_chunk(self, x, mom, man=None, r0=0, cls=None, lab=None, ker=None, cset=None):
         """One classifier pass -> logits; with the moment state of a scoring that has a reference, the pass's features go into it; with
         the state of one that has a manifold, they are copied to rows r0.. of its buffer; with the state of one that has a class reference,
         the features go into the state of their label `lab` and the logits into the confusion matrix; the state of one that has a kernel
-        reference holds the manifold's buffer when there is one: one copy serves both."""
+        reference holds the manifold's buffer when there is one: one copy serves both; the state of one that has a class manifold
+        or a class kernel reference shares that buffer too and keeps the labels."""
         man = ker if man is None else man
+        if cset is not None:
+            cset['lab'][r0:r0 + lab.shape[0]].copy_(lab)
+            man = cset if man is None else man
         if mom is None and man is None and cls is None:
             return self._logits(x)
         logits, feat = self._forward(x, True)
@@ -760,6 +1038,19 @@ class ClassifierScore:
         self._check_kernel_reference(ref)
         feat = man['feat'] if man is not None else torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
         return {'feat': feat, 'subset': kernel_subset(n, ref.n, self.kernel_subset)}
+
+    def _begin_class_sets(self, n, with_labels, what, shared):
+        """The state of a scoring with a class manifold or a class kernel reference: the [n, D] buffer of the chunks' features - the
+        manifold's or the kernel reference's when there is one - and the [n] labels."""
+        if self.class_manifold is None and self.class_kernel_reference is None:
+            return None
+        if not with_labels:
+            raise ValueError('ClassifierScore.%s: a class manifold or class kernel reference is set and the samples have no labels' % what)
+        for ref, name in ((self.class_manifold, 'class manifold'), (self.class_kernel_reference, 'class kernel reference')):
+            if ref is not None:
+                self._check_class_set(ref, name)
+        feat = shared['feat'] if shared is not None else torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
+        return {'feat': feat, 'lab': torch.empty(n, dtype=torch.int32, device=self.dev)}
 
     def _begin_frechet(self, n):
         if self.reference is None:
@@ -795,6 +1086,7 @@ class ClassifierScore:
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
         ker = self._begin_kernel(n, man)
+        cset = self._begin_class_sets(n, labels is not None, 'score', ker if man is None else man)
         data = data.to(self.dev).contiguous()
         labels = self._labels(labels, n)
         chunk = min(DEFAULT_CHUNK, n) if chunk is None else int(chunk)
@@ -804,9 +1096,9 @@ class ClassifierScore:
             m = min(chunk, n - r0)
             idx = torch.arange(r0, r0 + m, dtype=torch.int32, device=self.dev)
             lab = None if labels is None else labels[r0:r0 + m]
-            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0, cls, lab, ker)
+            logits = self._score_chunk(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), mom, man, r0, cls, lab, ker, cset)
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
-        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls, ker)
+        return self._finish(acc, cnt, n, splits, labels is not None, None if mom is None else mom[0], man, cls, ker, cset)
 
     def score_generator(self, gan_trainer, n, labels=None, splits=10, chunk=None, averaged=False):
         """The score of `n` samples of a gan_cifar / gan_cifar_resnet trainer's generator, drawn exactly as evaluate.Evaluator.score_samples
@@ -823,15 +1115,16 @@ class ClassifierScore:
         mom = self._begin_frechet(n)
         man = self._begin_manifold(n)
         ker = self._begin_kernel(n, man)
+        cset = self._begin_class_sets(n, ev.resnet, 'score_generator', ker if man is None else man)
         labels = self._labels(labels, n)
         r0, with_labels = 0, False
         for x, lab in ev.score_draws(n, labels, chunk, **_avg_kw(averaged)):
             lab = None if lab is None else lab.contiguous()
-            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab, ker)
+            logits = self._score_chunk(K.score_input(x, cfg.CHANNELS, scale, self.lut), mom, man, r0, cls, lab, ker, cset)
             K.score_accum(logits, r0, n, splits, acc, cnt, lab)
             with_labels = lab is not None
             r0 += x.shape[0]
-        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man, cls, ker)
+        return self._finish(acc, cnt, n, splits, with_labels, None if mom is None else mom[0], man, cls, ker, cset)
 
     def _evaluator(self, gan_trainer, what):
         from . import evaluate
@@ -914,9 +1207,10 @@ class ClassifierScore:
         return self._class_statistics(st['cnt'].cpu().numpy(), st['mom'].cpu().numpy(), n)
 
     # ---- the features themselves
-    def features(self, images_u8, chunk=None):
+    def features(self, images_u8, chunk=None, labels=None):
         """The FeatureSet of a uint8 set [N, CHANNELS, IMG, IMG], read exactly as `statistics` reads it: what a manifold is made of (the
-        training images, once; `.save(path)` keeps it with its radii)."""
+        training images, once; `.save(path)` keeps it with its radii).  labels [N]: a labelled set of N_CLASSES classes - what a class
+        manifold or a class kernel reference is made of."""
         cfg = self.cfg
         data = torch.as_tensor(images_u8)
         if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (cfg.CHANNELS, cfg.IMG, cfg.IMG):
@@ -933,17 +1227,24 @@ class ClassifierScore:
         for r0 in range(0, n, chunk):
             idx = torch.arange(r0, min(r0 + chunk, n), dtype=torch.int32, device=self.dev)
             out[r0:r0 + chunk].copy_(self._forward(K.aug_gather(data, idx, self.lut, cfg.IMG, cfg.PAD), True)[1])
+        if labels is not None:
+            return FeatureSet(out, self.fingerprint(), labels=self._labels(labels, n), classes=cfg.N_CLASSES)
         return FeatureSet(out, self.fingerprint())
 
     def features_generator(self, gan_trainer, n, labels=None, chunk=None, averaged=False):
         """The FeatureSet of `n` generator samples, drawn and quantised exactly as `statistics_generator` draws them (the evaluation
-        stream; the training stream, the weights and the optimizers stay untouched)."""
+        stream; the training stream, the weights and the optimizers stay untouched).  A conditional generator's samples carry the labels
+        they were generated from: a labelled set."""
         ev, scale = self._evaluator(gan_trainer, 'features_generator')
         if n < 1:
             raise ValueError('ClassifierScore.features_generator: no samples')
         out = torch.empty(n, self.cfg.D_WIDTHS[-1], dtype=torch.float32, device=self.dev)
-        r0 = 0
-        for x, _ in ev.score_draws(n, self._labels(labels, n), chunk, **_avg_kw(averaged)):
+        r0, labs = 0, []
+        for x, lab in ev.score_draws(n, self._labels(labels, n), chunk, **_avg_kw(averaged)):
             out[r0:r0 + x.shape[0]].copy_(self._forward(K.score_input(x, self.cfg.CHANNELS, scale, self.lut), True)[1])
             r0 += x.shape[0]
+            if lab is not None:
+                labs.append(lab.reshape(-1).to(torch.int32))
+        if labs:
+            return FeatureSet(out, self.fingerprint(), labels=torch.cat(labs), classes=self.cfg.N_CLASSES)
         return FeatureSet(out, self.fingerprint())

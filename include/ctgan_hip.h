@@ -949,6 +949,39 @@ int ctgan_knn_cover(const float* a, int64_t m, const float* b, int64_t n, int32_
 int ctgan_kernel_tile(void);
 int ctgan_kernel_tile_sums(const float* a, int64_t m, const float* b, int64_t n, int32_t d, double gamma, double coef0, int32_t exclude_diag,
                            double* sums, ctgan_stream_t stream);
+/* The same three kernels per class of CLASS-SORTED operands, one launch for every class (csrc/knn.hip, csrc/kid.hip), for the per-class
+ * precision, recall and kernel distance of score_cifar.py.  An operand's rows of class 0 come first, then class 1, ..., in their original
+ * order inside a class; seg int32 [classes + 1], device-resident, holds the segment starts: class c is rows [seg[c], seg[c + 1]) and
+ * rows at or behind seg[classes] belong to no class and are never read as operands.  (A kernel clamps what it reads of seg into
+ * [0, rows]: a wrong array gives wrong numbers, never an access outside the operand.)  No count is needed on the host: the grid is
+ * ceil(rows of a / 64) + classes workgroups, each scans seg for its (class, tile of the class's rows of a), and a surplus workgroup
+ * returns at once.  The bodies are the pooled kernels' on the segment's bases and counts, so class c receives the BITS the pooled entry
+ * point leaves from the gathered rows of class c; no atomics, one owner per output element, the same bits on every run.
+ * ctgan_knn_radii_seg: f fp32 [n, d], seg -> r2 fp64 [n] in sorted order: the squared distance of row i to its k-th nearest other row OF
+ * ITS OWN CLASS; +inf for a row whose class has fewer than k + 1 rows (the selection never fills; the caller masks such classes); rows
+ * at or behind seg[classes] are not written.  n == 0: nothing is launched.
+ * ctgan_knn_cover_seg: row i of class c of a [m, d] against the rows of class c of b [n, d] only, r2_b fp64 [n] (sorted order) or NULL ->
+ * covered int32 [m], nn_d2 fp64 [m], nn_idx int32 [m] as ctgan_knn_cover, nn_idx counting from the start of the class's segment of b.
+ * A class with no rows in b: covered 0, nn_d2 +inf, nn_idx -1, and nothing of b or r2_b is read (n == 0 is such a call, b may be NULL).
+ * m == 0: nothing is launched.
+ * ctgan_kernel_tile_sums_seg: class c's tile matrix [ceil(m_c / T), ceil(n_c / T)] of ctgan_kernel_tile_sums is stored row-major at
+ * sums[toff[c] : toff[c + 1]]; toff int64 [classes + 1], device-resident, the caller's exclusive prefix sums of
+ * ceil(m_c / T) ceil(n_c / T); sums holds at least toff[classes] elements ((ceil(m / T) + classes) (ceil(n / T) + 1) always suffices)
+ * and elements no class owns are not written.  exclude_diag != 0 drops i == j by the index INSIDE the class and needs a == b,
+ * seg_a == seg_b, m == n (else CTGAN_E_BADARG).  grid.y is the slab count at the pooled bound ceil(n / T); a workgroup whose slab
+ * starts past its class's tiles returns.
+ * All three: classes outside 1..32 or d > 1024 (radii: k > ctgan_knn_max_k()): CTGAN_E_UNSUPPORTED for the upper limits,
+ * CTGAN_E_BADARG below 1; a null pointer or an fp64 / int64 array that is not 8-byte aligned: CTGAN_E_BADARG; nothing is launched.
+ * ctgan_segment_sums: out[s] = the fp64 sum of vals[off[s] : off[s + 1]], off int64 [segments + 1]: one workgroup per segment, thread
+ * t of 256 adds elements t, t + 256, ... in index order, then an LDS tree - one fixed order that does not depend on the grid: the
+ * same bits on every run.  An empty segment gives 0.  It turns the ragged tile sums into per-class totals (a cumsum difference would
+ * round against the total of all classes).  segments == 0: nothing is launched.                                                   */
+int ctgan_knn_radii_seg(const float* f, const int32_t* seg, int32_t classes, int64_t n, int32_t d, int32_t k, double* r2, ctgan_stream_t stream);
+int ctgan_knn_cover_seg(const float* a, const int32_t* seg_a, int64_t m, const float* b, const int32_t* seg_b, int64_t n, int32_t classes, int32_t d,
+                        const double* r2_b, int32_t* covered, double* nn_d2, int32_t* nn_idx, ctgan_stream_t stream);
+int ctgan_kernel_tile_sums_seg(const float* a, const int32_t* seg_a, int64_t m, const float* b, const int32_t* seg_b, int64_t n, int32_t classes,
+                               int32_t d, double gamma, double coef0, int32_t exclude_diag, const int64_t* toff, double* sums, ctgan_stream_t stream);
+int ctgan_segment_sums(const double* vals, const int64_t* off, int32_t segments, double* out, ctgan_stream_t stream);
 
 /* ---- differentiable augmentation of the critic's inputs (csrc/diffaug.hip; Zhao et al. 2020 - NOT in the reference) --------------
  * The policy `color,translation,cutout` on flat NCHW fp32 images [n, c, h, w], one workgroup per image.  Exactly one of x (fp32) and
