@@ -201,6 +201,15 @@ SIGNATURES = {
     'ctgan_gp_head_grad': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p]),
     'ctgan_gp_finish': (c_int, [_p, _p, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_float, _p, _p]),
     'ctgan_gp_head_wgrad': (c_int, [_p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, c_int, _p]),
+    # projection head: the fused heads with the per-row weight w_out + emb[label]
+    'ctgan_tail_critic_heads_fwd_proj': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, c_int32, _p, _p, _p, c_float, c_float, c_float, _p, _p,
+                                                 _p, _p, _p]),
+    'ctgan_tail_heads_bwd_proj': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, _p, _p, c_int32,
+                                          _p, _p, _p, _p, _p, c_int32, _p, _p]),
+    'ctgan_gen_heads_fwd_proj': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, c_int32, _p, _p, _p, _p, _p]),
+    'ctgan_gen_heads_bwd_proj': (c_int, [_p, _p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, c_int32, _p, _p]),
+    'ctgan_gp_head_grad_proj': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p]),
+    'ctgan_gp_head_wgrad_proj': (c_int, [_p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_int, _p]),
     'ctgan_accuracy2': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
     'ctgan_adam_step': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
     'ctgan_adam_advance': (c_int, [_p, c_float, c_float, _p]),

@@ -130,9 +130,18 @@ def critic_step(tr, R, real_int, labels, fake, early=None, prep=None):
     w_ac = P('Discriminator.ACGANOutput.W') if use_ac else None
     b_ac = P('Discriminator.ACGANOutput.b') if use_ac else None
     y_clean = y[ranges['clean'][0]:ranges['clean'][1]] if use_ac else None
+    # projection head (cfg.PROJECTION, never with the class head): the head below with the per-row weight w_out + emb[labels[i]] - rows
+    # [real, fake, real'] and the penalty row x_hat of sample i share labels[i].  The critic stays piecewise linear in x, so nothing between
+    # the three head launches changes: they take their `_proj` forms, the table's gradient is the sum of the two they return.
+    emb = R.projection_table() if cfg.PROJECTION else None
     # loss heads of the dropout passes; the penalty joins out5[0] / out5[4] when its value exists (phase C's first launch)
-    out5, f_all, d_all, _a, ct_i, probs, acc = K.tail_critic_heads_fwd(y[:3 * B], B, w_out, b_out, w_ac, b_ac, labels, None, cfg.LAMBDA_2, cfg.Factor_M,
-                                                                        cfg.ACGAN_SCALE if use_ac else 0.0, y_clean=y_clean, clean_relu=False)
+    if emb is not None:
+        out5, f_all, d_all, ct_i = K.tail_critic_heads_fwd_proj(y[:3 * B], B, w_out, b_out, emb, labels, None, cfg.LAMBDA_2, cfg.Factor_M)
+        probs = acc = None
+    else:
+        out5, f_all, d_all, _a, ct_i, probs, acc = K.tail_critic_heads_fwd(y[:3 * B], B, w_out, b_out, w_ac, b_ac, labels, None, cfg.LAMBDA_2,
+                                                                            cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, y_clean=y_clean,
+                                                                            clean_relu=False)
 
     # ------------------------------------------------------------------ phase B: one backward chain over [dropout-pass rows ; penalty rows]
     G = _Grads()
@@ -140,9 +149,13 @@ def critic_step(tr, R, real_int, labels, fake, early=None, prep=None):
     g3 = ConvGeom(D, 8, 8, D, 3, 3, 1)
     gy = K.empty_cl(T, D, 8, 8, y.device)
     # both seeds in one launch: the loss heads' gradient on the dropout-pass rows, dD/dz = (y > 0) w_out / hw / keep on the penalty rows
-    _, gw_out, gb_out, gw_ac, gb_ac = K.tail_heads_bwd(y[:3 * B], d_all, f_all, probs, labels, ct_i, one, B, cfg.LAMBDA_2, cfg.Factor_M,
-                                                       cfg.ACGAN_SCALE if use_ac else 0.0, 1.0 / 0.5, w_out, w_ac, out=gy[:3 * B],
-                                                       y_gp=y[3 * B:T], out_gp=gy[3 * B:T])
+    if emb is not None:
+        _, gw_out, gb_out, g_emb = K.tail_heads_bwd_proj(y[:3 * B], d_all, f_all, labels, ct_i, one, B, cfg.LAMBDA_2, cfg.Factor_M, 1.0 / 0.5, w_out,
+                                                         emb, out=gy[:3 * B], y_gp=y[3 * B:T], out_gp=gy[3 * B:T])
+    else:
+        _, gw_out, gb_out, gw_ac, gb_ac = K.tail_heads_bwd(y[:3 * B], d_all, f_all, probs, labels, ct_i, one, B, cfg.LAMBDA_2, cfg.Factor_M,
+                                                           cfg.ACGAN_SCALE if use_ac else 0.0, 1.0 / 0.5, w_out, w_ac, out=gy[:3 * B],
+                                                           y_gp=y[3 * B:T], out_gp=gy[3 * B:T])
 
     def rdrop(i):         # the dropout in front of block 3 (i = 0) / block 4 (i = 1): each range with the mask of its own forward draw
         return {'ranges': [(3 * B, main_specs[i]), (T, gp_specs[i])]}
@@ -227,12 +240,17 @@ def critic_step(tr, R, real_int, labels, fake, early=None, prep=None):
     G.wgrad('Discriminator.4.Conv1', u4, g_a41[3 * B:T], W41, g3, False, False)
     G.wgrad('Discriminator.4.Conv2', u_a41, gy[3 * B:T], W42, g3, False, False)
     # the seed dD/dz = (y > 0) w_out / hw / keep depends on w_out
-    K.gp_head_wgrad(u_gz, y[3 * B:T], 1.0 / 0.5, w_out, add_to=gw_out)
+    if emb is not None:     # ... and on the table, row labels[i] for penalty row i: both adjoints added onto the dropout passes' gradients
+        K.gp_head_wgrad_proj(u_gz, y[3 * B:T], 1.0 / 0.5, w_out, emb, labels, add_to=gw_out, add_to_emb=g_emb)
+    else:
+        K.gp_head_wgrad(u_gz, y[3 * B:T], 1.0 / 0.5, w_out, add_to=gw_out)
 
     by = G.by_name
     by['Discriminator.Output.W'], by['Discriminator.Output.b'] = gw_out, gb_out
     if use_ac:
         by['Discriminator.ACGANOutput.W'], by['Discriminator.ACGANOutput.b'] = gw_ac, gb_ac
+    if emb is not None:
+        by['Discriminator.Projection.W'] = g_emb
     grads = [by.get(n) for n, _ in tr.d_named]
     out = {'cost': out5[0], 'wgan': out5[4], 'acgan': out5[3] if use_ac else None, 'wgan_only': out5[1], 'ct': out5[2], 'gp': gp, 'slopes': slopes,
            'fake': fake, 'real': rf[:B], 'd_real': d_all[:B], 'd_fake': d_all[B:2 * B], 'gp_grads': grads_x}

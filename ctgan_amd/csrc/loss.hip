@@ -341,10 +341,21 @@ __global__ __launch_bounds__(256) void accuracy2_kernel(const float* __restrict_
 //   d[row]   = f . w_out + b_out                    (:181 Linear nf -> 1)
 //   a[row,:] = f . w_ac + b_ac                      (:183 Linear nf -> ncls)
 // replaces [relu +] spatial_sum + two linear launches.  blockDim = 256.
+// PROJ (projection head, ctgan_*_proj): d[row] = f . (w_out + pr.er) + b_out with pr.er = the row's line of the label table E [n_labels,nf],
+// read straight from global memory (nf floats per workgroup).  The projection forms' extra arguments travel in structs that are empty for
+// the plain forms, whose kernels stay the instructions they were.
+template <bool PROJ> struct ProjArgs;                 // the template kernels': table, its row count, its gradient
+template <> struct ProjArgs<false> {};
+template <> struct ProjArgs<true> { const float* __restrict__ emb; int n_labels; float* __restrict__ g_emb; };
+template <bool PROJ> struct ProjRow;                  // head_row's: the row's line of the table
+template <> struct ProjRow<false> {};
+template <> struct ProjRow<true> { const float* er; };
+
+template <bool PROJ>
 __device__ __forceinline__ void head_row(const float* __restrict__ yr, int hw, int nf, int relu, const float* __restrict__ w_out,
                                          const float* __restrict__ b_out, const float* __restrict__ w_ac, const float* __restrict__ b_ac,
                                          int ncls, float* part /*[<=1024]*/, float* fs /*[nf]*/, float* f_row, float* d_row, float* a_row,
-                                         float* d_sh) {
+                                         float* d_sh, ProjRow<PROJ> pr = ProjRow<PROJ>{}) {
     const int tid = threadIdx.x;
     const int nf4 = nf >> 2;
     const int S = 256 / nf4;                          // position slices (nf4 <= 256)
@@ -375,7 +386,10 @@ __device__ __forceinline__ void head_row(const float* __restrict__ yr, int hw, i
         const bool is_d = w_out && o == 0;
         const int k = o - (w_out ? 1 : 0);
         float acc = 0.f;
-        if (is_d) { for (int j = lane; j < nf; j += 64) acc += fs[j] * w_out[j]; }
+        if (is_d) {
+            if constexpr (PROJ) { for (int j = lane; j < nf; j += 64) acc += fs[j] * (w_out[j] + pr.er[j]); }
+            else                { for (int j = lane; j < nf; j += 64) acc += fs[j] * w_out[j]; }
+        }
         else      { for (int j = lane; j < nf; j += 64) acc += fs[j] * w_ac[(long long)j * ncls + k]; }
         acc = wave_sum(acc);
         if (lane == 0) {
@@ -405,16 +419,16 @@ __global__ __launch_bounds__(256) void tail_heads_rows_kernel(const float* __res
     const long long row_elems = (long long)hw * nf;
     if (y2 && r >= n_main) {        // rows of a second tensor that only feed the class head (the clean pass of the accuracies, :249-266)
         const int q = r - n_main;
-        head_row(y2 + q * row_elems, hw, nf, relu2, nullptr, nullptr, w_ac, b_ac, ncls, part, fs0, f2 + (long long)q * nf, nullptr,
-                 a2 + (long long)q * ncls, dsh);
+        head_row<false>(y2 + q * row_elems, hw, nf, relu2, nullptr, nullptr, w_ac, b_ac, ncls, part, fs0, f2 + (long long)q * nf, nullptr,
+                        a2 + (long long)q * ncls, dsh);
         return;
     }
-    head_row(y + r * row_elems, hw, nf, relu, w_out, b_out, w_ac, b_ac, ncls, part, fs0, f + (long long)r * nf, d ? d + r : nullptr,
-             a ? a + (long long)r * ncls : nullptr, dsh);
+    head_row<false>(y + r * row_elems, hw, nf, relu, w_out, b_out, w_ac, b_ac, ncls, part, fs0, f + (long long)r * nf, d ? d + r : nullptr,
+                    a ? a + (long long)r * ncls : nullptr, dsh);
     if (pair_B == 0 || r >= pair_B) return;
     const int r2 = 2 * pair_B + r;
-    head_row(y + r2 * row_elems, hw, nf, relu, w_out, b_out, w_ac, b_ac, ncls, part, fs1, f + (long long)r2 * nf, d ? d + r2 : nullptr,
-             a ? a + (long long)r2 * ncls : nullptr, dsh + 1);
+    head_row<false>(y + r2 * row_elems, hw, nf, relu, w_out, b_out, w_ac, b_ac, ncls, part, fs1, f + (long long)r2 * nf, d ? d + r2 : nullptr,
+                    a ? a + (long long)r2 * ncls : nullptr, dsh + 1);
     float sq = 0.f;
     for (int j = threadIdx.x; j < nf; j += 256) { const float t = fs0[j] - fs1[j]; sq += t * t; }
     sq = block_sum(sq, sh);
@@ -431,6 +445,31 @@ __global__ __launch_bounds__(256) void tail_heads_rows_kernel(const float* __res
             for (int k = 0; k < ncls; ++k) probs[(long long)r * ncls + k] = expf(z[k] - mx - lse);
             ce_i[r] = (mx + lse) - z[labels[r]];                                 // :246-248
         }
+    }
+}
+// The projection head's rows: no class head, no second tensor.  Row r reads the table line of labels[r % pair_B] - the rows [real, fake,
+// real'] of sample i of a critic step share labels[i] - or of labels[r] when pair_B = 0 (one label per row: the generator step).
+__global__ __launch_bounds__(256) void tail_heads_rows_proj_kernel(const float* __restrict__ y, int hw, int nf, const float* __restrict__ w_out,
+                                                                   const float* __restrict__ b_out, const float* __restrict__ emb,
+                                                                   float* __restrict__ f, float* __restrict__ d, int pair_B,
+                                                                   const int32_t* __restrict__ labels, float l2, float* __restrict__ ct_i) {
+    __shared__ __attribute__((aligned(16))) float part[1024];
+    __shared__ float fs0[1024], fs1[1024];
+    __shared__ float dsh[2];
+    __shared__ float sh[4];
+    const int r = blockIdx.x;
+    const long long row_elems = (long long)hw * nf;
+    const ProjRow<true> pr{emb + (long long)labels[pair_B ? r % pair_B : r] * nf};
+    head_row<true>(y + r * row_elems, hw, nf, 0, w_out, b_out, nullptr, nullptr, 0, part, fs0, f + (long long)r * nf, d + r, nullptr, dsh, pr);
+    if (pair_B == 0 || r >= pair_B) return;
+    const int r2 = 2 * pair_B + r;
+    head_row<true>(y + r2 * row_elems, hw, nf, 0, w_out, b_out, nullptr, nullptr, 0, part, fs1, f + (long long)r2 * nf, d + r2, nullptr, dsh + 1, pr);
+    float sq = 0.f;
+    for (int j = threadIdx.x; j < nf; j += 256) { const float t = fs0[j] - fs1[j]; sq += t * t; }
+    sq = block_sum(sq, sh);
+    if (threadIdx.x == 0) {
+        const float t = dsh[0] - dsh[1];
+        ct_i[r] = l2 * t * t + l2 * 0.1f * (sq / (float)nf);                     // :288-290
     }
 }
 // the batch means over those per-sample terms: out[5] as ctgan_critic_heads_fwd
@@ -498,6 +537,10 @@ __device__ __forceinline__ float head_gd(const float* d, const float* ct_i, int 
 //   workgroups [0, 3B): gy[row,hw,j] = y > 0 ? (gf[j] + gd*w_out[j] + sum_k ga[k]*w_ac[j,k]) / hw * mask_scale : 0
 //   workgroups [3B, ..): gw_out[j] = sum_row f[row,j]*gd[row], gb_out = sum gd, gw_ac[j,k] = sum_row f[row,j]*ga[row,k], gb_ac
 // (fixed summation order over rows => deterministic).  blockDim = 256; dynamic shared: max(nf, 3B) floats.
+// PROJ (projection head, no class head): row r and penalty row i use the per-row weight w_out + emb[labels[r % B]] wherever the plain form
+// uses w_out, and n_labels * nf more waves of the weight workgroups write g_emb[c][j] = sum_{r : labels[r % B] = c} f[r][j] * gd[r] -
+// gw_out's scheme (lanes over rows in ascending order, wave_sum, a plain store) under a label mask; a class no row carries gets zeros.
+template <bool PROJ>
 __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __restrict__ y, const float* __restrict__ d,
                                                              const float* __restrict__ f, const float* __restrict__ probs,
                                                              const int32_t* __restrict__ labels, const float* __restrict__ ct_i,
@@ -506,7 +549,8 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
                                                              const float* __restrict__ w_out, const float* __restrict__ w_ac,
                                                              float* __restrict__ gy, float* __restrict__ gw_out, float* __restrict__ gb_out,
                                                              float* __restrict__ gw_ac, float* __restrict__ gb_ac,
-                                                             const float* __restrict__ y_gp, int n_gp, float* __restrict__ gz_gp) {
+                                                             const float* __restrict__ y_gp, int n_gp, float* __restrict__ gz_gp,
+                                                             ProjArgs<PROJ> pa) {
     extern __shared__ float sm[];
     const int tid = threadIdx.x;
     const HeadCoef c = head_coef(gout, n_gout, B, scale);
@@ -516,10 +560,16 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
         const long long base = (long long)((int)blockIdx.x - 3 * B) * hw * nf;
         const int n4 = (hw * nf) >> 2;
         const float sc = mask_scale / (float)hw;
+        const float* er = nullptr;
+        if constexpr (PROJ) er = pa.emb + (long long)labels[((int)blockIdx.x - 3 * B) % B] * nf;
         for (int q = tid; q < n4; q += 256) {
             const int j = (q * 4) % nf;
             const float4 yv = *reinterpret_cast<const float4*>(y_gp + base + (long long)q * 4);
-            const float4 wv = *reinterpret_cast<const float4*>(w_out + j);
+            float4 wv = *reinterpret_cast<const float4*>(w_out + j);
+            if constexpr (PROJ) {
+                // (four 4-byte loads: the table is a view into the optimizer's flat bucket, behind a one-element bias - not 16-byte aligned)
+                wv.x += er[j]; wv.y += er[j + 1]; wv.z += er[j + 2]; wv.w += er[j + 3];
+            }
             float4 o;
             o.x = yv.x > 0.f ? wv.x * sc : 0.f; o.y = yv.y > 0.f ? wv.y * sc : 0.f;
             o.z = yv.z > 0.f ? wv.z * sc : 0.f; o.w = yv.w > 0.f ? wv.w * sc : 0.f;
@@ -531,6 +581,8 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
         const int row = blockIdx.x;
         const float gd = head_gd(d, ct_i, row, B, l2, M, c);
         float* t = sm;                                   // [nf]
+        const float* er = nullptr;
+        if constexpr (PROJ) er = pa.emb + (long long)labels[row % B] * nf;
         for (int j = tid; j < nf; j += 256) {
             float v = 0.f;
             if (row < B || row >= 2 * B) {
@@ -539,7 +591,8 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
                 v = on * l2 * 0.1f * 2.f * (f[(long long)i * nf + j] - f[(long long)(2 * B + i) * nf + j]) / (float)nf;
                 if (row >= 2 * B) v = -v;
             }
-            v += gd * w_out[j];
+            if constexpr (PROJ) v += gd * (w_out[j] + er[j]);
+            else v += gd * w_out[j];
             if (w_ac && row < B) {
                 const int lab = labels[row];
                 for (int k = 0; k < ncls; ++k)
@@ -567,6 +620,19 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
     const int n_w = nf * (1 + nac), n_all = n_w + 1 + nac;
     const int lane = tid & 63;
     const int idx = ((int)blockIdx.x - 3 * B - n_gp) * 4 + (tid >> 6);   // one wave per output, lanes over rows (fixed order)
+    if constexpr (PROJ) {
+        if (idx >= n_all) {                              // g_emb[cls][j]: gw_out[j]'s sum over the rows of class cls
+            const int q = idx - n_all;
+            if (q >= pa.n_labels * nf) return;
+            const int cls = q / nf, j = q - cls * nf;
+            float acc = 0.f;
+            for (int r = lane; r < 3 * B; r += 64)
+                if (labels[r % B] == cls) acc += f[(long long)r * nf + j] * gds[r];
+            acc = wave_sum(acc);
+            if (lane == 0) pa.g_emb[q] = acc;
+            return;
+        }
+    }
     if (idx >= n_all) return;
     float acc = 0.f;
     if (idx < nf) {
@@ -615,16 +681,22 @@ __global__ __launch_bounds__(256) void gen_heads_loss_kernel(const float* __rest
 }
 // backward, one workgroup per sample: gradient w.r.t. the last conv's result through both Linear layers, the spatial mean and
 // the relu/dropout mask:  gy[row,hw,j] = y > 0 ? gout * (-w_out[j] + scale * sum_k (p_k - 1[k = label]) w_ac[j,k]) / n / hw * mask_scale : 0
+// PROJ (projection head, no class head): the per-row weight w_out + emb[labels[row]] in place of w_out
+template <bool PROJ>
 __global__ __launch_bounds__(256) void gen_heads_bwd_kernel(const float* __restrict__ y, const float* __restrict__ probs,
                                                             const int32_t* __restrict__ labels, const float* __restrict__ gout, int n,
                                                             int hw, int nf, int ncls, float scale, float mask_scale,
                                                             const float* __restrict__ w_out, const float* __restrict__ w_ac,
-                                                            float* __restrict__ gy) {
+                                                            float* __restrict__ gy, ProjArgs<PROJ> pa) {
     extern __shared__ float sm[];                          // t [nf]
     const int row = blockIdx.x, tid = threadIdx.x;
     const float g0 = gout[0] / (float)n;
+    const float* er = nullptr;
+    if constexpr (PROJ) er = pa.emb + (long long)labels[row] * nf;
     for (int j = tid; j < nf; j += 256) {
-        float v = -g0 * w_out[j];
+        float v;
+        if constexpr (PROJ) v = -g0 * (w_out[j] + er[j]);
+        else v = -g0 * w_out[j];
         if (w_ac) {
             const int lab = labels[row];
             for (int k = 0; k < ncls; ++k)
@@ -647,17 +719,32 @@ __global__ __launch_bounds__(256) void gen_heads_bwd_kernel(const float* __restr
 
 // Gradient-penalty branch: dD/dy of D = mean_hw(y) . w_out for the last block's output y = relu(dropout(z)), taken w.r.t. z:
 //   gz[row,hw,j] = y > 0 ? w_out[j] / hw * mask_scale : 0      (the value D(x_hat) itself is never needed, :284)
-__global__ void gp_head_grad_kernel(const float* __restrict__ y, const float* __restrict__ w_out, long long n4, int nf, float s,
-                                    float* __restrict__ gz) {
+// PROJ: w_out[j] + emb[labels[row]][j] in place of w_out[j] (row_n4 = hw * nf / 4 float4s per row)
+template <bool PROJ>
+__device__ __forceinline__ void gp_head_grad_body(const float* __restrict__ y, const float* __restrict__ w_out, long long n4, int nf, float s,
+                                                  float* __restrict__ gz, const float* __restrict__ emb, const int32_t* __restrict__ labels,
+                                                  int row_n4) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n4) return;
     const int j = (int)((q * 4) % nf);
     const float4 yv = *reinterpret_cast<const float4*>(y + q * 4);
-    const float4 wv = *reinterpret_cast<const float4*>(w_out + j);
+    float4 wv = *reinterpret_cast<const float4*>(w_out + j);
+    if constexpr (PROJ) {
+        const float* er = emb + (long long)labels[q / row_n4] * nf + j;      // 4-byte loads: the table need not be 16-byte aligned
+        wv.x += er[0]; wv.y += er[1]; wv.z += er[2]; wv.w += er[3];
+    }
     float4 o;
     o.x = yv.x > 0.f ? wv.x * s : 0.f; o.y = yv.y > 0.f ? wv.y * s : 0.f;
     o.z = yv.z > 0.f ? wv.z * s : 0.f; o.w = yv.w > 0.f ? wv.w * s : 0.f;
     *reinterpret_cast<float4*>(gz + q * 4) = o;
+}
+__global__ void gp_head_grad_kernel(const float* __restrict__ y, const float* __restrict__ w_out, long long n4, int nf, float s,
+                                    float* __restrict__ gz) {
+    gp_head_grad_body<false>(y, w_out, n4, nf, s, gz, nullptr, nullptr, 0);
+}
+__global__ void gp_head_grad_proj_kernel(const float* __restrict__ y, const float* __restrict__ w_out, const float* __restrict__ emb,
+                                         const int32_t* __restrict__ labels, long long n4, int row_n4, int nf, float s, float* __restrict__ gz) {
+    gp_head_grad_body<true>(y, w_out, n4, nf, s, gz, emb, labels, row_n4);
 }
 // its adjoint w.r.t. w_out (the double backward): gw[j] = s * sum_{row,hw : y > 0} gg[row,hw,j].  Two fixed-order stages:
 // GPW_SLICES workgroups each reduce a contiguous slice of the (row, hw) axis with coalesced 16-B loads over all channels,
@@ -700,6 +787,56 @@ __global__ __launch_bounds__(256) void gp_head_wgrad_stage2_kernel(const float* 
         for (int u = 0; u < 8; ++u) acc += v[u];
     }
     gw[j] = accumulate ? gw[j] + acc * s : acc * s;
+}
+// The same adjoint for the projection head, whose seed reads w_out + emb[labels[row]]: gw[j] as above and g_emb[c][j] = the same sum over
+// the rows of label c.  The 64 slices above straddle rows, so the first stage is per ROW here: one workgroup per row, head_row's slicing
+// (nf/4 channel lanes x 256 / (nf/4) position slices: any nf % 4 == 0 up to 1024), part[row][nf]; the second stage sums part over the rows in
+// ascending order, unmasked for gw (blockIdx.y = 0) and under the label mask for g_emb[c] (blockIdx.y = 1 + c).  No atomics; a class no row
+// carries gets zeros (or, accumulating, keeps its value).  With 64 rows of hw positions the order of every addition is the plain form's.
+__global__ __launch_bounds__(256) void gp_head_wgrad_rows_kernel(const float* __restrict__ gg, const float* __restrict__ y, int hw, int nf,
+                                                                 float* __restrict__ part /*[n][nf]*/) {
+    __shared__ __attribute__((aligned(16))) float red[1024];
+    const int tid = threadIdx.x;
+    const int nf4 = nf >> 2;
+    const int S = 256 / nf4;
+    const int s = tid / nf4, j4 = tid - s * nf4;
+    const long long base = (long long)blockIdx.x * hw * nf;
+    if (s < S) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+        for (int p = s; p < hw; p += S) {
+            const float4 g = *reinterpret_cast<const float4*>(gg + base + (long long)p * nf + j4 * 4);
+            const float4 yv = *reinterpret_cast<const float4*>(y + base + (long long)p * nf + j4 * 4);
+            acc.x += yv.x > 0.f ? g.x : 0.f; acc.y += yv.y > 0.f ? g.y : 0.f;
+            acc.z += yv.z > 0.f ? g.z : 0.f; acc.w += yv.w > 0.f ? g.w : 0.f;
+        }
+        *reinterpret_cast<float4*>(red + s * nf + j4 * 4) = acc;
+    }
+    __syncthreads();
+    for (int j = tid; j < nf; j += 256) {
+        float acc = red[j];
+        for (int q = 1; q < S; ++q) acc += red[q * nf + j];
+        part[(long long)blockIdx.x * nf + j] = acc;
+    }
+}
+__global__ __launch_bounds__(256) void gp_head_wgrad_proj_stage2_kernel(const float* __restrict__ part, const int32_t* __restrict__ labels, int n,
+                                                                        int nf, float s, float* __restrict__ gw, float* __restrict__ g_emb,
+                                                                        int accumulate) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= nf) return;
+    const int cls = (int)blockIdx.y - 1;                          // -1: gw (every row)
+    float acc = 0.f;
+    int r = 0;
+    for (; r + 8 <= n; r += 8) {                                  // 8 independent loads in flight, fixed summation order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = (cls < 0 || labels[r + u] == cls) ? part[(long long)(r + u) * nf + j] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += v[u];
+    }
+    for (; r < n; ++r) acc += (cls < 0 || labels[r] == cls) ? part[(long long)r * nf + j] : 0.f;
+    float* o = cls < 0 ? gw + j : g_emb + (long long)cls * nf + j;
+    o[0] = accumulate ? o[0] + acc * s : acc * s;
 }
 
 // End of the penalty's first backward (hand-scheduled critic step): dD/dx_hat = ga + scale * upsample2(gs) - the gradient through the first
@@ -853,9 +990,9 @@ int ctgan_tail_heads_bwd(const float* y, const float* d, const float* f, const f
     const int nac = w_ac ? ncls : 0;
     const int wblocks = (nf * (1 + nac) + 1 + nac + 3) / 4;               // one wave per output
     const size_t sh = (size_t)(nf > 3 * B ? nf : 3 * B) * sizeof(float);
-    hipLaunchKernelGGL(tail_heads_bwd_kernel, dim3(3 * B + n_gp + wblocks), dim3(256), sh, static_cast<hipStream_t>(s), y, d, f, probs, labels, ct_i,
+    hipLaunchKernelGGL(tail_heads_bwd_kernel<false>, dim3(3 * B + n_gp + wblocks), dim3(256), sh, static_cast<hipStream_t>(s), y, d, f, probs, labels, ct_i,
                        gout, n_gout, B, hw, nf, ncls, lambda2, M, acgan_scale, mask_scale, w_out, w_ac, gy, gw_out, gb_out, gw_ac, gb_ac,
-                       y_gp, n_gp, gz_gp);
+                       y_gp, n_gp, gz_gp, ProjArgs<false>{});
     return ctgan_check_launch("tail_heads_bwd");
 }
 int ctgan_gen_heads_fwd(const float* y, int32_t n, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* w_ac,
@@ -878,8 +1015,8 @@ int ctgan_gen_heads_bwd(const float* y, const float* probs, const int32_t* label
     if (!y || !gout || !w_out || !gy || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || (w_ac && (!probs || !labels || ncls <= 0)) ||
         ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gy)) & 15))
         return ctgan_fail(CTGAN_E_BADARG, "gen_heads_bwd: bad argument");
-    hipLaunchKernelGGL(gen_heads_bwd_kernel, dim3(n), dim3(256), (size_t)nf * sizeof(float), static_cast<hipStream_t>(s), y, probs, labels, gout,
-                       n, hw, nf, ncls, ac_scale, mask_scale, w_out, w_ac, gy);
+    hipLaunchKernelGGL(gen_heads_bwd_kernel<false>, dim3(n), dim3(256), (size_t)nf * sizeof(float), static_cast<hipStream_t>(s), y, probs, labels, gout,
+                       n, hw, nf, ncls, ac_scale, mask_scale, w_out, w_ac, gy, ProjArgs<false>{});
     return ctgan_check_launch("gen_heads_bwd");
 }
 int ctgan_gp_head_grad(const float* y, const float* w_out, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gz,
@@ -908,6 +1045,92 @@ int ctgan_gp_head_wgrad(const float* gg, const float* y, int32_t n, int32_t hw, 
     if (rc) return rc;
     hipLaunchKernelGGL(gp_head_wgrad_stage2_kernel, dim3((nf + 255) / 256), dim3(256), 0, st, ws, nf, mask_scale / (float)hw, gw, accumulate ? 1 : 0);
     return ctgan_check_launch("gp_head_wgrad_stage2");
+}
+
+// ---- projection head (ctgan_hip.h): the entry points above with the per-row weight w_out + emb[label]; no class head, no clean rows
+int ctgan_tail_critic_heads_fwd_proj(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
+                                     int32_t n_labels, const int32_t* labels, float* gp, const float* slopes, float gp_lambda, float lambda2,
+                                     float M, float* f, float* d, float* ct_i, float* out, ctgan_stream_t s) {
+    if (!y || !f || !d || !w_out || !emb || !labels || !ct_i || !out || B <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 || n_labels <= 0 ||
+        (reinterpret_cast<uintptr_t>(y) & 15))
+        return ctgan_fail(CTGAN_E_BADARG, "tail_critic_heads_fwd_proj: bad argument");
+    if (slopes && !gp) return ctgan_fail(CTGAN_E_BADARG, "tail_critic_heads_fwd_proj: slopes without a gp slot");
+    hipStream_t st = static_cast<hipStream_t>(s);
+    hipLaunchKernelGGL(tail_heads_rows_proj_kernel, dim3(2 * B), dim3(256), 0, st, y, hw, nf, w_out, b_out, emb, f, d, B, labels, lambda2, ct_i);
+    int rc = ctgan_check_launch("tail_heads_rows_proj");
+    if (rc) return rc;
+    hipLaunchKernelGGL(critic_heads_final_kernel, dim3(1), dim3(256), 0, st, d, ct_i, (const float*)nullptr, gp, B, M, 0.f, out, slopes, gp_lambda,
+                       (const float*)nullptr, labels, 0, (float*)nullptr);
+    return ctgan_check_launch("critic_heads_final");
+}
+int ctgan_tail_heads_bwd_proj(const float* y, const float* d, const float* f, const int32_t* labels, const float* ct_i, const float* gout,
+                              int32_t n_gout, int32_t B, int32_t hw, int32_t nf, float lambda2, float M, float mask_scale, const float* w_out,
+                              const float* emb, int32_t n_labels, float* gy, float* gw_out, float* gb_out, float* g_emb, const float* y_gp,
+                              int32_t n_gp, float* gz_gp, ctgan_stream_t s) {
+    if (!y || !d || !f || !labels || !ct_i || !gout || (n_gout != 1 && n_gout != 4) || !w_out || !emb || !gy || !gw_out || !gb_out || !g_emb ||
+        B <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || n_labels <= 0 || n_gp < 0 || (n_gp > 0 && (!y_gp || !gz_gp)))
+        return ctgan_fail(CTGAN_E_BADARG, "tail_heads_bwd_proj: bad argument");
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(y_gp) | reinterpret_cast<uintptr_t>(gz_gp) |
+         (n_gp > 0 ? reinterpret_cast<uintptr_t>(w_out) : 0)) & 15)
+        return ctgan_fail(CTGAN_E_BADARG, "tail_heads_bwd_proj: unaligned");
+    const long long n_waves = (long long)nf * (1 + n_labels) + 1;         // one wave per output: gw_out, gb_out, g_emb
+    if (3LL * B + n_gp + (n_waves + 3) / 4 > 0x7fffffffLL) return ctgan_fail(CTGAN_E_BADARG, "tail_heads_bwd_proj: too large");
+    const int wblocks = (int)((n_waves + 3) / 4);
+    const size_t sh = (size_t)(nf > 3 * B ? nf : 3 * B) * sizeof(float);
+    const float* nof = nullptr;
+    float* nog = nullptr;
+    hipLaunchKernelGGL(tail_heads_bwd_kernel<true>, dim3(3 * B + n_gp + wblocks), dim3(256), sh, static_cast<hipStream_t>(s), y, d, f, nof, labels, ct_i,
+                       gout, n_gout, B, hw, nf, 0, lambda2, M, 0.f, mask_scale, w_out, nof, gy, gw_out, gb_out, nog, nog, y_gp, n_gp, gz_gp,
+                       ProjArgs<true>{emb, n_labels, g_emb});
+    return ctgan_check_launch("tail_heads_bwd_proj");
+}
+int ctgan_gen_heads_fwd_proj(const float* y, int32_t n, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
+                             int32_t n_labels, const int32_t* labels, float* f, float* d, float* out, ctgan_stream_t s) {
+    if (!y || !f || !d || !w_out || !emb || !labels || !out || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 || n_labels <= 0 ||
+        (reinterpret_cast<uintptr_t>(y) & 15))
+        return ctgan_fail(CTGAN_E_BADARG, "gen_heads_fwd_proj: bad argument");
+    hipStream_t st = static_cast<hipStream_t>(s);
+    hipLaunchKernelGGL(tail_heads_rows_proj_kernel, dim3(n), dim3(256), 0, st, y, hw, nf, w_out, b_out, emb, f, d, 0, labels, 0.f, (float*)nullptr);
+    int rc = ctgan_check_launch("tail_heads_rows_proj");
+    if (rc) return rc;
+    hipLaunchKernelGGL(gen_heads_loss_kernel, dim3(1), dim3(256), 0, st, d, (const float*)nullptr, labels, n, 0, 0.f, (float*)nullptr, out);
+    return ctgan_check_launch("gen_heads_loss");
+}
+int ctgan_gen_heads_bwd_proj(const float* y, const int32_t* labels, const float* gout, int32_t n, int32_t hw, int32_t nf, float mask_scale,
+                             const float* w_out, const float* emb, int32_t n_labels, float* gy, ctgan_stream_t s) {
+    if (!y || !labels || !gout || !w_out || !emb || !gy || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || n_labels <= 0 ||
+        ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gy)) & 15))
+        return ctgan_fail(CTGAN_E_BADARG, "gen_heads_bwd_proj: bad argument");
+    const float* nof = nullptr;
+    hipLaunchKernelGGL(gen_heads_bwd_kernel<true>, dim3(n), dim3(256), (size_t)nf * sizeof(float), static_cast<hipStream_t>(s), y, nof, labels, gout, n,
+                       hw, nf, 0, 0.f, mask_scale, w_out, nof, gy, ProjArgs<true>{emb, n_labels, nullptr});
+    return ctgan_check_launch("gen_heads_bwd_proj");
+}
+int ctgan_gp_head_grad_proj(const float* y, const float* w_out, const float* emb, const int32_t* labels, int32_t n_labels, int32_t n, int32_t hw,
+                            int32_t nf, float mask_scale, float* gz, ctgan_stream_t s) {
+    if (!y || !w_out || !emb || !labels || !gz || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || n_labels <= 0 || (long long)hw * nf / 4 > 0x7fffffffLL)
+        return ctgan_fail(CTGAN_E_BADARG, "gp_head_grad_proj: bad argument");
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gz) | reinterpret_cast<uintptr_t>(w_out)) & 15)
+        return ctgan_fail(CTGAN_E_BADARG, "gp_head_grad_proj: unaligned");
+    const long long n4 = (long long)n * hw * nf / 4;
+    if ((n4 + 255) / 256 > 0x7fffffffLL) return ctgan_fail(CTGAN_E_BADARG, "gp_head_grad_proj: too large");
+    hipLaunchKernelGGL(gp_head_grad_proj_kernel, dim3(ctgan_blocks(n4, 256, 0x7fffffff)), dim3(256), 0, static_cast<hipStream_t>(s), y, w_out, emb,
+                       labels, n4, (int)((long long)hw * nf / 4), nf, mask_scale / (float)hw, gz);
+    return ctgan_check_launch("gp_head_grad_proj");
+}
+int ctgan_gp_head_wgrad_proj(const float* gg, const float* y, const int32_t* labels, int32_t n_labels, int32_t n, int32_t hw, int32_t nf,
+                             float mask_scale, float* gw, float* g_emb, float* ws, int accumulate, ctgan_stream_t s) {
+    if (!gg || !y || !labels || !gw || !g_emb || !ws || n <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 || n_labels <= 0 || n_labels >= 65535)
+        return ctgan_fail(CTGAN_E_BADARG, "gp_head_wgrad_proj: bad argument");
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gg)) & 15)
+        return ctgan_fail(CTGAN_E_BADARG, "gp_head_wgrad_proj: unaligned");
+    hipStream_t st = static_cast<hipStream_t>(s);
+    hipLaunchKernelGGL(gp_head_wgrad_rows_kernel, dim3(n), dim3(256), 0, st, gg, y, hw, nf, ws);
+    int rc = ctgan_check_launch("gp_head_wgrad_rows");
+    if (rc) return rc;
+    hipLaunchKernelGGL(gp_head_wgrad_proj_stage2_kernel, dim3((nf + 255) / 256, 1 + n_labels), dim3(256), 0, st, ws, labels, n, nf,
+                       mask_scale / (float)hw, gw, g_emb, accumulate ? 1 : 0);
+    return ctgan_check_launch("gp_head_wgrad_proj_stage2");
 }
 int ctgan_gp_finish(float* ga, const float* gs, const int64_t* gs_strides, int32_t b, int32_t c, int32_t h, int32_t w, float scale, float* slopes,
                     ctgan_stream_t s) {

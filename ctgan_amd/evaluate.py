@@ -184,8 +184,9 @@ class Evaluator:
         with torch.enable_grad():
             if fuse_heads:        # D(x_hat) itself is never used: the backward starts at the last block with dD/dz (F.gp_head_grad)
                 y_gp = R.DiscriminatorTailBody(R.DiscriminatorTrunk(interp), 0.8, 0.5, 0.5, rng=rng, mask_done=True)
-                with torch.no_grad():
-                    gz = F.gp_head_grad(y_gp, lib.param('Discriminator.Output.W'), 1.0 / 0.5)
+                with torch.no_grad():     # (projection head: x_hat row i of the stacked batches carries labels[i], its own batch's)
+                    emb = R.projection_table() if cfg.PROJECTION else None
+                    gz = F.gp_head_grad(y_gp, lib.param('Discriminator.Output.W'), 1.0 / 0.5, emb=emb, labels=labels if emb is not None else None)
                 (grads,) = torch.autograd.grad(y_gp, interp, grad_outputs=gz, create_graph=False)
             else:
                 u_gp = _cat_masks(rnds, 'u_gp') if rnds is not None else None
@@ -202,14 +203,16 @@ class Evaluator:
                 y = R.DiscriminatorTailBody(h, 0.8, 0.5, 0.5, rng=rng, mask_done=True, cat_extra=n)
                 return F.critic_tail_heads(y, P('Discriminator.Output.W'), P('Discriminator.Output.b'),
                                            P('Discriminator.ACGANOutput.W') if use_ac else None, P('Discriminator.ACGANOutput.b') if use_ac else None,
-                                           labels, n, cfg.LAMBDA_2, cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, 1.0 / 0.5, gp)[0]
+                                           labels, n, cfg.LAMBDA_2, cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, 1.0 / 0.5, gp,
+                                           emb=R.projection_table() if cfg.PROJECTION else None)[0]
             u = None
             if rnds is not None:       # rows: real (pass 1) of all batches, fake (pass 1) of all batches, real (pass 2) of all batches
                 p1r, p1f, p2r = (_cat_masks(rnds, 'u_pass1', slice(0, B)), _cat_masks(rnds, 'u_pass1', slice(B, 2 * B)),
                                  _cat_masks(rnds, 'u_pass2', slice(0, B)))
                 u = [torch.cat([a, b, c], 0) for a, b, c in zip(p1r, p1f, p2r)]
             d_all, f_all, a_all = R.DiscriminatorTail(torch.cat([h, h[:n]], 0), 0.8, 0.5, 0.5, u=u, rng=rng,
-                                                      labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None)
+                                                      labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None,
+                                                      proj_labels=torch.cat([labels, labels, labels], 0) if cfg.PROJECTION else None)
             return F.critic_heads(d_all, f_all, a_all if use_ac else None, labels, n, cfg.LAMBDA_2, cfg.Factor_M,
                                   cfg.ACGAN_SCALE if use_ac else 0.0, gp)[0]
 

@@ -1831,6 +1831,11 @@ class RowsSumByLabelFn(Function):
         return RowsGatherFn.apply(g.contiguous(), labels), None, None
 
 
+def rows_gather(table, labels):
+    """[n_labels, C] table, int32 labels [N] -> its rows [N, C]; differentiable to any order w.r.t. the table (RowsGatherFn)."""
+    return RowsGatherFn.apply(table, labels)
+
+
 def layer_norm(x, scale, offset, eps=1e-5, relu=False, labels=None):
     """Per-sample normalisation over all non-batch axes, then per-channel scale / offset (TF/tflib/ops/layernorm.py);
     relu=True also applies the nonlinearity that follows it in the critics' blocks (fused kernels: same pass).  With `labels`
@@ -2022,9 +2027,47 @@ class CriticTailHeadsFn(Function):
                 (g0.reshape(()) if (ctx.has_gp and g0 is not None) else None), None, None, None, None)
 
 
+class CriticTailHeadsProjFn(Function):
+    """CriticTailHeadsFn with the projection head (NOT in the reference): d = f . (w_out + emb[label]) + b_out, row r of the 3B rows reading
+    labels[r % B]; no class head, no clean rows.  Same launches; the backward also returns the table's gradient.  First-order only."""
+
+    @staticmethod
+    def forward(ctx, y, w_out, b_out, emb, labels, B, lam2, M, mask_scale, gp=None, slopes=None, gp_lambda=0.0):
+        out, f, d, ct_i = K.tail_critic_heads_fwd_proj(y, B, w_out, b_out, emb, labels, gp.reshape(1) if gp is not None else None, lam2, M,
+                                                       slopes=slopes, gp_lambda=gp_lambda)
+        ctx.has_gp = gp is not None
+        ctx.cfg = (B, lam2, M, mask_scale)
+        ctx.labels = labels
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(y, w_out, emb, d, f, ct_i)
+        acc = out.new_zeros(0)
+        ctx.mark_non_differentiable(out[4], d, acc)
+        return out[0], out[1], out[2], out[3], out[4], d, acc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, g1, g2, g3, _g4=None, _gd=None, _gacc=None):
+        B, lam2, M, mask_scale = ctx.cfg
+        y, w_out, emb, d, f, ct_i = ctx.saved_tensors
+        if g1 is None and g2 is None and g3 is None:
+            gout = g0.reshape(1).contiguous()
+        else:
+            z = lambda g: g.reshape(1) if g is not None else d.new_zeros(1)
+            gout = torch.cat([z(g0), z(g1), z(g2), z(g3)])
+        gy, gw_out, gb_out, g_emb = K.tail_heads_bwd_proj(y, d, f, ctx.labels, ct_i, gout, B, lam2, M, mask_scale, w_out, emb)
+        return (gy, gw_out, gb_out, g_emb, None, None, None, None, None,
+                (g0.reshape(()) if (ctx.has_gp and g0 is not None) else None), None, None)
+
+
 def critic_tail_heads(y, w_out, b_out, w_ac, b_ac, labels, B, lam2=2.0, M=0.0, acgan_scale=1.0, mask_scale=1.0, gp=None, slopes=None,
-                      gp_lambda=0.0, y_clean=None, clean_relu=False):
-    """-> (cost, wgan, ct, acgan, wgan + ct + gp, d [3B], acc [2] (empty without y_clean)); see CriticTailHeadsFn."""
+                      gp_lambda=0.0, y_clean=None, clean_relu=False, emb=None):
+    """-> (cost, wgan, ct, acgan, wgan + ct + gp, d [3B], acc [2] (empty without y_clean)); see CriticTailHeadsFn.
+    emb [n_labels,nf] (projection head, CriticTailHeadsProjFn): d = f . (w_out + emb[labels]) + b_out; excludes the class head and y_clean."""
+    if emb is not None:
+        if w_ac is not None or b_ac is not None or y_clean is not None:
+            raise ValueError('critic_tail_heads: the projection head has no class head and no clean rows')
+        return CriticTailHeadsProjFn.apply(y, w_out, b_out, emb, labels, int(B), float(lam2), float(M), float(mask_scale), gp, slopes,
+                                           float(gp_lambda))
     return CriticTailHeadsFn.apply(y, w_out, b_out, w_ac, b_ac, labels, int(B), float(lam2), float(M), float(acgan_scale),
                                    float(mask_scale), gp, slopes, float(gp_lambda), y_clean, bool(clean_relu))
 
@@ -2060,8 +2103,35 @@ class GenTailHeadsFn(Function):
         return gy, None, None, None, None, None, None, None
 
 
-def gen_tail_heads(y, w_out, b_out, w_ac, b_ac, labels, ac_scale, mask_scale):
-    """-> (cost, d [n])"""
+class GenTailHeadsProjFn(Function):
+    """GenTailHeadsFn with the projection head (NOT in the reference): cost = -mean(f . (w_out + emb[labels]) + b_out), one label per row."""
+
+    @staticmethod
+    def forward(ctx, y, w_out, b_out, emb, labels, mask_scale):
+        out, d = K.gen_heads_fwd_proj(y, w_out, b_out, emb, labels)
+        ctx.mask_scale = mask_scale
+        ctx.labels = labels
+        ctx.save_for_backward(y, w_out, emb)
+        ctx.mark_non_differentiable(d)
+        ctx.set_materialize_grads(False)
+        return out.reshape(()), d
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, _gd=None):
+        y, w_out, emb = ctx.saved_tensors
+        gy = K.gen_heads_bwd_proj(y, ctx.labels, g0.reshape(1).contiguous(), ctx.mask_scale, w_out, emb)
+        return gy, None, None, None, None, None
+
+
+def gen_tail_heads(y, w_out, b_out, w_ac, b_ac, labels, ac_scale, mask_scale, emb=None):
+    """-> (cost, d [n]).  emb [n_labels,nf]: the projection head (GenTailHeadsProjFn); excludes the class head.  The critic's weights, the
+    table included, get no gradient in the generator step."""
+    if emb is not None:
+        if w_ac is not None or b_ac is not None:
+            raise ValueError('gen_tail_heads: the projection head has no class head')
+        return GenTailHeadsProjFn.apply(y, w_out.detach(), b_out.detach() if b_out is not None else None, emb.detach(), labels,
+                                        float(mask_scale))
     return GenTailHeadsFn.apply(y, w_out.detach(), b_out.detach() if b_out is not None else None,
                                 w_ac.detach() if w_ac is not None else None, b_ac.detach() if b_ac is not None else None, labels,
                                 float(ac_scale), float(mask_scale))
@@ -2087,7 +2157,33 @@ class GpHeadGradFn(Function):
         return None, K.gp_head_wgrad(gg, y, ctx.mask_scale, w_out), None
 
 
-def gp_head_grad(y, w_out, mask_scale):
+class GpHeadGradProjFn(Function):
+    """GpHeadGradFn with the projection head (NOT in the reference): gz = (y > 0) * (w_out + emb[labels[row]]) / hw / keep; the double backward
+    returns both adjoints, (gw_out, g_emb), from ONE gp_head_wgrad_proj."""
+
+    @staticmethod
+    def forward(ctx, y, w_out, mask_scale, emb, labels):
+        ctx.mask_scale = mask_scale
+        ctx.labels = labels
+        ctx.save_for_backward(y, w_out, emb)
+        return K.gp_head_grad_proj(y, w_out, mask_scale, emb, labels)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gg):
+        y, w_out, emb = ctx.saved_tensors
+        if not gg.permute(0, 2, 3, 1).is_contiguous():
+            gg = K.to_channels_last(gg)
+        gw_out, g_emb = K.gp_head_wgrad_proj(gg, y, ctx.mask_scale, w_out, emb, ctx.labels)
+        return None, gw_out, None, g_emb, None
+
+
+def gp_head_grad(y, w_out, mask_scale, emb=None, labels=None):
+    """emb [n_labels,nf] + labels [n] (one per row of y): the projection head's seed (GpHeadGradProjFn)."""
+    if emb is not None:
+        if labels is None:
+            raise ValueError('gp_head_grad: the projection head needs the labels of the rows')
+        return GpHeadGradProjFn.apply(y.detach(), w_out, float(mask_scale), emb, labels)
     return GpHeadGradFn.apply(y.detach(), w_out, float(mask_scale))
 
 

@@ -16,6 +16,7 @@ Exact restructurings relative to the reference graph (same outputs, less work):
 import contextlib
 import functools
 
+import numpy as np
 import torch
 
 from . import functional as F
@@ -51,6 +52,7 @@ class Config:
     ACGAN_SCALE = 1.
     ACGAN_SCALE_G = 0.1
     GP_LAMBDA = 10.0          # the literal 10.0 of :286
+    PROJECTION = False        # NOT in the reference: projection head D(x, y) = f . (w_out + E[y]) + b_out (projection_table)
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -71,8 +73,12 @@ FUSE_RELU = _os.environ.get('CTGAN_FUSE_RELU', '1') != '0'
 
 def configure(**kw):
     global cfg
-    cfg = Config(**kw)
-    if cfg.CONDITIONAL and (not cfg.ACGAN) and (not cfg.NORMALIZATION_D):
+    new = Config(**kw)
+    if new.PROJECTION and not (new.CONDITIONAL and not new.ACGAN):
+        raise ValueError('PROJECTION=True needs CONDITIONAL=True and ACGAN=False (got CONDITIONAL=%r, ACGAN=%r): the projection head is '
+                         'the label path of a conditional critic without the classifier loss' % (new.CONDITIONAL, new.ACGAN))
+    cfg = new
+    if cfg.CONDITIONAL and (not cfg.ACGAN) and (not cfg.NORMALIZATION_D) and (not cfg.PROJECTION):
         print("WARNING! Conditional model without normalization in D might be effectively unconditional!")      # :58-59
     return cfg
 
@@ -320,13 +326,35 @@ def DiscriminatorTailBody(h, kp1, kp2, kp3, u=None, rng=None, mask_done=False, c
     return nonlinearity(out)
 
 
-def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan'), labels=None):
+def projection_table():
+    """`Discriminator.Projection.W` [10, DIM_D] (cfg.PROJECTION; NOT in the reference): the label table E of the projection head (Miyato &
+    Koyama 2018), D(x, y) = f(x) . (w_out + E[y]) + b_out with f = the pooled feature D_.  Each row is drawn the way Discriminator.Output.W is:
+    Linear's default initialiser at fan-in DIM_D, fan-out 1.  Created by its first use - in DiscriminatorTail, after the output head, the
+    last parameter of the critic - so every other parameter keeps its place and value."""
+    D = cfg.DIM_D
+
+    def make(rng):
+        stdev = _linear._weights_stdev if _linear._weights_stdev is not None else np.sqrt(2. / (D + 1))
+        return rng.uniform(low=-stdev * np.sqrt(3), high=stdev * np.sqrt(3), size=(10, D)).astype('float32')
+
+    return lib.param('Discriminator.Projection.W', make)
+
+
+def head_labels(labels):
+    """The labels the critic's output head consumes: the projection head's (cfg.PROJECTION), else None (critic_labels serves the blocks)."""
+    return labels if cfg.PROJECTION else None
+
+
+def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan'), labels=None, proj_labels=None):
     """dropout -> block 3 -> dropout -> block 4 -> dropout -> relu -> mean -> heads (:173-186).
-    `heads`: which of the two linear heads the caller consumes (the other one is not launched)."""
+    `heads`: which of the two linear heads the caller consumes (the other one is not launched).
+    proj_labels (cfg.PROJECTION): one label per row for the projection term f . E[label] of the output head, op by op."""
     D = cfg.DIM_D
     out = DiscriminatorTailBody(h, kp1, kp2, kp3, u=u, rng=rng, labels=labels)
     output2 = F.spatial_mean(out)
     output_wgan = _linear.Linear('Discriminator.Output', D, 1, output2).reshape(-1) if 'wgan' in heads else None
+    if cfg.PROJECTION and output_wgan is not None:
+        output_wgan = output_wgan + (output2 * F.rows_gather(projection_table(), proj_labels)).sum(1)
     if cfg.CONDITIONAL and cfg.ACGAN and 'acgan' in heads:
         output_acgan = _linear.Linear('Discriminator.ACGANOutput', D, 10, output2)
         return output_wgan, output2, output_acgan
@@ -336,8 +364,9 @@ def DiscriminatorTail(h, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan'
 def Discriminator(inputs, labels, kp1, kp2, kp3, u=None, rng=None, heads=('wgan', 'acgan')):
     """:169-186 - returns (D [n], D_ [n,DIM_D], acgan logits [n,10] or None).
     `u` = the three dropout uniforms [n,DIM_D,8,8] (explicit draws); else drawn from `rng`."""
+    proj = head_labels(labels)
     labels = critic_labels(labels)
-    return DiscriminatorTail(DiscriminatorTrunk(inputs, labels), kp1, kp2, kp3, u=u, rng=rng, heads=heads, labels=labels)
+    return DiscriminatorTail(DiscriminatorTrunk(inputs, labels), kp1, kp2, kp3, u=u, rng=rng, heads=heads, labels=labels, proj_labels=proj)
 
 
 def build_params(device=None):
@@ -451,7 +480,10 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
             d_gp = Discriminator(interp, labels, 0.8, 0.5, 0.5, u=u_gp, rng=rng, heads=('wgan',))[0]
     if fuse_heads:
         # D(x_hat) itself is never used: start the backward at the last block with dD/dz (one launch)
-        gz = F.gp_head_grad(y_gp, lib.param('Discriminator.Output.W'), 1.0 / 0.5)
+        if cfg.PROJECTION:       # x_hat_i lies between real_i and the fake drawn from labels[i]: one label
+            gz = F.gp_head_grad(y_gp, lib.param('Discriminator.Output.W'), 1.0 / 0.5, emb=projection_table(), labels=labels)
+        else:
+            gz = F.gp_head_grad(y_gp, lib.param('Discriminator.Output.W'), 1.0 / 0.5)
         (grads,) = torch.autograd.grad(y_gp, interp, grad_outputs=gz, create_graph=True)
     else:
         ones = torch.ones_like(d_gp)
@@ -597,12 +629,14 @@ class Trainer:
                 y, P('Discriminator.Output.W'), P('Discriminator.Output.b'),
                 P('Discriminator.ACGANOutput.W') if use_ac else None, P('Discriminator.ACGANOutput.b') if use_ac else None,
                 labels, B, cfg.LAMBDA_2, cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, 1.0 / 0.5, gp,
-                slopes if HEADS_FOLD else None, cfg.GP_LAMBDA, y_clean, False)
+                slopes if HEADS_FOLD else None, cfg.GP_LAMBDA, y_clean, False, emb=projection_table() if cfg.PROJECTION else None)
         else:
             tail_in = _cat_rows(h, h[:B])
             lab_c = critic_labels(labels)           # rows: real, fake (pass 1), real (pass 2)
+            lab_p = head_labels(labels)
             d_all, f_all, a_all = DiscriminatorTail(tail_in, 0.8, 0.5, 0.5, u=u, rng=rng,
-                                                    labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None)
+                                                    labels=torch.cat([lab_c, lab_c, lab_c], 0) if lab_c is not None else None,
+                                                    proj_labels=torch.cat([lab_p, lab_p, lab_p], 0) if lab_p is not None else None)
             # every loss head of the two dropout passes in one kernel (fwd) / one kernel (bwd): wgan :244, CT :288-291, ACGAN :246-248
             cost, wgan, ct, acgan, disc_wgan = F.critic_heads(d_all, f_all, a_all if use_ac else None, labels, B, cfg.LAMBDA_2,
                                                               cfg.Factor_M, cfg.ACGAN_SCALE if use_ac else 0.0, gp)
@@ -680,7 +714,8 @@ class Trainer:
                 cost, _ = F.gen_tail_heads(y, lib.param('Discriminator.Output.W'), lib.param('Discriminator.Output.b'),
                                            lib.param('Discriminator.ACGANOutput.W') if use_ac else None,
                                            lib.param('Discriminator.ACGANOutput.b') if use_ac else None, fake_labels,
-                                           cfg.ACGAN_SCALE_G if use_ac else 0.0, 1.0 / 0.5)
+                                           cfg.ACGAN_SCALE_G if use_ac else 0.0, 1.0 / 0.5,
+                                           emb=projection_table() if cfg.PROJECTION else None)
                 return {'cost': cost, 'samples': x}
             d, _, a = Discriminator(xa, fake_labels, 0.8, 0.5, 0.5, u=u, rng=rng)
         cost = F.mean_diff(d, n, 0, -1.0, 0.0)

@@ -2238,6 +2238,120 @@ def gp_head_wgrad(gg, y, mask_scale, like, add_to=None):
     return gw
 
 
+# ---- projection head (NOT in the reference): D(x, y) = f . (w_out + emb[y]) + b_out, the fused heads above with a per-row weight vector.
+# emb [n_labels, nf] fp32; labels int32 in [0, n_labels) - a label outside is the caller's error (as for rows_gather), not checked.
+def _proj_args(emb, labels, nf, n_rows):
+    assert emb.dim() == 2 and emb.is_contiguous() and emb.shape[1] == nf and emb.dtype == torch.float32
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n_rows
+    return emb.shape[0]
+
+
+def tail_critic_heads_fwd_proj(y, B, w_out, b_out, emb, labels, gp, lam2, M, slopes=None, gp_lambda=0.0):
+    """tail_critic_heads_fwd with the projected head (no class head, no clean rows): row r of the 3B rows reads labels[r % B].
+    -> (out[5] = {cost, wgan, ct, 0, wgan + ct + gp}, f [3B,nf], d [3B], ct_i [B]); gp / slopes as in tail_critic_heads_fwd."""
+    _need_dev(y, w_out, b_out, emb, labels, gp, slopes)
+    n, hw, nf = _cl_rows(y)
+    assert n == 3 * B and w_out.is_contiguous() and w_out.numel() == nf
+    n_labels = _proj_args(emb, labels, nf, B)
+    dev = y.device
+    assert slopes is None or (gp is not None and slopes.is_contiguous() and slopes.numel() == B)
+    f = torch.empty(n, nf, dtype=torch.float32, device=dev)
+    d = torch.empty(n, dtype=torch.float32, device=dev)
+    ct_i = torch.empty(B, dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    check(lib.ctgan_tail_critic_heads_fwd_proj(_ptr(y), B, hw, nf, _ptr(w_out), _ptr(b_out), _ptr(emb), n_labels, _ptr(labels), _ptr(gp),
+                                               _ptr(slopes), gp_lambda, lam2, M, _ptr(f), _ptr(d), _ptr(ct_i), _ptr(out), _stream()),
+          'tail_critic_heads_fwd_proj')
+    return out, f, d, ct_i
+
+
+def tail_heads_bwd_proj(y, d, f, labels, ct_i, gout, B, lam2, M, mask_scale, w_out, emb, out=None, y_gp=None, out_gp=None):
+    """tail_heads_bwd with the projected head -> (gy, gw_out, gb_out, g_emb [n_labels,nf]) - one launch.  Penalty row i (y_gp, at most B rows)
+    reads labels[i]: out_gp = gp_head_grad_proj(y_gp, w_out, mask_scale, emb, labels[:n_gp])."""
+    _need_dev(y, d, f, labels, ct_i, gout, w_out, emb, out, y_gp, out_gp)
+    n, hw, nf = _cl_rows(y)
+    assert n == 3 * B and gout.is_contiguous() and gout.numel() in (1, 4)
+    assert w_out.is_contiguous() and w_out.numel() == nf
+    n_labels = _proj_args(emb, labels, nf, B)
+    if out is not None:
+        assert tuple(out.shape) == tuple(y.shape) and _cl_rows(out) == (n, hw, nf)
+        gy = out
+    else:
+        gy = empty_cl(n, nf, y.shape[2], y.shape[3], y.device)
+    gw_out = torch.empty_like(w_out); gb_out = torch.empty(1, dtype=torch.float32, device=y.device)
+    g_emb = torch.empty_like(emb)
+    n_gp = 0
+    if y_gp is not None:
+        n_gp = y_gp.shape[0]
+        assert n_gp <= B
+        assert out_gp is not None and tuple(out_gp.shape) == tuple(y_gp.shape) and _cl_rows(y_gp) == (n_gp, hw, nf) and _cl_rows(out_gp) == (n_gp, hw, nf)
+    check(lib.ctgan_tail_heads_bwd_proj(_ptr(y), _ptr(d), _ptr(f), _ptr(labels), _ptr(ct_i), _ptr(gout), gout.numel(), B, hw, nf, lam2, M, mask_scale,
+                                        _ptr(w_out), _ptr(emb), n_labels, _ptr(gy), _ptr(gw_out), _ptr(gb_out), _ptr(g_emb), _ptr(y_gp), n_gp,
+                                        _ptr(out_gp), _stream()), 'tail_heads_bwd_proj')
+    return gy, gw_out, gb_out, g_emb
+
+
+def gen_heads_fwd_proj(y, w_out, b_out, emb, labels):
+    """-> (cost [1] = -mean(d), d [n]) with d = f . (w_out + emb[labels]) + b_out from the last critic block's output."""
+    _need_dev(y, w_out, b_out, emb, labels)
+    n, hw, nf = _cl_rows(y)
+    assert w_out.is_contiguous() and w_out.numel() == nf
+    n_labels = _proj_args(emb, labels, nf, n)
+    dev = y.device
+    f = torch.empty(n, nf, dtype=torch.float32, device=dev); d = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    check(lib.ctgan_gen_heads_fwd_proj(_ptr(y), n, hw, nf, _ptr(w_out), _ptr(b_out), _ptr(emb), n_labels, _ptr(labels), _ptr(f), _ptr(d), _ptr(out),
+                                       _stream()), 'gen_heads_fwd_proj')
+    return out, d
+
+
+def gen_heads_bwd_proj(y, labels, gout, mask_scale, w_out, emb):
+    """gradient of that cost w.r.t. the last critic conv's result (mask and 1/keep included), one launch."""
+    _need_dev(y, labels, gout, w_out, emb)
+    n, hw, nf = _cl_rows(y)
+    assert w_out.is_contiguous() and w_out.numel() == nf
+    n_labels = _proj_args(emb, labels, nf, n)
+    gy = empty_cl(n, nf, y.shape[2], y.shape[3], y.device)
+    check(lib.ctgan_gen_heads_bwd_proj(_ptr(y), _ptr(labels), _ptr(gout), n, hw, nf, mask_scale, _ptr(w_out), _ptr(emb), n_labels, _ptr(gy),
+                                       _stream()), 'gen_heads_bwd_proj')
+    return gy
+
+
+def gp_head_grad_proj(y, w_out, mask_scale, emb, labels, out=None):
+    """gz = (y > 0) * (w_out + emb[labels[row]]) / hw * mask_scale; labels [n], one per row; out: buffer for gz (as gp_head_grad)."""
+    _need_dev(y, w_out, emb, labels, out)
+    n, hw, nf = _cl_rows(y)
+    assert w_out.is_contiguous() and w_out.numel() == nf
+    n_labels = _proj_args(emb, labels, nf, n)
+    if out is not None:
+        assert tuple(out.shape) == tuple(y.shape) and _cl_rows(out) == (n, hw, nf)
+        gz = out
+    else:
+        gz = empty_cl(n, nf, y.shape[2], y.shape[3], y.device)
+    check(lib.ctgan_gp_head_grad_proj(_ptr(y), _ptr(w_out), _ptr(emb), _ptr(labels), n_labels, n, hw, nf, mask_scale, _ptr(gz), _stream()),
+          'gp_head_grad_proj')
+    return gz
+
+
+def gp_head_wgrad_proj(gg, y, mask_scale, like, emb, labels, add_to=None, add_to_emb=None):
+    """Adjoint of gp_head_grad_proj -> (gw_out like `like`, g_emb like emb): gw_out as gp_head_wgrad, g_emb[c] = the same sum over the rows of
+    label c.  add_to / add_to_emb (both or neither): finished gradients the results are ADDED onto in place (and they are returned)."""
+    _need_dev(gg, y, emb, labels, add_to, add_to_emb)
+    n, hw, nf = _cl_rows(y)
+    assert tuple(gg.shape) == tuple(y.shape) and gg.permute(0, 2, 3, 1).is_contiguous()
+    n_labels = _proj_args(emb, labels, nf, n)
+    assert (add_to is None) == (add_to_emb is None)
+    ws = torch.empty(n * nf, dtype=torch.float32, device=y.device)
+    if add_to is not None:
+        assert add_to.is_contiguous() and add_to.numel() == nf
+        assert add_to_emb.is_contiguous() and tuple(add_to_emb.shape) == tuple(emb.shape) and add_to_emb.dtype == torch.float32
+    gw = add_to if add_to is not None else torch.empty_like(like)
+    g_emb = add_to_emb if add_to_emb is not None else torch.empty_like(emb)
+    check(lib.ctgan_gp_head_wgrad_proj(_ptr(gg), _ptr(y), _ptr(labels), n_labels, n, hw, nf, mask_scale, _ptr(gw), _ptr(g_emb), _ptr(ws),
+                                       0 if add_to is None else 1, _stream()), 'gp_head_wgrad_proj')
+    return gw, g_emb
+
+
 def gp_finish(ga, gs, scale):
     """ga [B,C,H,W] (plain NCHW, contiguous) += scale * upsample2(gs [B,C,H/2,W/2], any strides), in place; -> slopes [B] = per-sample L2
     norm of the result.  The end of the penalty's first backward: gradient through the first conv + through the pooled shortcut."""

@@ -611,6 +611,40 @@ int ctgan_gp_head_grad(const float* y, const float* w_out, int32_t n, int32_t hw
                        float* gz, ctgan_stream_t stream);
 int ctgan_gp_head_wgrad(const float* gg, const float* y, int32_t n, int32_t hw, int32_t nf, float mask_scale, float* gw,
                         float* ws /* 64 * nf floats */, int accumulate, ctgan_stream_t stream);
+/* ---- Projection head (Miyato & Koyama 2018; NOT in the reference): D(x, y) = f . (w_out + E[y]) + b_out with a label table
+ * emb = E [n_labels, nf] (row-major; 4-byte alignment is enough: it lives in the optimizer's flat bucket) - the output head above with a PER-ROW weight vector, so every entry point below is its
+ * twin without the `_proj` with w_out + emb[label of the row] wherever the twin reads w_out: same launches, same grids for the rows, same
+ * summation orders (a zero table gives the twin's bits).  There is no class head and there are no clean rows in these forms.
+ * labels are int32 in [0, n_labels); a label outside that range is the CALLER's error (as for ctgan_rows_gather): it is not checked and
+ * makes the kernels read outside emb.  No kernel writes through a label: g_emb is indexed by class.
+ *   tail_critic_heads_fwd_proj : labels [B]; row r of the 3B rows [real, fake, real'] reads labels[r % B].  gp / slopes / gp_lambda as in
+ *                                ctgan_tail_critic_heads_fwd.  out[5] = {cost, wgan, ct, 0, wgan + ct + gp}.
+ *   tail_heads_bwd_proj        : as ctgan_tail_heads_bwd; penalty row i (n_gp <= B rows) reads labels[i]; additionally
+ *                                g_emb [n_labels, nf]: g_emb[c][j] = sum over the rows r with labels[r % B] = c of f[r][j] * gd[r], in ascending
+ *                                row order by one wave per element (no atomics: the same bits on every run).  Every element is written; the
+ *                                row of a class no sample carries is exact zeros.  sum_c g_emb[c] = gw_out up to rounding.
+ *   gen_heads_fwd_proj / _bwd_proj : labels [n], one per row; cost = -mean(d); gy = (y > 0) (-gout / n) (w_out + emb[label]) / hw * mask_scale.
+ *   gp_head_grad_proj          : labels [n], one per row; gz = (y > 0) (w_out + emb[label]) / hw * mask_scale.
+ *   gp_head_wgrad_proj         : its adjoint: gw [nf] as ctgan_gp_head_wgrad and g_emb[c][j] = the same sum over the rows of label c; accumulate != 0
+ *                                ADDS onto both.  Any nf % 4 == 0 up to 1024; ws = n * nf floats.  Two launches: per-row partial sums, then
+ *                                their sum over the rows in ascending order (for n = 64 the additions are ctgan_gp_head_wgrad's, in its order). */
+int ctgan_tail_critic_heads_fwd_proj(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out,
+                                     const float* emb, int32_t n_labels, const int32_t* labels, float* gp, const float* slopes,
+                                     float gp_lambda, float lambda2, float M, float* f, float* d, float* ct_i, float* out,
+                                     ctgan_stream_t stream);
+int ctgan_tail_heads_bwd_proj(const float* y, const float* d, const float* f, const int32_t* labels, const float* ct_i, const float* gout,
+                              int32_t n_gout, int32_t B, int32_t hw, int32_t nf, float lambda2, float M, float mask_scale,
+                              const float* w_out, const float* emb, int32_t n_labels, float* gy, float* gw_out, float* gb_out, float* g_emb,
+                              const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t stream);
+int ctgan_gen_heads_fwd_proj(const float* y, int32_t n, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
+                             int32_t n_labels, const int32_t* labels, float* f, float* d, float* out, ctgan_stream_t stream);
+int ctgan_gen_heads_bwd_proj(const float* y, const int32_t* labels, const float* gout, int32_t n, int32_t hw, int32_t nf, float mask_scale,
+                             const float* w_out, const float* emb, int32_t n_labels, float* gy, ctgan_stream_t stream);
+int ctgan_gp_head_grad_proj(const float* y, const float* w_out, const float* emb, const int32_t* labels, int32_t n_labels, int32_t n,
+                            int32_t hw, int32_t nf, float mask_scale, float* gz, ctgan_stream_t stream);
+int ctgan_gp_head_wgrad_proj(const float* gg, const float* y, const int32_t* labels, int32_t n_labels, int32_t n, int32_t hw, int32_t nf,
+                             float mask_scale, float* gw, float* g_emb, float* ws /* n * nf floats */, int accumulate,
+                             ctgan_stream_t stream);
 /* ACGAN accuracies of the clean critic pass (:249-266): logits [2B,ncls] (real rows, then fake rows); acc[2]   */
 int ctgan_accuracy2(const float* logits, const int32_t* labels, int32_t B, int32_t ncls, float* acc,
                     ctgan_stream_t stream);
