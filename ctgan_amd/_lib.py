@@ -211,32 +211,20 @@ SIGNATURES = {
     'ctgan_gp_head_grad_proj': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p]),
     'ctgan_gp_head_wgrad_proj': (c_int, [_p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_int, _p]),
     'ctgan_accuracy2': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
-    'ctgan_adam_step': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
+    # the optimizer updates: avg (may be NULL, then rate 0), avg_rate, scaler (may be NULL) ahead of the stream
+    'ctgan_adam_step': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
     'ctgan_adam_advance': (c_int, [_p, c_float, c_float, _p]),
-    'ctgan_step_advance': (c_int, [_p, c_float, c_float, _p, c_uint64, _p]),
+    'ctgan_step_advance': (c_int, [_p, c_float, c_float, _p, c_uint64, _p, c_int64, c_float, c_float, _p]),
     'ctgan_adam_step_packed': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float, c_float,
-                                       c_float, c_float, _p]),
+                                       c_float, c_float, _p, c_float, _p, _p]),
     'ctgan_pack': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p]),
-    'ctgan_rmsprop_step': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p]),
+    'ctgan_rmsprop_step': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
     'ctgan_rmsprop_step_packed': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float, c_float,
-                                          c_float, c_float, _p]),
-    'ctgan_adam_step_avg': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p]),
-    'ctgan_adam_step_packed_avg': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float,
-                                           c_float, c_float, c_float, _p, c_float, _p]),
-    'ctgan_rmsprop_step_avg': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p]),
-    'ctgan_rmsprop_step_packed_avg': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float,
-                                              c_float, c_float, c_float, _p, c_float, _p]),
+                                          c_float, c_float, _p, c_float, _p, _p]),
     'ctgan_exchange': (c_int, [_p, _p, c_int64, _p]),
-    # dynamic loss scale: scan, the scaled updates (avg may be NULL), the scaled end of a step
+    # dynamic loss scale: the scan
     'ctgan_grads_nonfinite_blocks': (ctypes.c_uint, [c_int64, c_int32]),
     'ctgan_grads_nonfinite': (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, _p, _p]),
-    'ctgan_adam_step_scaled': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
-    'ctgan_adam_step_packed_scaled': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, _p, c_float,
-                                              c_float, c_float, c_float, _p, c_float, _p, _p]),
-    'ctgan_rmsprop_step_scaled': (c_int, [_p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
-    'ctgan_rmsprop_step_packed_scaled': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), c_int32, _p, _p, _p, _p, c_float,
-                                                 c_float, c_float, c_float, _p, c_float, _p, _p]),
-    'ctgan_step_advance_scaled': (c_int, [_p, c_float, c_float, _p, c_uint64, _p, c_int64, c_float, c_float, _p]),
     'ctgan_dropout_rng':(c_int, [_p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_dropout_rng_mask': (c_int, [_p, _p, _p, _p, c_int64, c_float, c_uint64, c_uint64, _p, _p]),
     'ctgan_lrelu_dropout_rng': (c_int, [_p, _p, _p, c_int64, c_float, c_float, c_uint64, c_uint64, _p, _p]),

@@ -1,6 +1,7 @@
 // optim_rng.hip - TF-form Adam on flat buffers (K21) and Philox4x32-10 random streams (K12/K19).
 #include "common.h"
 #include "philox.h"
+#include <type_traits>
 
 namespace {
 using namespace ctgan_philox;
@@ -557,97 +558,71 @@ __global__ void exchange_kernel(float* __restrict__ a, float* __restrict__ b, lo
     }
 }
 
-// Host side of the four update launches, one template each on "keeps an average" (the C entry points below forward here).
-inline bool avg_args_bad(const float* avg, float avg_rate) { return !avg || !(avg_rate > 0.f && avg_rate <= 1.f); }
-// ... and on "under the dynamic loss scale" (scaler = device float[4], see adam_kernel).  Launches per kind since the library was loaded
-// (ctgan_debug_optim_launches): what a test reads to see that a run without a scaler launches none of the scaled forms.
+// Launches per kind since the library was loaded (ctgan_debug_optim_launches): what a test reads to see that a run without a scaler
+// launches none of the scaled forms.
 unsigned long long g_optim_launches[5];
 enum { LAUNCH_UPDATE = 0, LAUNCH_ADVANCE = 1, LAUNCH_SCAN = 2, LAUNCH_UPDATE_SCALED = 3, LAUNCH_ADVANCE_SCALED = 4 };
-template <bool SCALED> inline void count_update() { ++g_optim_launches[SCALED ? LAUNCH_UPDATE_SCALED : LAUNCH_UPDATE]; }
 
-template <bool AVG, bool SCALED>
-int adam_step_host(const char* what, float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2,
-                   float eps, float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (!theta || !g || !m || !v || !state || n < 0 || (SCALED && !scaler)) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
-    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
-    if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL((adam_kernel<AVG, SCALED>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g, m,
-                       v, (long long)n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
-    count_update<SCALED>();
+// The two optional operands of an update, checked ahead of any launch: avg (device float[n], NULL: no average; then avg_rate is 0) and
+// scaler (device float[4], see adam_kernel; NULL: no dynamic loss scale).  0 or the error.
+int check_avg(const char* what, const float* avg, float avg_rate) {
+    if (!avg && !(avg_rate == 0.f)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null but avg_rate is not 0", what);
+    if (avg && !(avg_rate > 0.f && avg_rate <= 1.f)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is given but avg_rate is outside (0, 1]", what);
+    return CTGAN_OK;
+}
+// ... and turned into the template arguments of the update kernels, here and nowhere else: launch(AVG, SCALED) gets them as
+// std::bool_constant values; the launch is counted under its kind.
+template <class Launch>
+int launch_update(const char* what, const float* avg, const float* scaler, Launch launch) {
+    using yes = std::true_type; using no = std::false_type;
+    if (avg) { if (scaler) launch(yes{}, yes{}); else launch(yes{}, no{}); }
+    else     { if (scaler) launch(no{}, yes{}); else launch(no{}, no{}); }
+    ++g_optim_launches[scaler ? LAUNCH_UPDATE_SCALED : LAUNCH_UPDATE];
     return ctgan_check_launch(what);
 }
-// the pointer table of a packed update; 0 or the error
+// the pointer table of a launch over separately allocated tensors (dst_offs == NULL: a table of sources alone); 0 or the error
 int fill_pack_table(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                    PackTable& t, long long& mx) {
-    mx = 1;
+                    PackTable& t) {
     for (int i = 0; i < n_tensors; ++i) {
-        if (counts[i] < 0 || dst_offs[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: negative extent", what);
-        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs[i]; t.n[i] = counts[i];
-        if (t.n[i] > mx) mx = t.n[i];
+        if (counts[i] < 0 || (dst_offs && dst_offs[i] < 0)) return ctgan_fail(CTGAN_E_BADARG, "%s: negative extent", what);
+        t.src[i] = srcs[i]; t.dst_off[i] = dst_offs ? dst_offs[i] : 0; t.n[i] = counts[i];
     }
     return CTGAN_OK;
 }
-template <bool AVG, bool SCALED>
-int adam_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                          float* flat, float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps,
-                          float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0 || (SCALED && !scaler))
-        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
-    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
-    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
-    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(m) |
-         reinterpret_cast<uintptr_t>(v) | (AVG ? reinterpret_cast<uintptr_t>(avg) : 0)) & 15)
-        return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: flat buffers must be 16-byte aligned", what);
-    PackTable t;
-    long long mx;
-    if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
-    hipLaunchKernelGGL((adam_packed_kernel<AVG, SCALED>), dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0,
-                       static_cast<hipStream_t>(s), t, flat, theta, m, v, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
-    count_update<SCALED>();
-    return ctgan_check_launch(what);
+// what grid.x has to cover: the largest extent, at least 1 (with_null = false: of the tensors that have a source)
+long long max_extent(const PackTable& t, int n_tensors, bool with_null = true) {
+    long long mx = 1;
+    for (int i = 0; i < n_tensors; ++i)
+        if ((with_null || t.src[i]) && t.n[i] > mx) mx = t.n[i];
+    return mx;
 }
-template <bool AVG, bool SCALED>
-int rmsprop_step_host(const char* what, float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                      float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (!theta || !g || !ms || !state || n < 0 || (SCALED && !scaler)) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
-    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
-    if (n == 0) return CTGAN_OK;
-    hipLaunchKernelGGL((rmsprop_kernel<AVG, SCALED>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(s), theta, g,
-                       ms, (long long)n, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
-    count_update<SCALED>();
-    return ctgan_check_launch(what);
-}
-template <bool AVG, bool SCALED>
-int rmsprop_step_packed_host(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                             float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                             float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0 || (SCALED && !scaler))
-        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
-    if (AVG && avg_args_bad(avg, avg_rate)) return ctgan_fail(CTGAN_E_BADARG, "%s: avg is null or avg_rate is outside (0, 1]", what);
+// the checks that the two packed updates share, then the table (slot2: m's second slot v, NULL for RMSProp); 0 or the error
+int packed_update_args(const char* what, const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
+                       const float* flat, const float* theta, const float* slot, const float* slot2, const float* avg, float avg_rate,
+                       PackTable& t) {
+    if (int rc = check_avg(what, avg, avg_rate)) return rc;
     if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
-    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(ms) |
-         (AVG ? reinterpret_cast<uintptr_t>(avg) : 0)) & 15)
+    if ((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(slot) |
+         reinterpret_cast<uintptr_t>(slot2) | reinterpret_cast<uintptr_t>(avg)) & 15)
         return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: flat buffers must be 16-byte aligned", what);
-    PackTable t;
-    long long mx;
-    if (int rc = fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t, mx)) return rc;
-    hipLaunchKernelGGL((rmsprop_packed_kernel<AVG, SCALED>), dim3(ctgan_blocks(mx, 1024, 512), n_tensors), dim3(256), 0,
-                       static_cast<hipStream_t>(s), t, flat, theta, ms, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
-    count_update<SCALED>();
-    return ctgan_check_launch(what);
+    return fill_pack_table(what, srcs, dst_offs, counts, n_tensors, t);
 }
 
 }  // namespace
 
 extern "C" {
 
-int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
-                    float beta2, float eps, float grad_scale, ctgan_stream_t s) {
-    return adam_step_host<false, false>("adam_step", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, nullptr, s);
-}
-int ctgan_adam_step_avg(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
-                        float beta2, float eps, float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    return adam_step_host<true, false>("adam_step_avg", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, nullptr, s);
+// The four updates: one entry each; avg and scaler are optional and pick the kernel instantiation (launch_update).
+int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
+                    float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    const char* what = "adam_step";
+    if (!theta || !g || !m || !v || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (int rc = check_avg(what, avg, avg_rate)) return rc;
+    if (n == 0) return CTGAN_OK;
+    return launch_update(what, avg, scaler, [&](auto AVG, auto SCALED) {
+        hipLaunchKernelGGL((adam_kernel<decltype(AVG)::value, decltype(SCALED)::value>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0,
+                           static_cast<hipStream_t>(s), theta, g, m, v, (long long)n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
+    });
 }
 int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
                ctgan_stream_t s) {
@@ -666,103 +641,77 @@ int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t*
     }
     return CTGAN_OK;
 }
-int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, ctgan_stream_t s) {
-    if (!state) return ctgan_fail(CTGAN_E_BADARG, "step_advance: null");
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by);
-    ++g_optim_launches[LAUNCH_ADVANCE];
-    return ctgan_check_launch("step_advance");
-}
 int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                           float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                           ctgan_stream_t s) {
-    return adam_step_packed_host<false, false>("adam_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1, beta2,
-                                               eps, grad_scale, nullptr, 0.f, nullptr, s);
-}
-int ctgan_adam_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                               float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                               float* avg, float avg_rate, ctgan_stream_t s) {
-    return adam_step_packed_host<true, false>("adam_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
-                                              beta2, eps, grad_scale, avg, avg_rate, nullptr, s);
+                           float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale, float* avg,
+                           float avg_rate, const float* scaler, ctgan_stream_t s) {
+    const char* what = "adam_step_packed";
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !m || !v || !state || n_tensors <= 0)
+        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    PackTable t;
+    if (int rc = packed_update_args(what, srcs, dst_offs, counts, n_tensors, flat, theta, m, v, avg, avg_rate, t)) return rc;
+    return launch_update(what, avg, scaler, [&](auto AVG, auto SCALED) {
+        hipLaunchKernelGGL((adam_packed_kernel<decltype(AVG)::value, decltype(SCALED)::value>),
+                           dim3(ctgan_blocks(max_extent(t, n_tensors), 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t, flat,
+                           theta, m, v, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler);
+    });
 }
 int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                       float grad_scale, ctgan_stream_t s) {
-    return rmsprop_step_host<false, false>("rmsprop_step", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, nullptr, s);
-}
-int ctgan_rmsprop_step_avg(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                           float grad_scale, float* avg, float avg_rate, ctgan_stream_t s) {
-    return rmsprop_step_host<true, false>("rmsprop_step_avg", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, nullptr, s);
+                       float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
+    const char* what = "rmsprop_step";
+    if (!theta || !g || !ms || !state || n < 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (int rc = check_avg(what, avg, avg_rate)) return rc;
+    if (n == 0) return CTGAN_OK;
+    return launch_update(what, avg, scaler, [&](auto AVG, auto SCALED) {
+        hipLaunchKernelGGL((rmsprop_kernel<decltype(AVG)::value, decltype(SCALED)::value>), dim3(ctgan_blocks(n, 256, 2048)), dim3(256), 0,
+                           static_cast<hipStream_t>(s), theta, g, ms, (long long)n, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
+    });
 }
 int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                              ctgan_stream_t s) {
-    return rmsprop_step_packed_host<false, false>("rmsprop_step_packed", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho, eps,
-                                                  clip, grad_scale, nullptr, 0.f, nullptr, s);
+                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale, float* avg,
+                              float avg_rate, const float* scaler, ctgan_stream_t s) {
+    const char* what = "rmsprop_step_packed";
+    if (!srcs || !dst_offs || !counts || !flat || !theta || !ms || !state || n_tensors <= 0)
+        return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    PackTable t;
+    if (int rc = packed_update_args(what, srcs, dst_offs, counts, n_tensors, flat, theta, ms, nullptr, avg, avg_rate, t)) return rc;
+    return launch_update(what, avg, scaler, [&](auto AVG, auto SCALED) {
+        hipLaunchKernelGGL((rmsprop_packed_kernel<decltype(AVG)::value, decltype(SCALED)::value>),
+                           dim3(ctgan_blocks(max_extent(t, n_tensors), 1024, 512), n_tensors), dim3(256), 0, static_cast<hipStream_t>(s), t, flat,
+                           theta, ms, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler);
+    });
 }
-int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                                  float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale, float* avg,
-                                  float avg_rate, ctgan_stream_t s) {
-    return rmsprop_step_packed_host<true, false>("rmsprop_step_packed_avg", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho,
-                                                 eps, clip, grad_scale, avg, avg_rate, nullptr, s);
-}
-// ---- the dynamic loss scale: scan, the four scaled updates (avg == NULL: without the average), the scaled end of a step
+// ---- the dynamic loss scale: the scan ahead of an update with a scaler
 unsigned ctgan_grads_nonfinite_blocks(int64_t max_count, int32_t n_tensors) {
     // one table entry (the flat bucket) gets the grid of the plain update kernels; a table the grid of the packed ones, in 16-byte items
     return n_tensors == 1 ? ctgan_blocks((max_count + 3) >> 2, 256, 2048) : ctgan_blocks((max_count + 3) >> 2, 256, 512);
 }
 int ctgan_grads_nonfinite(const float* const* srcs, const int64_t* counts, int32_t n_tensors, float* scaler, ctgan_stream_t s) {
-    if (!srcs || !counts || !scaler || n_tensors <= 0) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: bad argument");
-    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "grads_nonfinite: more than %d tensors", PACK_MAX);
+    const char* what = "grads_nonfinite";
+    if (!srcs || !counts || !scaler || n_tensors <= 0) return ctgan_fail(CTGAN_E_BADARG, "%s: bad argument", what);
+    if (n_tensors > PACK_MAX) return ctgan_fail(CTGAN_E_UNSUPPORTED, "%s: more than %d tensors", what, PACK_MAX);
     PackTable t;
-    long long mx = 1;
-    for (int i = 0; i < n_tensors; ++i) {
-        if (counts[i] < 0) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: negative extent");
-        if (reinterpret_cast<uintptr_t>(srcs[i]) & 3) return ctgan_fail(CTGAN_E_BADARG, "grads_nonfinite: source %d is not 4-byte aligned", i);
-        t.src[i] = srcs[i]; t.dst_off[i] = 0; t.n[i] = counts[i];
-        if (srcs[i] && t.n[i] > mx) mx = t.n[i];
-    }
-    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(ctgan_grads_nonfinite_blocks(mx, n_tensors), n_tensors), dim3(256), 0,
-                       static_cast<hipStream_t>(s), t, scaler);
+    if (int rc = fill_pack_table(what, srcs, nullptr, counts, n_tensors, t)) return rc;
+    for (int i = 0; i < n_tensors; ++i)
+        if (reinterpret_cast<uintptr_t>(srcs[i]) & 3) return ctgan_fail(CTGAN_E_BADARG, "%s: source %d is not 4-byte aligned", what, i);
+    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(ctgan_grads_nonfinite_blocks(max_extent(t, n_tensors, false), n_tensors), n_tensors),
+                       dim3(256), 0, static_cast<hipStream_t>(s), t, scaler);
     ++g_optim_launches[LAUNCH_SCAN];
-    return ctgan_check_launch("grads_nonfinite");
+    return ctgan_check_launch(what);
 }
-int ctgan_adam_step_scaled(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
-                           float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (avg) return adam_step_host<true, true>("adam_step_scaled", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, avg, avg_rate, scaler, s);
-    return adam_step_host<false, true>("adam_step_scaled", theta, g, m, v, n, state, beta1, beta2, eps, grad_scale, nullptr, 0.f, scaler, s);
-}
-int ctgan_adam_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                                  float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                                  float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (avg)
-        return adam_step_packed_host<true, true>("adam_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
-                                                 beta2, eps, grad_scale, avg, avg_rate, scaler, s);
-    return adam_step_packed_host<false, true>("adam_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, m, v, state, beta1,
-                                              beta2, eps, grad_scale, nullptr, 0.f, scaler, s);
-}
-int ctgan_rmsprop_step_scaled(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                              float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (avg) return rmsprop_step_host<true, true>("rmsprop_step_scaled", theta, g, ms, n, state, rho, eps, clip, grad_scale, avg, avg_rate, scaler, s);
-    return rmsprop_step_host<false, true>("rmsprop_step_scaled", theta, g, ms, n, state, rho, eps, clip, grad_scale, nullptr, 0.f, scaler, s);
-}
-int ctgan_rmsprop_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                                     float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                                     float* avg, float avg_rate, const float* scaler, ctgan_stream_t s) {
-    if (avg)
-        return rmsprop_step_packed_host<true, true>("rmsprop_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state,
-                                                    rho, eps, clip, grad_scale, avg, avg_rate, scaler, s);
-    return rmsprop_step_packed_host<false, true>("rmsprop_step_packed_scaled", srcs, dst_offs, counts, n_tensors, flat, theta, ms, state, rho,
-                                                 eps, clip, grad_scale, nullptr, 0.f, scaler, s);
-}
+// End of a step, one launch either way: scaler == NULL ignores the three constants of the scale.
 static bool pow2(float x) { int e; return x > 0.f && x <= 3.0e38f && frexpf(x, &e) == 0.5f; }
-int ctgan_step_advance_scaled(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler,
-                              int64_t growth_interval, float min_scale, float max_scale, ctgan_stream_t s) {
-    if (!state || !scaler) return ctgan_fail(CTGAN_E_BADARG, "step_advance_scaled: null");
-    if (growth_interval < 1 || !pow2(min_scale) || !pow2(max_scale) || min_scale > max_scale)
-        return ctgan_fail(CTGAN_E_BADARG, "step_advance_scaled: growth_interval < 1, or a bound that is no power of two, or min > max");
-    hipLaunchKernelGGL(step_advance_scaled_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by,
-                       scaler, (float)growth_interval, min_scale, max_scale);
-    ++g_optim_launches[LAUNCH_ADVANCE_SCALED];
-    return ctgan_check_launch("step_advance_scaled");
+int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler, int64_t growth_interval,
+                       float min_scale, float max_scale, ctgan_stream_t s) {
+    if (!state) return ctgan_fail(CTGAN_E_BADARG, "step_advance: null");
+    if (scaler && (growth_interval < 1 || !pow2(min_scale) || !pow2(max_scale) || min_scale > max_scale))
+        return ctgan_fail(CTGAN_E_BADARG, "step_advance: growth_interval < 1, or a bound that is no power of two, or min > max");
+    if (scaler)
+        hipLaunchKernelGGL(step_advance_scaled_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by,
+                           scaler, (float)growth_interval, min_scale, max_scale);
+    else
+        hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(s), state, beta1, beta2, rng_ctr, rng_by);
+    ++g_optim_launches[scaler ? LAUNCH_ADVANCE_SCALED : LAUNCH_ADVANCE];
+    return ctgan_check_launch("step_advance");
 }
 uint64_t ctgan_debug_optim_launches(int kind) { return kind >= 0 && kind < 5 ? g_optim_launches[kind] : 0; }
 

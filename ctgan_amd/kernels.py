@@ -1913,13 +1913,6 @@ def gan_loss_bwd(d, gout, B, kind):
 
 
 # ------------------------------------------------------------------------------- optimizer / rng
-def _check_avg(avg, theta, avg_rate):
-    """The weight average of an update launch: laid out like theta; a rate in (0, 1] (the C entry refuses anything else)."""
-    _need_dev(avg)
-    assert avg.is_contiguous() and avg.dtype == torch.float32 and avg.numel() == theta.numel()
-    return float(avg_rate)
-
-
 def _check_scaler(scaler):
     """The state of a dynamic loss scale (optim.LossScaler.state): device float[4] {S, found, good, skipped}."""
     _need_dev(scaler)
@@ -1927,24 +1920,37 @@ def _check_scaler(scaler):
     return _ptr(scaler)
 
 
-def _avg_or_null(avg, theta, avg_rate):
-    """(pointer, rate) of the optional average of a scaled update launch."""
-    return (_ptr(avg), _check_avg(avg, theta, avg_rate)) if avg is not None else (None, 0.0)
+def _avg_scaler(theta, avg, avg_rate, scaler):
+    """(avg pointer, rate, scaler pointer) of an update launch; (None, 0.0) and None for the operand that is off.  The average is laid out
+    like theta; its rate is in (0, 1] (the C entry refuses anything else)."""
+    ps = None if scaler is None else _check_scaler(scaler)
+    if avg is None:
+        return None, 0.0, ps
+    _need_dev(avg)
+    assert avg.is_contiguous() and avg.dtype == torch.float32 and avg.numel() == theta.numel()
+    return _ptr(avg), float(avg_rate), ps
+
+
+def _pack_tables(srcs, dst_offs=None, counts=None):
+    """(P, O, C, n): the host tables of a launch over `srcs`, contiguous fp32 tensors (None = zeros) of counts[i] elements each
+    (counts None: their own numel; dst_offs None: O is None)."""
+    _need_dev(*[t for t in srcs if t is not None])
+    n = len(srcs)
+    if counts is None:
+        counts = [t.numel() if t is not None else 0 for t in srcs]
+    for t, c in zip(srcs, counts):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c)
+    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
+    O = (ctypes.c_int64 * n)(*dst_offs) if dst_offs is not None else None
+    return P, O, (ctypes.c_int64 * n)(*counts), n
 
 
 def grads_nonfinite(srcs, scaler):
     """scaler[1] = 1 if any element of `srcs` - a list of contiguous fp32 tensors (None = zeros; at most ADAM_PACKED_MAX), or ONE tensor,
     the flat bucket - is NaN or +-inf; one launch, nothing read back (ctgan_grads_nonfinite).  The first launch of an update under a
     dynamic loss scale: the `scaler=` form of the update, next on the stream, drops the update when the flag is set."""
-    if torch.is_tensor(srcs):
-        srcs = [srcs]
-    _need_dev(*[t for t in srcs if t is not None])
-    n = len(srcs)
+    P, _, C, n = _pack_tables([srcs] if torch.is_tensor(srcs) else srcs)
     assert 0 < n <= ADAM_PACKED_MAX
-    for t in srcs:
-        assert t is None or (t.is_contiguous() and t.dtype == torch.float32)
-    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
-    C = (ctypes.c_int64 * n)(*[t.numel() if t is not None else 0 for t in srcs])
     check(lib.ctgan_grads_nonfinite(P, C, n, _check_scaler(scaler), _stream()), 'grads_nonfinite')
 
 
@@ -1956,38 +1962,26 @@ def grads_nonfinite_grid(srcs):
 
 
 def adam_step(theta, g, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0, avg=None, avg_rate=0.0, scaler=None):
-    """In-place TF-Adam on flat fp32 buffers; `state` = device float[4] {lr, beta1^t, beta2^t, -}.  `avg` (not in the reference): a
-    weight average moved in the same launch, avg <- avg + avg_rate (theta - avg) after the update (ctgan_adam_step_avg).  `scaler` (not
-    in the reference): the state of a dynamic loss scale - the gradient is also divided by scaler[0], and the whole update is dropped
-    when scaler[1] is set (ctgan_adam_step_scaled; grads_nonfinite sets it).  Both keywords are omitted on the paths without them."""
+    """In-place TF-Adam on flat fp32 buffers (ctgan_adam_step); `state` = device float[4] {lr, beta1^t, beta2^t, -}.  `avg` (not in the
+    reference): a weight average moved in the same launch, avg <- avg + avg_rate (theta - avg) after the update.  `scaler` (not in the
+    reference): the state of a dynamic loss scale - the gradient is also divided by scaler[0], and the whole update is dropped when
+    scaler[1] is set (grads_nonfinite sets it).  Both keywords are omitted on the paths without them."""
     _need_dev(theta, g, m, v, state)
     for t in (theta, g, m, v):
         assert t.is_contiguous() and t.numel() == theta.numel()
-    if scaler is not None:
-        pa, ra = _avg_or_null(avg, theta, avg_rate)
-        check(lib.ctgan_adam_step_scaled(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps, grad_scale,
-                                         pa, ra, _check_scaler(scaler), _stream()), 'adam_step_scaled')
-        return
-    if avg is not None:
-        check(lib.ctgan_adam_step_avg(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps,
-                                      grad_scale, _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'adam_step_avg')
-        return
-    check(lib.ctgan_adam_step(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps,
-                              grad_scale, _stream()), 'adam_step')
+    check(lib.ctgan_adam_step(_ptr(theta), _ptr(g), _ptr(m), _ptr(v), theta.numel(), _ptr(state), beta1, beta2, eps, grad_scale,
+                              *_avg_scaler(theta, avg, avg_rate, scaler), _stream()), 'adam_step')
 
 
 def step_advance(state, beta1, beta2, rng_ctr=None, rng_by=1, scaler=None, scaler_consts=None):
-    """adam_advance(state) and rng_advance(rng_ctr, rng_by) in one launch - the end of a step.  `scaler` (+ scaler_consts =
-    (growth_interval, min_scale, max_scale)): the end of a step under a dynamic loss scale, still one launch - the beta powers advance
-    only when the update was applied, the scale grows or backs off, the flag is cleared (ctgan_step_advance_scaled)."""
+    """adam_advance(state) and rng_advance(rng_ctr, rng_by) in one launch - the end of a step (ctgan_step_advance).  `scaler` (+
+    scaler_consts = (growth_interval, min_scale, max_scale)): the end of a step under a dynamic loss scale, still one launch - the beta
+    powers advance only when the update was applied, the scale grows or backs off, the flag is cleared."""
     _need_dev(state)
     assert rng_ctr is None or (rng_ctr.is_cuda and rng_ctr.dtype == torch.int64)
-    if scaler is not None:
-        growth, s_min, s_max = scaler_consts
-        check(lib.ctgan_step_advance_scaled(_ptr(state), beta1, beta2, _ptr(rng_ctr), rng_by, _check_scaler(scaler), int(growth), float(s_min),
-                                            float(s_max), _stream()), 'step_advance_scaled')
-        return
-    check(lib.ctgan_step_advance(_ptr(state), beta1, beta2, _ptr(rng_ctr), rng_by, _stream()), 'step_advance')
+    growth, s_min, s_max = scaler_consts if scaler is not None else (0, 0.0, 0.0)
+    check(lib.ctgan_step_advance(_ptr(state), beta1, beta2, _ptr(rng_ctr), rng_by, None if scaler is None else _check_scaler(scaler),
+                                 int(growth), float(s_min), float(s_max), _stream()), 'step_advance')
 
 
 ADAM_PACKED_MAX = 64
@@ -1996,25 +1990,11 @@ ADAM_PACKED_MAX = 64
 def adam_step_packed(srcs, dst_offs, counts, flat, theta, m, v, state, beta1, beta2, eps=1e-8, grad_scale=1.0, avg=None, avg_rate=0.0,
                      scaler=None):
     """pack(srcs -> flat) + adam_step in one launch (len(srcs) <= ADAM_PACKED_MAX); `avg`, `scaler`: as adam_step."""
-    _need_dev(flat, theta, m, v, state, *[t for t in srcs if t is not None])
-    n = len(srcs)
+    _need_dev(flat, theta, m, v, state)
+    P, O, C, n = _pack_tables(srcs, dst_offs, counts)
     assert n <= ADAM_PACKED_MAX
-    for t, c in zip(srcs, counts):
-        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c)
-    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
-    O = (ctypes.c_int64 * n)(*dst_offs)
-    C = (ctypes.c_int64 * n)(*counts)
-    if scaler is not None:
-        pa, ra = _avg_or_null(avg, theta, avg_rate)
-        check(lib.ctgan_adam_step_packed_scaled(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps,
-                                                grad_scale, pa, ra, _check_scaler(scaler), _stream()), 'adam_step_packed_scaled')
-        return
-    if avg is not None:
-        check(lib.ctgan_adam_step_packed_avg(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps,
-                                             grad_scale, _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'adam_step_packed_avg')
-        return
     check(lib.ctgan_adam_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(m), _ptr(v), _ptr(state), beta1, beta2, eps, grad_scale,
-                                     _stream()), 'adam_step_packed')
+                                     *_avg_scaler(theta, avg, avg_rate, scaler), _stream()), 'adam_step_packed')
 
 
 def rmsprop_step(theta, g, ms, state, rho, eps, clip=0.0, grad_scale=1.0, avg=None, avg_rate=0.0, scaler=None):
@@ -2023,41 +2003,18 @@ def rmsprop_step(theta, g, ms, state, rho, eps, clip=0.0, grad_scale=1.0, avg=No
     _need_dev(theta, g, ms, state)
     for t in (theta, g, ms):
         assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == theta.numel()
-    if scaler is not None:
-        pa, ra = _avg_or_null(avg, theta, avg_rate)
-        check(lib.ctgan_rmsprop_step_scaled(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, pa, ra,
-                                            _check_scaler(scaler), _stream()), 'rmsprop_step_scaled')
-        return
-    if avg is not None:
-        check(lib.ctgan_rmsprop_step_avg(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, _ptr(avg),
-                                         _check_avg(avg, theta, avg_rate), _stream()), 'rmsprop_step_avg')
-        return
-    check(lib.ctgan_rmsprop_step(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale, _stream()),
-          'rmsprop_step')
+    check(lib.ctgan_rmsprop_step(_ptr(theta), _ptr(g), _ptr(ms), theta.numel(), _ptr(state), rho, eps, clip, grad_scale,
+                                 *_avg_scaler(theta, avg, avg_rate, scaler), _stream()), 'rmsprop_step')
 
 
 def rmsprop_step_packed(srcs, dst_offs, counts, flat, theta, ms, state, rho, eps, clip=0.0, grad_scale=1.0, avg=None, avg_rate=0.0,
                         scaler=None):
     """pack(srcs -> flat) + rmsprop_step in one launch (len(srcs) <= ADAM_PACKED_MAX); `avg`, `scaler`: as adam_step."""
-    _need_dev(flat, theta, ms, state, *[t for t in srcs if t is not None])
-    n = len(srcs)
+    _need_dev(flat, theta, ms, state)
+    P, O, C, n = _pack_tables(srcs, dst_offs, counts)
     assert n <= ADAM_PACKED_MAX
-    for t, c in zip(srcs, counts):
-        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c)
-    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
-    O = (ctypes.c_int64 * n)(*dst_offs)
-    C = (ctypes.c_int64 * n)(*counts)
-    if scaler is not None:
-        pa, ra = _avg_or_null(avg, theta, avg_rate)
-        check(lib.ctgan_rmsprop_step_packed_scaled(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale,
-                                                   pa, ra, _check_scaler(scaler), _stream()), 'rmsprop_step_packed_scaled')
-        return
-    if avg is not None:
-        check(lib.ctgan_rmsprop_step_packed_avg(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale,
-                                                _ptr(avg), _check_avg(avg, theta, avg_rate), _stream()), 'rmsprop_step_packed_avg')
-        return
-    check(lib.ctgan_rmsprop_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale, _stream()),
-          'rmsprop_step_packed')
+    check(lib.ctgan_rmsprop_step_packed(P, O, C, n, _ptr(flat), _ptr(theta), _ptr(ms), _ptr(state), rho, eps, clip, grad_scale,
+                                        *_avg_scaler(theta, avg, avg_rate, scaler), _stream()), 'rmsprop_step_packed')
 
 
 def exchange_(a, b):
@@ -2069,11 +2026,8 @@ def exchange_(a, b):
 
 def pack(srcs, dst_offs, counts, flat):
     """flat[off_i : off_i+n_i] = srcs[i] (None = zeros) for all i in one launch (per 64 tensors)."""
-    _need_dev(flat, *[t for t in srcs if t is not None])
-    n = len(srcs)
-    P = (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in srcs])
-    O = (ctypes.c_int64 * n)(*dst_offs)
-    C = (ctypes.c_int64 * n)(*counts)
+    _need_dev(flat)
+    P, O, C, n = _pack_tables(srcs, dst_offs, counts)
     check(lib.ctgan_pack(P, O, C, n, _ptr(flat), _stream()), 'pack')
 
 

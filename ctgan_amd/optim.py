@@ -89,7 +89,7 @@ class FlatAdam:
         of 1e-4 is a decay of 0.9999 - starting at a COPY of the weights (FlatAdamTheano's starts at zeros, as its script's does).  0: no
         average, and nothing differs from an optimizer built without the argument (launches, slots(), state_dict()).
         scaler (NOT in the reference): a LossScaler, shared with the trainer's other optimizer - update() and step() then run scan ->
-        scaled update -> scaled end of step (kernels.grads_nonfinite, the `scaler=` forms), one launch more than without; the
+        update -> end of step (kernels.grads_nonfinite, then the `scaler=` operand of the other two), one launch more than without; the
         grad_scale they are given is the host's factor only (1 / world), the division by the scale happens on the device.  None: nothing
         differs.  `t` counts ATTEMPTED updates on the host, dropped ones included: with a scaler the beta powers on the device (state[1],
         state[2]) are what knows how many were applied."""
@@ -182,8 +182,17 @@ class FlatAdam:
         counter (DeviceRNG.end_step)."""
         if self.scaler is not None:
             K.grads_nonfinite(self.grad, self.scaler.state)         # (the bucket after the all-reduce: every rank sees the same bits)
-        K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale, **self._extras())
+        self._launch(grad_scale)
         self._end(rng)
+
+    def _launch(self, grad_scale, srcs=None):
+        """The update launch of a step, the one thing an optimizer on these buffers has of its own: over the bucket, or (srcs) gathering
+        the bucket in the same launch."""
+        if srcs is None:
+            K.adam_step(self.theta, self.grad, self.m, self.v, self.state, self.beta1, self.beta2, self.eps, grad_scale, **self._extras())
+        else:
+            K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
+                               self.eps, grad_scale, **self._extras())
 
     def _extras(self):
         """The keywords of an update launch beyond the static one's: each is OMITTED when its feature is off."""
@@ -197,11 +206,8 @@ class FlatAdam:
         return [(n, self.avg[o:o + s].view(p.shape)) for n, p, o, s in zip(self.names, self.params, self.offsets, self.sizes)]
 
     def _end(self, rng):
-        if self.scaler is not None:
-            K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1, scaler=self.scaler.state,
-                           scaler_consts=self.scaler.consts)
-        else:
-            K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1)
+        kw = {'scaler': self.scaler.state, 'scaler_consts': self.scaler.consts} if self.scaler is not None else {}
+        K.step_advance(self.state, self.beta1, self.beta2, rng.ctr if rng is not None else None, 1, **kw)
         self.t += 1
         lib.bump_epoch(self.group)    # this network's weights changed: its derived-filter caches are stale
 
@@ -214,8 +220,7 @@ class FlatAdam:
         srcs = [g.contiguous() if g is not None else None for g in grads]
         if self.scaler is not None:
             K.grads_nonfinite(srcs, self.scaler.state)
-        K.adam_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.m, self.v, self.state, self.beta1, self.beta2,
-                           self.eps, grad_scale, **self._extras())
+        self._launch(grad_scale, srcs)
         self._keepalive = srcs
         self._end(rng)
 
@@ -327,23 +332,12 @@ class FlatRMSProp(FlatAdam):
         rate 0, as in a graph capture's warm-up, still clips)."""
         return [self.ms, self.state] + ([self.theta] if self.clip > 0 else []) + self._avg_slot()
 
-    def step(self, grad_scale=1.0, rng=None):
-        if self.scaler is not None:
-            K.grads_nonfinite(self.grad, self.scaler.state)
-        K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale, **self._extras())
-        self._end(rng)
-
-    def update(self, grads, grad_scale=1.0, rng=None):
-        if self.grad.device.type != 'cuda' or len(grads) > K.ADAM_PACKED_MAX:
-            self.gather_grads(grads)
-            return self.step(grad_scale, rng)
-        srcs = [g.contiguous() if g is not None else None for g in grads]
-        if self.scaler is not None:
-            K.grads_nonfinite(srcs, self.scaler.state)
-        K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
-                              grad_scale, **self._extras())
-        self._keepalive = srcs
-        self._end(rng)
+    def _launch(self, grad_scale, srcs=None):
+        if srcs is None:
+            K.rmsprop_step(self.theta, self.grad, self.ms, self.state, self.rho, self.eps, self.clip, grad_scale, **self._extras())
+        else:
+            K.rmsprop_step_packed(srcs, self.offsets, self.sizes, self.grad, self.theta, self.ms, self.state, self.rho, self.eps, self.clip,
+                                  grad_scale, **self._extras())
 
     def load_named_slots(self, ms_by_name, t):
         off = 0

@@ -655,84 +655,69 @@ int ctgan_accuracy2(const float* logits, const int32_t* labels, int32_t B, int32
  *      ctgan_adam_advance multiplies the powers after all buckets of a step are applied.  An element whose scaled gradient is not
  *      finite (NaN / inf: an overflow of the fp16 matrix-core mode, a degenerate input) keeps its weight and slots unchanged - one
  *      inf would otherwise poison m, v and theta for good, also at lr = 0 (build-only safeguard; TF would propagate it) - and
- *      state[3] is incremented by one per skipped element (float accumulator, exact to 2^24), so the caller can see it. ------ */
-int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state,
-                    float beta1, float beta2, float eps, float grad_scale, ctgan_stream_t stream);
+ *      state[3] is incremented by one per skipped element (float accumulator, exact to 2^24), so the caller can see it.
+ *
+ *      Every update entry point (ctgan_adam_step, ctgan_rmsprop_step and their _packed forms) takes two optional operands, both
+ *      build-only (NOT in the reference) and both fused into the one launch; all argument rules are checked before any launch.
+ *      avg, avg_rate - generator weight averaging (Yazici et al. 2019).  avg == NULL with avg_rate == 0: no average.  avg != NULL with
+ *        avg_rate in (0, 1]: after the update - after the clip, and also for an element whose non-finite gradient was skipped -
+ *        avg = avg + avg_rate * (theta - avg), two fp32 roundings, identical in the plain and the packed form; theta, the slots, the
+ *        bucket and state come out bit-identical to the call without it.  avg == NULL with any other rate, or avg != NULL with a rate
+ *        outside (0, 1] (NaN included): CTGAN_E_BADARG.  The packed forms also want a non-NULL avg 16-byte aligned (CTGAN_E_UNSUPPORTED).
+ *      scaler - the dynamic loss scale of the fp16 matrix-core mode, device float[4] {S, found, good, skipped} (see
+ *        ctgan_grads_nonfinite below).  NULL: none.  Otherwise grad_scale / scaler[0] stands for grad_scale - exact, S being a power of
+ *        two: bit-identical to the call without a scaler given that quotient - and, when scaler[1] != 0, the WHOLE update is dropped:
+ *        no theta, m, v, ms changes (the RMSProp clip still clips, the average still moves towards the weights as they are, the packed
+ *        forms still write the bucket) and state[3] does not count its elements.  The per-element skip stays in place on the steps
+ *        that are applied.                                                                                                    ------ */
+int ctgan_adam_step(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
+                    float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
 int ctgan_adam_advance(float* state, float beta1, float beta2, ctgan_stream_t stream);
 /* tf.train.RMSPropOptimizer (decay rho, momentum 0, not centered) on a flat buffer, with an optional fused weight clip
  * (TF/CT_gan_mnist.py:134-143, TF/CT_gan_64x64.py:548-558):  ms += (g^2 - ms) (1 - rho);  theta = clip(theta - lr g / sqrt(ms + eps))
  * with g = grad * grad_scale, lr = state[0] (graph-replay safe), clip(x) = min(max(x, -clip), clip) when clip > 0 (no clip otherwise).
  * TF creates the ms slot at ONES: the caller initialises it so.  A non-finite scaled gradient leaves the element's ms unchanged and its
- * weight only clipped, and adds one to state[3], as ctgan_adam_step.  The packed form = ctgan_pack + the update in one launch
- * (n_tensors <= 64, 16-byte aligned flat buffers), bit-identical to ctgan_pack + ctgan_rmsprop_step.                              */
+ * weight only clipped, and adds one to state[3], as ctgan_adam_step.  avg, avg_rate, scaler: as ctgan_adam_step.  The packed form =
+ * ctgan_pack + the update in one launch (n_tensors <= 64, 16-byte aligned flat buffers), bit-identical to ctgan_pack +
+ * ctgan_rmsprop_step.                                                                                                             */
 int ctgan_rmsprop_step(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                       float grad_scale, ctgan_stream_t stream);
+                       float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
 int ctgan_rmsprop_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                              ctgan_stream_t stream);
-/* End of a step in one launch: ctgan_adam_advance(state) and, with rng_ctr != NULL, ctgan_rng_advance(rng_ctr, rng_by).            */
-int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, ctgan_stream_t stream);
+                              float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale, float* avg,
+                              float avg_rate, const float* scaler, ctgan_stream_t stream);
+/* End of a step in one launch.  scaler == NULL (growth_interval, min_scale, max_scale ignored): ctgan_adam_advance(state) and, with
+ * rng_ctr != NULL, ctgan_rng_advance(rng_ctr, rng_by).  scaler != NULL, the end of a step under the dynamic loss scale - applied
+ * (scaler[1] == 0): the beta powers advance, good += 1, and at growth_interval in a row S = min(2 S, max_scale), good = 0; dropped: the
+ * beta powers stay, S = max(S / 2, min_scale), good = 0, skipped += 1; either way found = 0 and rng_ctr advances.  Then
+ * growth_interval >= 1 and min_scale <= max_scale, both powers of two (CTGAN_E_BADARG otherwise).                                 */
+int ctgan_step_advance(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler, int64_t growth_interval,
+                       float min_scale, float max_scale, ctgan_stream_t stream);
 /* ctgan_pack + ctgan_adam_step in one launch (n_tensors <= 64, 16-byte aligned flat buffers; CTGAN_E_UNSUPPORTED otherwise):
  * compute_gradients' bucket and apply_gradients (TF/CT_gan_cifar_resnet.py:335-338) of a single-rank step.  flat receives the
  * packed gradients as ctgan_pack writes them; theta/m/v are updated with bit-identical arithmetic to the two-launch form.        */
 int ctgan_adam_step_packed(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                           float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                           ctgan_stream_t stream);
+                           float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale, float* avg,
+                           float avg_rate, const float* scaler, ctgan_stream_t stream);
 /* flat[dst_offs[i] : dst_offs[i] + counts[i]] = srcs[i][0:counts[i]] (srcs[i] == NULL: zeros), i < n_tensors, in one
  * launch per 64 tensors.  The three arrays are HOST arrays (the pointers are device pointers); they are passed to
  * the kernel by value, so the call is hipGraph-capture safe.  This is the gradient bucket of compute_gradients
  * (TF/CT_gan_cifar_resnet.py:335-336) without one copy per variable.                                   */
 int ctgan_pack(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
                float* flat, ctgan_stream_t stream);
-/* Generator weight averaging (build-only: NOT in the reference; Yazici et al. 2019).  The four update entry points above with the
- * average fused into the same launch: after the update - after the clip, and also for an element whose non-finite gradient was
- * skipped - avg = avg + avg_rate * (theta - avg), two fp32 roundings, identical in the plain and the packed form.  theta, the slots,
- * the bucket and state come out bit-identical to the entry point without the suffix.  avg == NULL or avg_rate outside (0, 1]:
- * CTGAN_E_BADARG; the packed forms also want avg 16-byte aligned (CTGAN_E_UNSUPPORTED).                                              */
-int ctgan_adam_step_avg(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
-                        float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
-int ctgan_adam_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                               float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                               float* avg, float avg_rate, ctgan_stream_t stream);
-int ctgan_rmsprop_step_avg(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                           float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
-int ctgan_rmsprop_step_packed_avg(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                                  float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip,
-                                  float grad_scale, float* avg, float avg_rate, ctgan_stream_t stream);
 /* Swap the contents of two disjoint fp32 buffers of n elements in one launch (16-byte accesses when both pointers are 16-byte
  * aligned, with the n % 4 last elements one by one; element by element otherwise; n == 0: nothing is launched; overlapping
  * buffers: CTGAN_E_BADARG): the weights and their average change places without either address changing.                         */
 int ctgan_exchange(float* a, float* b, int64_t n, ctgan_stream_t stream);
-/* Dynamic loss scale of the fp16 matrix-core mode, kept on the device (build-only: NOT in the reference).  scaler = device float[4]
- * {S, found, good, skipped}: S the power-of-two scale the step's backward is seeded with (the caller reads scaler[0] as the seed),
- * found != 0 once this step's gradients held a NaN / inf, good = updates applied in a row since S last changed, skipped = updates dropped
- * so far (float counts, exact to 2^24).  A step is three launches - scan, update, end of step - all stream-ordered, none reads the host:
- *   ctgan_grads_nonfinite: scaler[1] = 1 if any element of the n_tensors (<= 64) sources is NaN or +-inf (raw bits: +-FLT_MAX, denormals
- *     and -0 are finite); a NULL source is all zeros.  One source = the flat bucket after the all-reduce.  16-byte loads between a
- *     source's first and last 16-byte boundary.  ctgan_grads_nonfinite_blocks: grid.x of that launch (its workgroups hold 256 threads,
- *     each reads one 16-byte item per trip; grid.y = n_tensors), for the largest count and the number of sources.
- *   ctgan_*_step*_scaled: the update entry points above (avg == NULL: without the weight average) with grad_scale / scaler[0] for
- *     grad_scale - exact, S being a power of two: bit-identical to the static entry point called with that quotient - and, when
- *     scaler[1] != 0, the WHOLE update dropped: no theta, m, v, ms changes (the RMSProp clip still clips, the average still moves towards
- *     the weights as they are, the packed forms still write the bucket) and state[3] does not count its elements.  The per-element skip
- *     of ctgan_adam_step stays in place on the steps that are applied.
- *   ctgan_step_advance_scaled: ctgan_step_advance for such a step.  Applied: the beta powers advance, good += 1, and at growth_interval
- *     in a row S = min(2 S, max_scale), good = 0.  Dropped: the beta powers stay, S = max(S / 2, min_scale), good = 0, skipped += 1.
- *     Either way found = 0 and rng_ctr advances.  min_scale / max_scale: powers of two, min <= max (CTGAN_E_BADARG otherwise).        */
+/* The scan of the dynamic loss scale.  scaler = device float[4] {S, found, good, skipped}: S the power-of-two scale the step's backward
+ * is seeded with (the caller reads scaler[0] as the seed), found != 0 once this step's gradients held a NaN / inf, good = updates
+ * applied in a row since S last changed, skipped = updates dropped so far (float counts, exact to 2^24).  A step is three launches -
+ * this scan, an update with `scaler`, ctgan_step_advance with `scaler` - all stream-ordered, none reads the host.
+ * ctgan_grads_nonfinite: scaler[1] = 1 if any element of the n_tensors (<= 64) sources is NaN or +-inf (raw bits: +-FLT_MAX, denormals
+ * and -0 are finite); a NULL source is all zeros.  One source = the flat bucket after the all-reduce.  16-byte loads between a
+ * source's first and last 16-byte boundary.  ctgan_grads_nonfinite_blocks: grid.x of that launch (its workgroups hold 256 threads,
+ * each reads one 16-byte item per trip; grid.y = n_tensors), for the largest count and the number of sources.                         */
 unsigned ctgan_grads_nonfinite_blocks(int64_t max_count, int32_t n_tensors);
 int ctgan_grads_nonfinite(const float* const* srcs, const int64_t* counts, int32_t n_tensors, float* scaler, ctgan_stream_t stream);
-int ctgan_adam_step_scaled(float* theta, const float* g, float* m, float* v, int64_t n, float* state, float beta1, float beta2, float eps,
-                           float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
-int ctgan_adam_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors, float* flat,
-                                  float* theta, float* m, float* v, float* state, float beta1, float beta2, float eps, float grad_scale,
-                                  float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
-int ctgan_rmsprop_step_scaled(float* theta, const float* g, float* ms, int64_t n, float* state, float rho, float eps, float clip,
-                              float grad_scale, float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
-int ctgan_rmsprop_step_packed_scaled(const float* const* srcs, const int64_t* dst_offs, const int64_t* counts, int32_t n_tensors,
-                                     float* flat, float* theta, float* ms, float* state, float rho, float eps, float clip, float grad_scale,
-                                     float* avg, float avg_rate, const float* scaler, ctgan_stream_t stream);
-int ctgan_step_advance_scaled(float* state, float beta1, float beta2, uint64_t* rng_ctr, uint64_t rng_by, float* scaler,
-                              int64_t growth_interval, float min_scale, float max_scale, ctgan_stream_t stream);
 
 /* ---- RNG: Philox4x32-10 counter-based streams (tf.random_uniform / tf.random_normal /
  *      dropout masks :157,202,277,319).  counter base is read from device memory

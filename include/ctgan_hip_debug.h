@@ -50,9 +50,9 @@ void ctgan_debug_x3_halo_always(int on);
    SIDE stream next to a measured launch, out[0..3] = real0, shader0, real1, shader1 give the shader clock sustained over that launch
    (d shader / d real x 100 MHz); out[4] = 1 when the flag ended the wait.  `out`: five uint64 in device memory. */
 int ctgan_debug_clock_probe(const int* flag, uint64_t max_real_ticks, uint64_t* out, void* stream);
-/* tests only: how many launches of one kind the optimizer entry points (csrc/optim_rng.hip) have made in this process - kind 0: a static
-   update (ctgan_adam_step / ctgan_rmsprop_step and their _packed / _avg forms), 1: ctgan_step_advance, 2: ctgan_grads_nonfinite, 3: a
-   _scaled update, 4: ctgan_step_advance_scaled.  A run without a dynamic loss scale moves kinds 0 and 1 only.  Any other kind: 0. */
+/* tests only: how many launches of one kind the optimizer entry points (csrc/optim_rng.hip) have made in this process - kind 0: an
+   update (ctgan_adam_step / ctgan_rmsprop_step and their _packed forms) with scaler == NULL, 1: ctgan_step_advance with scaler == NULL,
+   2: ctgan_grads_nonfinite, 3: an update with a scaler, 4: ctgan_step_advance with a scaler.  A run without a dynamic loss scale moves kinds 0 and 1 only.  Any other kind: 0. */
 uint64_t ctgan_debug_optim_launches(int kind);
 
 #ifdef __cplusplus

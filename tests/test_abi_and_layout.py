@@ -53,10 +53,16 @@ def test_removed_step_variants_stay_removed():
 
 def test_forwarding_twins_stay_removed():
     """One C entry per operation: the nine entry points that only forwarded to a wider sibling (or differed from it in one flag) are gone from
-    the ctypes table and from the library's exports; the un-suffixed name carries the wider signature."""
+    the ctypes table and from the library's exports; the un-suffixed name carries the wider signature.  The same for the optimizer's nine:
+    the weight average and the loss scaler are optional operands of the five un-suffixed entries."""
     from ctgan_amd import _lib
     twins = ('ctgan_conv2d_fwd_ex', 'ctgan_conv2d_dgrad_ex', 'ctgan_conv2d16_fwd_ex', 'ctgan_conv2d16_dgrad_ex', 'ctgan_conv2d16_wgrad_bias',
              'ctgan_conv2d_wgrad_group_ex', 'ctgan_tail_critic_heads_fwd2', 'ctgan_tail_heads_bwd_gp', 'ctgan_gp_head_wgrad_acc')
+    twins += tuple('ctgan_%s_step%s%s' % (o, p, s) for o in ('adam', 'rmsprop') for p in ('', '_packed') for s in ('_avg', '_scaled'))
+    twins += ('ctgan_step_advance_scaled',)
+    assert len(twins) == 18
+    assert len(_lib.SIGNATURES['ctgan_adam_step'][1]) == 11 + 3           # + avg, avg_rate, scaler
+    assert len(_lib.SIGNATURES['ctgan_step_advance'][1]) == 10
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in twins:
         assert name not in _lib.SIGNATURES, name
@@ -80,6 +86,40 @@ def test_error_reporting_without_gpu():
     assert rc == -1 and b'keep' in _lib.lib.ctgan_last_error()
     rc = _lib.lib.ctgan_conv2d_fwd(None, None, None, None, None, None, 0, None, None)
     assert rc == -1
+
+
+def test_optimizer_entries_refuse_bad_optional_operands_without_gpu():
+    """The rules of the two optional operands of the update entries (avg + avg_rate, scaler) and of ctgan_step_advance's scale constants,
+    all checked ahead of any launch: every call here is refused, none reaches the device.  Host addresses stand in for device pointers."""
+    from ctgan_amd._lib import lib
+    nan = float('nan')
+    buf = (ctypes.c_float * 32)()
+    base = (ctypes.addressof(buf) + 15) & ~15                      # 16-byte aligned, 16 floats behind it
+    x, odd = ctypes.c_void_p(base), ctypes.c_void_p(base + 4)      # odd: 4 bytes past a 16-byte boundary
+    n = 8
+    P, O, C = (ctypes.c_void_p * 1)(base), (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(n)
+    entries = {         # name -> (arguments ahead of avg, packed?)
+        'adam_step': ((x, x, x, x, n, x, 0.5, 0.9, 1e-8, 1.0), False),
+        'adam_step_packed': ((P, O, C, 1, x, x, x, x, x, 0.5, 0.9, 1e-8, 1.0), True),
+        'rmsprop_step': ((x, x, x, n, x, 0.9, 1e-10, 0.0, 1.0), False),
+        'rmsprop_step_packed': ((P, O, C, 1, x, x, x, x, 0.9, 1e-10, 0.0, 1.0), True),
+    }
+    for name, (head, packed) in entries.items():
+        fn = getattr(lib, 'ctgan_' + name)
+        for scaler in (None, x):
+            # no average wants a rate of exactly 0 (with a scaler too: the rate used to be ignored there); an average a rate in (0, 1]
+            for avg, rate in ((None, 0.5), (None, -0.5), (None, 1.5), (None, nan), (x, 0.0), (x, -0.5), (x, 1.5), (x, nan)):
+                assert fn(*head, avg, rate, scaler, None) == -1, (name, avg, rate, scaler)
+                err = lib.ctgan_last_error()
+                assert b'avg' in err and name.encode() + b':' in err, err
+            if packed:
+                assert fn(*head, odd, 0.5, scaler, None) == -2, (name, scaler)
+                assert name.encode() + b':' in lib.ctgan_last_error()
+    for consts in ((0, 1.0, 65536.0), (-1, 1.0, 65536.0), (2000, 3.0, 65536.0), (2000, 1.0, 3.0), (2000, 4.0, 2.0), (2000, 0.0, 2.0),
+                   (2000, nan, 2.0), (2000, 1.0, float('inf'))):
+        assert lib.ctgan_step_advance(x, 0.5, 0.9, None, 1, x, *consts, None) == -1, consts
+        assert b'step_advance:' in lib.ctgan_last_error()
+    assert lib.ctgan_step_advance(None, 0.5, 0.9, None, 1, None, 0, 0.0, 0.0, None) == -1
 
 
 def test_product_never_imports_the_oracle():

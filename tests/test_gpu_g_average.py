@@ -1,4 +1,4 @@
-"""The generator's weight average on the MI355X (`-m gpu`): the `_avg` forms of the four update launches and ctgan_exchange
+"""The generator's weight average on the MI355X (`-m gpu`): the `avg` operand of the four update launches and ctgan_exchange
 (csrc/optim_rng.hip), the trainers' `g_average` / `averaged()` under graph replay, checkpoint resume, and the `averaged` flag of the
 scoring.  Not in the reference, so every check is the feature's own contract and every comparison is bit for bit:
   * theta, the slots, the bucket and the skip count of an averaging launch equal the launch without the average (the same code);
@@ -130,15 +130,15 @@ def test_update_kernels_refuse_bad_average_arguments_and_launch_nothing(K):
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
     P, Of, C = (ctypes.c_void_p * 1)(g.data_ptr()), (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(n)
     for avg, rate in ((None, 0.5), (a, 0.0), (a, -0.5), (a, 1.5), (a, float('nan'))):
-        assert lib.ctgan_adam_step_avg(p(th), p(g), p(m), p(v), n, p(state), 0.5, 0.9, 1e-8, 1.0, p(avg), rate, None) == -1
+        assert lib.ctgan_adam_step(p(th), p(g), p(m), p(v), n, p(state), 0.5, 0.9, 1e-8, 1.0, p(avg), rate, None, None) == -1
         assert b'avg' in lib.ctgan_last_error()
-        assert lib.ctgan_rmsprop_step_avg(p(th), p(g), p(m), n, p(state), 0.9, 1e-10, 0.0, 1.0, p(avg), rate, None) == -1
-        assert lib.ctgan_adam_step_packed_avg(P, Of, C, 1, p(flat), p(th), p(m), p(v), p(state), 0.5, 0.9, 1e-8, 1.0, p(avg), rate, None) == -1
-        assert lib.ctgan_rmsprop_step_packed_avg(P, Of, C, 1, p(flat), p(th), p(m), p(state), 0.9, 1e-10, 0.0, 1.0, p(avg), rate, None) == -1
+        assert lib.ctgan_rmsprop_step(p(th), p(g), p(m), n, p(state), 0.9, 1e-10, 0.0, 1.0, p(avg), rate, None, None) == -1
+        assert lib.ctgan_adam_step_packed(P, Of, C, 1, p(flat), p(th), p(m), p(v), p(state), 0.5, 0.9, 1e-8, 1.0, p(avg), rate, None, None) == -1
+        assert lib.ctgan_rmsprop_step_packed(P, Of, C, 1, p(flat), p(th), p(m), p(state), 0.9, 1e-10, 0.0, 1.0, p(avg), rate, None, None) == -1
     big = torch.full((n + 1,), 3.0, device='cuda')
     odd = big[1:]                                                                    # 4 bytes past a 16-byte boundary
-    assert lib.ctgan_adam_step_packed_avg(P, Of, C, 1, p(flat), p(th), p(m), p(v), p(state), 0.5, 0.9, 1e-8, 1.0, p(odd), 0.5, None) == -2
-    assert lib.ctgan_rmsprop_step_packed_avg(P, Of, C, 1, p(flat), p(th), p(m), p(state), 0.9, 1e-10, 0.0, 1.0, p(odd), 0.5, None) == -2
+    assert lib.ctgan_adam_step_packed(P, Of, C, 1, p(flat), p(th), p(m), p(v), p(state), 0.5, 0.9, 1e-8, 1.0, p(odd), 0.5, None, None) == -2
+    assert lib.ctgan_rmsprop_step_packed(P, Of, C, 1, p(flat), p(th), p(m), p(state), 0.9, 1e-10, 0.0, 1.0, p(odd), 0.5, None, None) == -2
     torch.cuda.synchronize()
     for t, x in ((th, 1.0), (m, 0.0), (v, 0.0), (a, 3.0), (flat, 0.0), (big, 3.0)):
         assert torch.equal(t, torch.full_like(t, x))
