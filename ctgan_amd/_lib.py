@@ -85,6 +85,7 @@ DEBUG_SIGNATURES = {
     'ctgan_debug_x3_halo_always': (None, [c_int]),
     'ctgan_debug_clock_probe': (c_int, [c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
     'ctgan_debug_optim_launches': (c_uint64, [c_int]),
+    'ctgan_debug_spectral_launches': (c_int, [c_int]),
 }
 
 # name -> (restype, argtypes); the single source the symbol-export test checks against include/ctgan_hip.h
@@ -290,6 +291,13 @@ SIGNATURES = {
     'ctgan_segment_sums': (c_int, [_p, _p, c_int32, _p, _p]),
     # differentiable augmentation of the critic's inputs, forward and adjoint (csrc/diffaug.hip)
     'ctgan_diffaug': (c_int, [_p, _p, c_float, _p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_int32, c_uint64, c_uint64, _p, _p, _p]),
+    # spectral normalisation of the weight matrices of a flat bucket (csrc/spectral.hip)
+    'ctgan_spectral_max_n': (c_int, []),
+    'ctgan_spectral_table_words': (c_int64, [c_int32]),
+    'ctgan_spectral_table_fill': (c_int, [POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int32, c_int64, POINTER(c_int64)]),
+    'ctgan_spectral_scratch_bytes': (c_size_t, [POINTER(c_int64)]),
+    'ctgan_spectral_normalize': (c_int, [_p, _p, c_int64, _p, c_int32, c_int64, _p, _p, _p, _p, c_int32, _p, _p]),
+    'ctgan_spectral_grad': (c_int, [_p, _p, _p, c_int32, c_int64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 

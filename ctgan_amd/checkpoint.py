@@ -8,7 +8,10 @@ continuation (tests/test_gpu_checkpoint.py).  The `rng` entry also holds the ste
 `eval_ctr`), so that a resumed run logs the dev costs of the uninterrupted one; a file written before that entry existed loads with the
 counter at 0.  A trainer with a dynamic loss scale (DCGANTrainer(loss_scale='dynamic')) adds the entry `loss_scaler` - the scale and its
 two counts; a run without one writes the keys it always wrote.  A file without the entry starts a dynamic trainer at its init_scale; a
-file with it loads into a trainer with a fixed scale, which ignores it."""
+file with it loads into a trainer with a fixed scale, which ignores it.  A trainer with spectral normalisation (`spectral_norm=True`) keeps
+`u`, `v`, `sigma` in the entry `spectral` of its critic optimizer's state; `params` hold the RAW weights under their usual names, and
+`d_opt.load_state_dict` - which runs after the parameters are restored - recomputes the normalised weights from the saved sigma without
+iterating.  A file without the entry starts such a trainer from its constructor's `u` with one iteration; a plain trainer ignores the entry."""
 import torch
 
 from . import tflib as lib

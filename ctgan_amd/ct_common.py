@@ -93,13 +93,14 @@ class SSLTrainerBase:
         """fn() without gradients; averaged: with every trained classifier parameter replaced by its average (`givens`) - a
         parameter that is not trained has no average and stays live."""
         if averaged:
-            lib.alias_params({p: a for p, (_, a) in zip(self.d_opt.params, self.d_opt.avg_views())})
+            own = {p: a for p, (_, a) in zip(self.d_opt.params, self.d_opt.avg_views())}
+            lib.alias_params(own)
         try:
             with torch.no_grad():
                 return fn()
         finally:
             if averaged:
-                lib.delete_param_aliases()
+                lib.delete_param_aliases(own)        # its own entries only: another owner's aliases stay installed
 
     # ---- what train_loop asks of a trainer beside the steps: nothing, except with temporal ensembling
     def end_epoch(self):

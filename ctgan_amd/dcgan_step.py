@@ -23,7 +23,7 @@ import torch
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
-from .optim import FlatAdam, FlatRMSProp, LossScaler
+from .optim import FlatAdam, FlatRMSProp, LossScaler, SpectralNorm
 from .optim import averaged as averaged_weights
 from .rng import AUG_FAKE, AUG_GEN, AUG_REAL, DeviceRNG
 
@@ -76,7 +76,8 @@ def mode_of(module):
 
 
 class DCGANTrainer:
-    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, loss_scale=None):
+    def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, loss_scale=None,
+                 spectral_norm=False):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
         real_prep, feat_shapes).  g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights,
         moved inside its update launch (optim.FlatAdam / FlatRMSProp avg_rate), whatever the mode's optimizer.  It is the RATE, 1 - decay:
@@ -89,7 +90,11 @@ class DCGANTrainer:
         moves, there is no state to checkpoint.  loss_scale (NOT in the reference; for kernels.set_mma_dtype('f16')): None - the
         module's LOSS_SCALE, or 1, as before; a float - that fixed power-of-two scale; 'dynamic' or an optim.LossScaler - a dynamic scale
         kept on the device (`scaler`; both optimizers share it): the backward is seeded with it, an update whose gradients hold a NaN /
-        inf is dropped as a whole and halves it, growth_interval applied updates in a row double it."""
+        inf is dropped as a whole and halves it, growth_interval applied updates in a row double it.  spectral_norm (NOT in
+        the reference; Miyato et al. 2018): the critic reads every conv filter and Linear weight divided by its spectral norm,
+        one power iteration per critic update (optim.SpectralNorm: `spectral`); the registry, the optimizer and the checkpoints keep the
+        raw weights, `d_params` and a step's out['grads'] are the normalised weights and the gradients with respect to them (the raw
+        weights' are in d_opt.grad).  ValueError under MODE 'wgan', whose weight clip answers the same question.  False: nothing differs."""
         self.mod = module
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape_of(module) if self.aug_policy else None
@@ -100,6 +105,8 @@ class DCGANTrainer:
         self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
         self.mode = mode_of(module)
         self.disc_iters = self.mode.critic_iters or module.cfg.CRITIC_ITERS     # critic steps per iteration
+        if spectral_norm and self.mode.clip:
+            raise ValueError('spectral_norm: not with the weight clip of MODE %r (two answers to one question: use one)' % (module.cfg.MODE,))
         # Power-of-two loss scale for the fp16 matrix-core mode (kernels.set_mma_dtype('f16')): the backward passes are linear in the
         # seed, so the cost gradient is seeded with S instead of 1 - every first-order gradient TENSOR the fp16 kernels round is S
         # times larger, away from fp16's subnormals (per-pixel gradients shrink with 1 / (B H W)) - and Adam divides it out again
@@ -125,6 +132,11 @@ class DCGANTrainer:
         self.iteration = 0
         self.d_params = [p for _, p in self.d_named]
         self.g_params = [p for _, p in self.g_named]
+        self.spectral = None
+        if spectral_norm:
+            self.spectral = SpectralNorm(self.d_named, self.d_opt)
+            self.spectral.install()            # (until detach_spectral() or lib.delete_all_params(): the registry reads theta_bar)
+            self.d_params = [v for _, v in self.spectral.views()]
         if self.scaler is not None:
             self._loss_scale = 1.0
         else:
@@ -142,6 +154,15 @@ class DCGANTrainer:
         if self.scaler is not None:
             raise AttributeError('loss_scale cannot be assigned on a trainer with a dynamic loss scale (it lives in trainer.scaler)')
         self._loss_scale = float(value)
+
+    def detach_spectral(self):
+        """Give the registry back (a trainer built with spectral_norm=True owns its alias table until this or lib.delete_all_params()):
+        the critic reads the raw weights again, d_params are the raw parameters, d_opt steps without the normalisation.  Not under graph
+        replay: captured graphs keep reading the normalised copy."""
+        if self.spectral is not None:
+            self.spectral.remove()
+            self.spectral = None
+            self.d_params = [p for _, p in self.d_named]
 
     def averaged(self):
         """Context manager: inside it the generator's parameters hold their weight average (optim.averaged; ValueError when the
@@ -386,7 +407,8 @@ def sample_grid(module, noise, trainer=None, averaged=False):
 
 
 def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
-          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None, loss_scale=None):
+          checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None, loss_scale=None,
+          spectral_norm=False):
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
@@ -396,7 +418,9 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  `augment` (NOT in the reference; DCGANTrainer):
     a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps; the dev cost, the sample
     grids and the scores stay un-augmented.  `loss_scale` (NOT in the reference; DCGANTrainer): None, a fixed scale, or 'dynamic' / an
-    optim.LossScaler - then the series `loss_scale` and `skipped_steps` are added at every flush.  Returns the trainer."""
+    optim.LossScaler - then the series `loss_scale` and `skipped_steps` are added at every flush.  `spectral_norm` (NOT in the reference;
+    DCGANTrainer): the critic's weights are spectrally normalised - then the series `sn_sigma_max` and `sn_sigma_min` are added at every
+    flush.  Returns the trainer."""
     import os
     import time
 
@@ -407,7 +431,7 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     cfg = module.cfg
     iters = cfg.ITERS if iters is None else iters
     build_params(module)
-    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment, loss_scale=loss_scale)
+    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment, loss_scale=loss_scale, spectral_norm=spectral_norm)
     start = checkpoint.load(resume, trainer) if resume else 0
     first = next_batch()
     eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)
@@ -443,6 +467,10 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
             if trainer.scaler is not None:
                 series.add('loss_scale', trainer.scaler.scale())
                 series.add('skipped_steps', trainer.scaler.skipped_steps())
+            if trainer.spectral is not None:
+                sig = trainer.spectral.sigmas().values()
+                series.add('sn_sigma_max', max(sig))
+                series.add('sn_sigma_min', min(sig))
             series.flush()
         series.tick()
     return trainer

@@ -22,7 +22,7 @@ import torch
 from . import functional as F
 from . import kernels as K
 from . import tflib as lib
-from .optim import FlatAdam
+from .optim import FlatAdam, SpectralNorm
 from .optim import averaged as averaged_weights
 from .rng import AUG_FAKE, AUG_GEN, AUG_REAL, DeviceRNG
 from .tflib.ops import batchnorm as _bn
@@ -495,7 +495,7 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
 class Trainer:
     """Owns the optimizers, the random streams and the D/G step (the session of the reference)."""
 
-    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None):
+    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, spectral_norm=False):
         """g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights, moved inside its update
         launch (optim.FlatAdam avg_rate).  It is the RATE, 1 - decay: g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it.
         The critic is never averaged.  0 (default): nothing differs from a trainer built without the argument.
@@ -503,7 +503,12 @@ class Trainer:
         'color,translation,cutout'; None / '': off, nothing differs.  The random transformation T (kernels.diffaug) is applied to the
         dequantised reals and to the fakes in front of the critic in the critic step - before the interpolation - and to the samples of
         both towers in the generator step, whose gradient flows back through T.  Its draws come from three reserved streams
-        (rng.AUG_REAL / AUG_FAKE / AUG_GEN) at the trainer's own counter: no other draw moves, there is nothing to checkpoint."""
+        (rng.AUG_REAL / AUG_FAKE / AUG_GEN) at the trainer's own counter: no other draw moves, there is nothing to checkpoint.
+        spectral_norm (NOT in the reference; Miyato et al. 2018): the critic reads every conv filter and Linear weight - the
+        projection table too - divided by its spectral norm, estimated by one power iteration per critic update (optim.SpectralNorm:
+        `spectral`).  The registry, the optimizer and the checkpoints keep the raw weights; lib.param gives the normalised ones through
+        the alias table, `d_params` are those, and a step's out['grads'] are gradients with respect to them (the raw weights' are in
+        d_opt.grad).  False (default): nothing differs from a trainer built without the argument."""
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape()
         self.dev = lib._dev()
@@ -517,6 +522,11 @@ class Trainer:
         self.g_opt = FlatAdam(self.g_named, 0.0, 0.9, state=self._opt_state[4:8], avg_rate=g_average)
         self.d_params = [p for _, p in self.d_named]
         self.g_params = [p for _, p in self.g_named]
+        self.spectral = None
+        if spectral_norm:
+            self.spectral = SpectralNorm(self.d_named, self.d_opt)
+            self.spectral.install()            # (until detach_spectral() or lib.delete_all_params(): the registry reads theta_bar)
+            self.d_params = [v for _, v in self.spectral.views()]
         self._one = None
         # Batch-sharded steps: hand the critic's gradient bucket to the all-reduce in two parts - blocks 1-2 (a prefix of the flat bucket)
         # as soon as the hand-scheduled step has completed them, under the rest of the penalty's double backward (north star: "all-reduce
@@ -818,6 +828,15 @@ class Trainer:
             out = self.d_step(data, labels, iteration=iteration, fake=fakes[i])
         return out
 
+    def detach_spectral(self):
+        """Give the registry back (a trainer built with spectral_norm=True owns its alias table until this or lib.delete_all_params()):
+        the critic reads the raw weights again, d_params are the raw parameters, d_opt steps without the normalisation.  Not under graph
+        replay: captured graphs keep reading the normalised copy."""
+        if self.spectral is not None:
+            self.spectral.remove()
+            self.spectral = None
+            self.d_params = [p for _, p in self.d_named]
+
     def averaged(self):
         """Context manager: inside it the generator's parameters hold their weight average (optim.averaged; ValueError when the
         trainer was built with g_average = 0).  Sample and score inside; do not train inside."""
@@ -832,7 +851,8 @@ class Trainer:
 
 
 def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100,
-          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0, augment=None):
+          checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0, augment=None,
+          spectral_norm=False):
     """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434): CIFAR-10 generator factories, `time` /
     `cost` / `wgan` / `acgan` / `acc_real` / `acc_fake` series (train_log.Series), fixed-noise sample grids every
     `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
@@ -842,7 +862,9 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     manifold (evaluate.record_score).  `g_average` > 0 (NOT in the reference; Trainer): the generator's weight average is kept, scored
     after the live generator under the same series names + `_avg`, and sampled into `samples_%d_avg.png`.  `augment` (NOT in the
     reference; Trainer): a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps;
-    the dev cost, the sample grids and the scores stay un-augmented."""
+    the dev cost, the sample grids and the scores stay un-augmented.  `spectral_norm` (NOT in the reference; Trainer): the critic's weights
+    are spectrally normalised; the series `sn_sigma_max` / `sn_sigma_min` - the largest and smallest estimated spectral norm of its
+    layers - are added whenever the series are flushed."""
     import os
     import time
 
@@ -852,7 +874,7 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     from .train_log import Series
     iters = cfg.ITERS if iters is None else iters
     build_params()
-    trainer = Trainer(seed=seed, g_average=g_average, augment=augment)
+    trainer = Trainer(seed=seed, g_average=g_average, augment=augment, spectral_norm=spectral_norm)
     start = checkpoint.load(resume, trainer) if resume else 0
     eng = GraphedTrainer(trainer, use_graphs=use_graphs)
     ev = evaluate.Evaluator(trainer)
@@ -884,6 +906,10 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
         if checkpoint_every and iteration % checkpoint_every == checkpoint_every - 1:
             checkpoint.save(os.path.join(out_dir, 'checkpoint.pt'), trainer, iteration + 1)
         if iteration < 500 or iteration % 1000 == 999:
+            if trainer.spectral is not None:
+                sig = trainer.spectral.sigmas().values()
+                series.add('sn_sigma_max', max(sig))
+                series.add('sn_sigma_min', min(sig))
             series.flush()
         series.tick()
     return trainer

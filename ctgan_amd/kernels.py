@@ -2031,6 +2031,84 @@ def pack(srcs, dst_offs, counts, flat):
     check(lib.ctgan_pack(P, O, C, n, _ptr(flat), _stream()), 'pack')
 
 
+# ------------------------------------------------------------------------------- spectral normalisation (csrc/spectral.hip)
+SPECTRAL_MAX_N = lib.ctgan_spectral_max_n()
+SPECTRAL_EPS = 1e-12
+
+
+def spectral_launches(which):
+    """Launches of one call - 'normalise': spectral_normalize(iterate=True), 'rescale': iterate=False, 'grad': spectral_grad."""
+    return int(lib.ctgan_debug_spectral_launches({'normalise': 0, 'rescale': 1, 'grad': 2}[which]))
+
+
+class SpectralTable:
+    """The job table of a bucket of `total` floats: jobs = [(offset, K, N)], ascending - the matrices M[K, N] that are normalised.  Built
+    ONCE (ctgan_spectral_table_fill: NotImplementedError for an N beyond SPECTRAL_MAX_N, ValueError for jobs that overlap or leave the
+    bucket); `dev` is its device copy (int64), `host` the same words; u_size / v_size the packed lengths of the u and v arrays, u_offs /
+    v_offs each job's offset into them (sigma: the job's index); scratch_floats what spectral_normalize / spectral_grad need."""
+
+    def __init__(self, jobs, total, device):
+        self.jobs = [(int(o), int(k), int(n)) for o, k, n in jobs]
+        self.total = int(total)
+        nj = len(self.jobs)
+        if nj < 1:
+            raise ValueError('SpectralTable: no job')
+        I = ctypes.c_int64 * nj
+        words = int(lib.ctgan_spectral_table_words(nj))
+        host = (ctypes.c_int64 * words)()
+        check(lib.ctgan_spectral_table_fill(I(*[j[0] for j in self.jobs]), I(*[j[1] for j in self.jobs]), I(*[j[2] for j in self.jobs]), nj,
+                                            self.total, host), 'spectral_table_fill')
+        self.host = list(host)
+        self.njobs, self.nslices = nj, int(host[1])
+        self.scratch_floats = int(lib.ctgan_spectral_scratch_bytes(host)) // 4
+        self.u_offs = [self.host[4 + 8 * j + 3] for j in range(nj)]
+        self.v_offs = [self.host[4 + 8 * j + 4] for j in range(nj)]
+        self.u_size = sum(j[2] for j in self.jobs)
+        self.v_size = sum(j[1] for j in self.jobs)
+        self.dev = torch.tensor(self.host, dtype=torch.int64).to(device)
+
+
+def _spectral_state(table, u, v, sigma, scratch):
+    _need_dev(u, v, sigma, scratch)
+    for t, n in ((u, table.u_size), (v, table.v_size), (sigma, table.njobs)):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n
+    assert scratch.is_contiguous() and scratch.dtype == torch.float32 and scratch.numel() >= table.scratch_floats
+    assert table.dev.is_cuda and table.dev.dtype == torch.int64
+
+
+def _check_hold(hold):
+    _need_dev(hold)
+    assert hold.is_contiguous() and hold.dtype == torch.float32 and hold.numel() == 1
+    return _ptr(hold)
+
+
+def spectral_normalize(theta, theta_bar, table, u, v, sigma, scratch, iterate=True, hold=None):
+    """One power iteration per job of `table` and theta_bar = M / max(sigma, 1e-12) inside a job, a copy of theta outside
+    (ctgan_spectral_normalize: three launches); iterate False: theta_bar alone, from the sigma it is given (one launch).  hold (a device
+    float[1] that spectral_grad(..., scaler=, hold=) wrote): when it is set - the update since then was dropped by the loss scaler - the
+    iteration is skipped on the device and u, v, sigma, theta_bar keep their bits."""
+    _need_dev(theta, theta_bar)
+    for t in (theta, theta_bar):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == table.total
+    _spectral_state(table, u, v, sigma, scratch)
+    check(lib.ctgan_spectral_normalize(_ptr(theta), _ptr(theta_bar), table.total, _ptr(table.dev), table.njobs, table.nslices, _ptr(u), _ptr(v),
+                                       _ptr(sigma), _ptr(scratch), 1 if iterate else 0, None if hold is None else _check_hold(hold), _stream()),
+          'spectral_normalize')
+
+
+def spectral_grad(gbar, theta_bar, table, u, v, sigma, scratch, scaler=None, hold=None):
+    """In place over the flat gradient bucket: per job gbar <- (gbar - <gbar, Mbar> v u^T) / max(sigma, 1e-12); the rest is not touched
+    (ctgan_spectral_grad: two launches).  scaler + hold (together or not at all): the state of a dynamic loss scale and a device
+    float[1] that receives its flag scaler[1], for the spectral_normalize after the update."""
+    _need_dev(gbar, theta_bar)
+    for t in (gbar, theta_bar):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == table.total
+    _spectral_state(table, u, v, sigma, scratch)
+    check(lib.ctgan_spectral_grad(_ptr(gbar), _ptr(theta_bar), _ptr(table.dev), table.njobs, table.nslices, _ptr(u), _ptr(v), _ptr(sigma),
+                                  _ptr(scratch), None if scaler is None else _check_scaler(scaler), None if hold is None else _check_hold(hold),
+                                  _stream()), 'spectral_grad')
+
+
 def critic_heads_fwd(d, f, a, labels, B, lam2, M, scale, gp=None):
     """-> (out[5] = cost (incl. gp), wgan, ct, acgan, wgan + ct + gp; ct_i [B]; probs [B,ncls] or None)."""
     _need_dev(d, f, a, labels, gp)

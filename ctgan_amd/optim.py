@@ -92,8 +92,13 @@ class FlatAdam:
         update -> end of step (kernels.grads_nonfinite, then the `scaler=` operand of the other two), one launch more than without; the
         grad_scale they are given is the host's factor only (1 / world), the division by the scale happens on the device.  None: nothing
         differs.  `t` counts ATTEMPTED updates on the host, dropped ones included: with a scaler the beta powers on the device (state[1],
-        state[2]) are what knows how many were applied."""
+        state[2]) are what knows how many were applied.
+        `spectral` (NOT in the reference) is no argument: a SpectralNorm is built FROM the finished optimizer - SpectralNorm(named_params,
+        opt) - and attaches itself (attach_spectral); step() then runs [scan] -> spectral.grad_(grad) -> update -> end of step ->
+        spectral.normalise(), and update() goes through gather_grads + step (the packed update has no bucket to transform).  Without one
+        nothing differs."""
         self.scaler = scaler
+        self.spectral = None
         self.avg_rate = float(avg_rate)
         if not 0.0 <= self.avg_rate <= 1.0:
             raise ValueError('avg_rate must be in [0, 1] (it is the rate 1 - decay, e.g. 1e-4 for a decay of 0.9999): %r' % (avg_rate,))
@@ -133,6 +138,14 @@ class FlatAdam:
         self.t = 0
         self._keepalive = []
         self.offsets = [sum(self.sizes[:i]) for i in range(len(self.sizes))]
+
+    def attach_spectral(self, spectral):
+        """Make `spectral` (a SpectralNorm built over this optimizer; its constructor calls this) part of every step from here on."""
+        if spectral.opt is not self:
+            raise ValueError('attach_spectral: the SpectralNorm was built over another optimizer')
+        if getattr(self, 'clip', 0.0) > 0:
+            raise ValueError('spectral normalisation and weight clipping (clip=%r) are two answers to one question: use one' % self.clip)
+        self.spectral = spectral
 
     def _alloc_slots(self, total, dev):
         self.m = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -182,8 +195,13 @@ class FlatAdam:
         counter (DeviceRNG.end_step)."""
         if self.scaler is not None:
             K.grads_nonfinite(self.grad, self.scaler.state)         # (the bucket after the all-reduce: every rank sees the same bits)
+        if self.spectral is not None:
+            self.spectral.grad_(self.grad, self.scaler)             # gradients w.r.t. the normalised weights -> w.r.t. the raw ones
         self._launch(grad_scale)
         self._end(rng)
+        if self.spectral is not None:
+            # one power iteration per weight version, the last launches of a step; none after an update the loss scaler dropped
+            self.spectral.normalise(held=self.scaler is not None)
 
     def _launch(self, grad_scale, srcs=None):
         """The update launch of a step, the one thing an optimizer on these buffers has of its own: over the bucket, or (srcs) gathering
@@ -214,7 +232,7 @@ class FlatAdam:
     def update(self, grads, grad_scale=1.0, rng=None):
         """gather_grads + step with the bucket and the update in ONE launch: the single-rank form of a step (no collective between
         gather and update)."""
-        if self.grad.device.type != 'cuda' or len(grads) > K.ADAM_PACKED_MAX:
+        if self.grad.device.type != 'cuda' or len(grads) > K.ADAM_PACKED_MAX or self.spectral is not None:
             self.gather_grads(grads)
             return self.step(grad_scale, rng)
         srcs = [g.contiguous() if g is not None else None for g in grads]
@@ -229,6 +247,8 @@ class FlatAdam:
         the clip as a float32 device scalar [1]; nothing crosses to the host (kernels.global_norm / clip_by_norm_)."""
         if self.scaler is not None:
             raise NotImplementedError('update_clipped: not under a dynamic loss scale (the norm would be the scaled gradient\'s)')
+        if self.spectral is not None:
+            raise NotImplementedError('update_clipped: not with spectral normalisation (which gradient the norm is of is undecided)')
         self.gather_grads(grads)
         norm = K.global_norm(self.grad)
         K.clip_by_norm_(self.grad, norm, clip_norm)
@@ -243,11 +263,14 @@ class FlatAdam:
 
     def _avg_slot(self):
         """(and the scaler's state: the tail of every slots() list)"""
-        return ([self.avg] if self._avg_own else []) + ([self.scaler.state] if self.scaler is not None else [])
+        return (([self.avg] if self._avg_own else []) + (self.spectral.slots() if self.spectral is not None else [])
+                + ([self.scaler.state] if self.scaler is not None else []))
 
     def _avg_state(self, sd):
         if self._avg_own:
             sd['avg'] = self.avg.cpu().clone()
+        if self.spectral is not None:
+            sd['spectral'] = self.spectral.state_dict()
         return sd
 
     def _load_avg(self, sd):
@@ -256,6 +279,8 @@ class FlatAdam:
         A state with 'avg' loaded into an optimizer that keeps none ignores it."""
         if self._avg_own:
             self.avg.copy_(sd['avg'] if sd.get('avg') is not None else self.theta)
+        if self.spectral is not None:
+            self.spectral.load_state_dict(sd.get('spectral'))
 
     def load_named_slots(self, m_by_name, v_by_name, t):
         """Overwrite the Adam slots from per-parameter tensors (teacher-forced parity tests, resume)."""
@@ -306,6 +331,112 @@ def averaged(opt):
     finally:
         K.exchange_(opt.theta, opt.avg)
         lib.bump_epoch(opt.group)
+
+
+def spectral_normalised(name):
+    """The name rule of spectral normalisation: conv filters and Linear weights (the projection table `Discriminator.Projection.W`
+    too); not biases, not the scales / offsets / tables of Layernorm and BatchNorm, not moving statistics."""
+    return name.endswith(('.Filters', '.W'))
+
+
+class SpectralNorm:
+    """Spectral normalisation of an optimizer's weight matrices (Miyato et al., ICLR 2018; NOT in the reference).  Every
+    parameter of `opt` whose name ends in `.Filters` or `.W` is read, in its stored layout, as M[K, N] with N the last axis, and keeps
+    u[N], v[K], sigma.  `theta_bar` is laid out like `opt.theta` and holds M / max(sigma, 1e-12) for those and a copy for the rest: it
+    is what the network reads (`views()`, installed with lib.alias_params by the trainer), while the optimizer, the registry and the
+    checkpoints keep the raw weights.  normalise() runs one power iteration (kernels.spectral_normalize) - once here, then as the last
+    launches of every opt.step() - so everything between two updates sees one theta_bar; grad_() turns the gradient with respect to
+    theta_bar into the one with respect to theta, u and v held constant, in place in the flat bucket (kernels.spectral_grad).  u starts
+    from lib.rng_for(name + '.u'): every rank starts, and stays, identical, nothing is communicated."""
+
+    def __init__(self, named_params, opt):
+        if [n for n, _ in named_params] != opt.names:
+            raise ValueError('SpectralNorm: named_params is not the list the optimizer was built from')
+        self.opt = opt
+        self.names = [n for n in opt.names if spectral_normalised(n)]
+        if not self.names:
+            raise ValueError('SpectralNorm: no parameter name ends in .Filters or .W')
+        jobs, u0 = [], []
+        for n, p, o in zip(opt.names, opt.params, opt.offsets):
+            if not spectral_normalised(n):
+                continue
+            N = p.shape[-1] if p.dim() else 1
+            jobs.append((o, p.numel() // N, N))
+            x = lib.rng_for(n + '.u').standard_normal(N)
+            u0.append(torch.from_numpy(x / max(float((x * x).sum()) ** 0.5, 1e-12)).to(torch.float32))
+        dev = opt.theta.device
+        self.table = K.SpectralTable(jobs, opt.theta.numel(), dev)
+        self.theta_bar = torch.empty_like(opt.theta)
+        self.u = torch.cat(u0).to(dev)
+        self._u0 = self.u.clone()
+        self.v = torch.zeros(self.table.v_size, dtype=torch.float32, device=dev)
+        self.sigma = torch.zeros(self.table.njobs, dtype=torch.float32, device=dev)
+        self.scratch = torch.empty(max(self.table.scratch_floats, 1), dtype=torch.float32, device=dev)
+        # under a dynamic loss scale: the flag of the step's gradient scan, kept past the end-of-step launch that clears it (grad_ writes
+        # it, the normalise of the same step reads it; nothing else does, so it is no slot)
+        self.hold = torch.zeros(1, dtype=torch.float32, device=dev) if opt.scaler is not None else None
+        self._views = [(n, torch.nn.Parameter(self.theta_bar[o:o + s].view(p.shape)))
+                       for n, p, o, s in zip(opt.names, opt.params, opt.offsets, opt.sizes)]
+        opt.attach_spectral(self)
+        self.normalise()
+
+    def normalise(self, iterate=True, held=False):
+        """One power iteration and theta_bar (three launches); iterate=False: theta_bar from the sigma held (one launch; after a load).
+        held (opt.step() under a dynamic loss scale): the iteration is skipped ON THE DEVICE when the update since the last grad_(bucket,
+        scaler) was dropped - no new weight version, so u, v, sigma and theta_bar keep their bits."""
+        kw = {'hold': self.hold} if held and self.hold is not None else {}
+        K.spectral_normalize(self.opt.theta, self.theta_bar, self.table, self.u, self.v, self.sigma, self.scratch, iterate=iterate, **kw)
+
+    def grad_(self, bucket, scaler=None):
+        """bucket (laid out like opt.grad) holds dL/d theta_bar; afterwards dL/d theta (two launches).  scaler (a LossScaler, after its
+        scan of the bucket): its flag is also kept for the normalise(held=True) that follows the update."""
+        kw = {'scaler': scaler.state, 'hold': self.hold} if scaler is not None and self.hold is not None else {}
+        K.spectral_grad(bucket, self.theta_bar, self.table, self.u, self.v, self.sigma, self.scratch, **kw)
+
+    def sigmas(self):
+        """name -> sigma as floats.  Reads device memory: outside captured regions, at logging cadence."""
+        return dict(zip(self.names, self.sigma.cpu().tolist()))
+
+    def views(self):
+        """[(name, the parameter's part of theta_bar, shaped like it)] for EVERY parameter of the optimizer, normalised or copied: leaf
+        Parameters that require a gradient, the same objects at every call."""
+        return list(self._views)
+
+    def aliases(self):
+        """{raw parameter: its view of theta_bar}: the argument of lib.alias_params."""
+        return {p: v for p, (_, v) in zip(self.opt.params, self._views)}
+
+    def install(self):
+        """Make the network read theta_bar: the aliases into the registry's table, the network's derived-filter caches stale.  They stay
+        until remove() or lib.delete_all_params(): a trainer built later on the same registry reads theta_bar too until then."""
+        lib.alias_params(self.aliases())
+        lib.bump_epoch(self.opt.group)
+
+    def remove(self):
+        """Undo install() - only this object's aliases - and leave the optimizer: the network reads the raw weights again and the
+        optimizer steps as one built without spectral normalisation."""
+        lib.delete_param_aliases(self.aliases())
+        lib.bump_epoch(self.opt.group)
+        if self.opt.spectral is self:
+            self.opt.spectral = None
+
+    def slots(self):
+        """What a step writes here (a graph capture's warm-up at learning rate 0 still iterates)."""
+        return [self.theta_bar, self.u, self.v, self.sigma]
+
+    def state_dict(self):
+        return {'u': self.u.cpu().clone(), 'v': self.v.cpu().clone(), 'sigma': self.sigma.cpu().clone()}
+
+    def load_state_dict(self, sd):
+        """After the parameters are restored (checkpoint.load: parameters first).  With the saved state theta_bar is recomputed from the
+        saved sigma and nothing iterates - a resumed run has the bits of the uninterrupted one; sd None (a checkpoint of a run without
+        spectral normalisation): one iteration from the constructor's u."""
+        if sd is None:
+            self.u.copy_(self._u0)
+            self.normalise()
+            return
+        self.u.copy_(sd['u']); self.v.copy_(sd['v']); self.sigma.copy_(sd['sigma'])
+        self.normalise(iterate=False)
 
 
 class FlatRMSProp(FlatAdam):
@@ -373,6 +504,9 @@ class FlatAdamTheano(FlatAdam):
         super().__init__(named_params, beta1, beta2, eps, state)
         self.avg_rate = float(avg_rate)
         self.avg = torch.zeros_like(self.theta) if self.avg_rate > 0 else None          # (its own: the base class was given no rate)
+
+    def attach_spectral(self, spectral):
+        raise NotImplementedError('FlatAdamTheano: no spectral normalisation (the classifiers it trains are weight-normalised)')
 
     def step(self, grad_scale=1.0, rng=None):
         assert grad_scale == 1.0

@@ -35,7 +35,12 @@ def epoch(group=None):
 
 
 def group_of(tensor):
-    """Network a registered parameter belongs to (first component of its name); None if not registered."""
+    """Network a registered parameter belongs to (first component of its name); None if not registered.  A tensor that stands in for a
+    parameter through the alias table (averaged or spectrally normalised weights) belongs to that parameter's network."""
+    for old, new in _param_aliases.items():
+        if new is tensor:
+            tensor = old
+            break
     for name, p in _params.items():
         if p is tensor:
             return name.split('.')[0]
@@ -107,6 +112,7 @@ def on_delete_all_params(fn):
 def delete_all_params():
     _params.clear()
     _non_trainable.clear()
+    _param_aliases.clear()            # (keyed by the parameters just forgotten)
     bump_epoch()
     for fn in _delete_hooks:
         fn()
@@ -127,8 +133,13 @@ def alias_params(replace_dict):
         _param_aliases[old] = new
 
 
-def delete_param_aliases():
-    _param_aliases.clear()
+def delete_param_aliases(keys=None):
+    """Empty the alias table; keys: only these entries (a caller that removes what it installed and leaves the others' alone)."""
+    if keys is None:
+        _param_aliases.clear()
+        return
+    for old in keys:
+        _param_aliases.pop(old, None)
 
 
 def state_dict():

@@ -1023,6 +1023,35 @@ int ctgan_diffaug(const float* x, const int32_t* x_int, float denom, float* y, i
                   uint32_t policy, int32_t adjoint, uint64_t seed, uint64_t stream_id, const uint64_t* ctr, float* params,
                   ctgan_stream_t stream);
 
+/* ---- spectral normalisation of the weight matrices of a flat parameter bucket (csrc/spectral.hip; Miyato et al. 2018 - NOT in the
+ * reference) -------------------------------------------------------------------------------------------------------------------
+ * A job is one normalised parameter: `K x N` floats at bucket offset `off`, read row-major as M[K, N]; its state is u[N], v[K] and
+ * sigma.  The jobs of a bucket are described ONCE by a table of ctgan_spectral_table_words(njobs) int64 words that
+ * ctgan_spectral_table_fill writes on the host (off / K / N: int64 [njobs], ascending and non-overlapping inside a bucket of `total`
+ * floats) and the caller copies to the device: per job its offsets into the packed u (sum of the N before it), v (sum of the K) and
+ * sigma (its index) arrays, its rows per slice and the prefix that flattens (job, row slice) into one grid; word 0 is njobs, word 1
+ * the slice count `nslices` the two operators are given back, ctgan_spectral_scratch_bytes(table) the scratch both need (floats, no
+ * alignment beyond 4 bytes; not preserved between calls).  N > ctgan_spectral_max_n() (4096): CTGAN_E_UNSUPPORTED from the fill,
+ * so before any launch; K is unbounded (the slices of a bucket: fewer than 2^31).  eps = 1e-12.
+ * ctgan_spectral_normalize, iterate != 0: three launches -
+ *   t = M u;  v = t / max(|t|, eps);  s = M^T v;  sigma = |s|;  u <- s / max(sigma, eps);  theta_bar = M / max(sigma, eps) inside
+ *   a job and a copy of theta outside one.  iterate == 0: the last launch alone (u, v, sigma are read only).
+ * ctgan_spectral_grad: two launches - over each job, gbar <- (gbar - <gbar, Mbar> v u^T) / max(sigma, eps), Mbar the job's part of
+ *   theta_bar; elements no job owns are not touched.
+ * Dynamic loss scale: scaler (the float[4] state of the update launches) and hold (one float) are both given or both NULL.  With
+ *   them ctgan_spectral_grad also copies the flag scaler[1] into hold[0]; ctgan_spectral_normalize given that hold (may be NULL)
+ *   skips the iteration when hold[0] != 0 - the update in between was dropped, there is no new weight version - and only rewrites
+ *   theta_bar from the unchanged sigma: u, v, sigma and theta_bar keep their bits.  Only one of the two: CTGAN_E_BADARG.
+ * Every sum has one fixed order relative to its job: the same bits on every run, at any offset and in any company.  theta and
+ * theta_bar are 16-byte aligned and distinct; the table is 8-byte aligned; a null pointer or njobs < 1: CTGAN_E_BADARG.          */
+int ctgan_spectral_max_n(void);
+int64_t ctgan_spectral_table_words(int32_t njobs);
+int ctgan_spectral_table_fill(const int64_t* off, const int64_t* K, const int64_t* N, int32_t njobs, int64_t total, int64_t* table);
+size_t ctgan_spectral_scratch_bytes(const int64_t* table);
+int ctgan_spectral_normalize(const float* theta, float* theta_bar, int64_t total, const int64_t* table, int32_t njobs, int64_t nslices,
+                             float* u, float* v, float* sigma, float* scratch, int32_t iterate, const float* hold, ctgan_stream_t stream);
+int ctgan_spectral_grad(float* gbar, const float* theta_bar, const int64_t* table, int32_t njobs, int64_t nslices, const float* u,
+                        const float* v, const float* sigma, float* scratch, const float* scaler, float* hold, ctgan_stream_t stream);
 
 #ifdef __cplusplus
 }

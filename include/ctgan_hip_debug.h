@@ -54,6 +54,9 @@ int ctgan_debug_clock_probe(const int* flag, uint64_t max_real_ticks, uint64_t* 
    update (ctgan_adam_step / ctgan_rmsprop_step and their _packed forms) with scaler == NULL, 1: ctgan_step_advance with scaler == NULL,
    2: ctgan_grads_nonfinite, 3: an update with a scaler, 4: ctgan_step_advance with a scaler.  A run without a dynamic loss scale moves kinds 0 and 1 only.  Any other kind: 0. */
 uint64_t ctgan_debug_optim_launches(int kind);
+/* the launches one call of the spectral normalisation makes (csrc/spectral.hip) - which 0: ctgan_spectral_normalize with iterate != 0
+   (3), 1: with iterate == 0 (1), 2: ctgan_spectral_grad (2).  Any other: 0. */
+int ctgan_debug_spectral_launches(int which);
 
 #ifdef __cplusplus
 }
