@@ -11,6 +11,7 @@ the generator step; the critic pass that only feeds the gradient penalty, where 
 piecewise linear so the penalty reaches the weights through the backward ops alone).
 """
 import contextlib
+import functools
 
 import torch
 from torch.autograd import Function
@@ -330,6 +331,34 @@ def tape_replay(items, r0, r1):
         assert _TAPE['pos'] == len(items), 'replayed layer sequence differs from the recorded one'
     finally:
         _TAPE.update(mode=None, items=None)
+
+
+# ---- first-order-only Functions ------------------------------------------------------------------------------
+# A kernel wrapper writes into a fresh torch.empty through ctypes: its result has no grad_fn.  A backward that calls a wrapper directly is
+# therefore a constant to autograd under create_graph=True, and a second differentiation through it would lose terms without a word.
+# torch's once_differentiable does not help where the second pass is a torch.autograd.grad(cost, inputs): its error node has no edges, the
+# engine never runs it and hands back None.  So such a backward refuses at once when it is asked to record (tests/autograd_orders_cases.py
+# declares the order of every Function here).
+_NO_BN_ACT = ('.  No twice-differentiable BN-activation layer exists: CTGAN_BN_ACT_FUSED=0 composes batch_norm, tanh and sigmoid, which are first '
+              'order only as well (a twice-differentiable one would be built from MulFn / ScaleFn / AddFn and a batch norm composed like '
+              'layer_norm_composed)')
+
+
+def _first_order_only(what, hint=''):
+    raise RuntimeError('%s is first order only: its backward calls kernels directly and is not differentiable (the objectives that use it '
+                       'have no gradient penalty behind it)%s' % (what, hint))
+
+
+def _once(backward):
+    """Decorator of a Function.backward made of kernel calls: refuses under create_graph=True instead of returning a constant."""
+    name = backward.__qualname__.split('.')[0]
+
+    @functools.wraps(backward)
+    def guarded(ctx, *grads):
+        if torch.is_grad_enabled():
+            _first_order_only(name)
+        return backward(ctx, *grads)
+    return guarded
 
 
 # --------------------------------------------------------------------------------- conv family
@@ -1126,6 +1155,7 @@ class RowsCatDropFn(Function):
         return _taped(lambda: K.rows_cat_dropout(x, n_extra, keep, seed, sid, ctr))
 
     @staticmethod
+    @_once
     def backward(ctx, g):
         n, n_extra = ctx.cfg
         if not K.is_dense(g) or (g.dim() == 4 and not g.is_contiguous() and not g.permute(0, 2, 3, 1).is_contiguous()):
@@ -1148,7 +1178,7 @@ class RowsSelectFn(Function):
     @staticmethod
     def backward(ctx, g):
         if g.dim() == 4 and not g.permute(0, 2, 3, 1).is_contiguous():
-            g = K.to_channels_last(g)
+            g = to_channels_last(g)                 # (the Function, not the wrapper: g keeps its graph under create_graph)
         out = None
         r0 = 0
         pieces = []
@@ -1169,7 +1199,7 @@ class RowsSelectFn(Function):
             'row ranges must tile the input (possibly repeated)'
         gx = torch.cat([acc[k] for k in order], 0)
         if g.dim() == 4 and not gx.permute(0, 2, 3, 1).is_contiguous():
-            gx = K.to_channels_last(gx)
+            gx = to_channels_last(gx)
         return gx, None
 
 
@@ -1308,6 +1338,7 @@ class CropFn(Function):
         return K.copy4d(v, K.empty_cl(*v.shape, device=x.device))
 
     @staticmethod
+    @_once
     def backward(ctx, g):
         h, w, top, left = ctx.win
         N, C, H, W = ctx.shape
@@ -1360,6 +1391,7 @@ class TanhFn(Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
         return K.tanh_bwd(gy.contiguous() if not K.is_dense(gy) else gy, y)
@@ -1373,6 +1405,7 @@ class SigmoidFn(Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
         return K.sigmoid_bwd(gy.contiguous() if not K.is_dense(gy) else gy, y)
@@ -1400,6 +1433,7 @@ class BatchNormFn(Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, gy):
         x4, mean, rstd, scale, offset = ctx.saved_tensors
         gx, gs, go = K.bn_bwd(gy, x4, mean, rstd, scale, offset, ctx.labels, ctx.groups, ctx.relu)
@@ -1419,11 +1453,6 @@ def batch_norm(x, scale, offset, labels=None, groups=1, relu=False, eps=1e-5, f6
 BN_ACT_FUSED = _os.environ.get('CTGAN_BN_ACT_FUSED', '1') != '0'
 
 
-def _first_order_only(what):
-    raise RuntimeError('%s is first order only: its backward is not differentiable (the objectives that use it have no gradient penalty); '
-                       'set CTGAN_BN_ACT_FUSED=0 for the composed, twice-differentiable layer' % what)
-
-
 class BatchNormActFn(Function):
     """Training-mode BN with the following LeakyReLU / tanh / gate folded into the apply launch and into both launches of the backward."""
 
@@ -1437,7 +1466,7 @@ class BatchNormActFn(Function):
     @staticmethod
     def backward(ctx, gy):
         if torch.is_grad_enabled():
-            _first_order_only('batch_norm_act')
+            _first_order_only('batch_norm_act', _NO_BN_ACT)
         x4, mean, rstd, scale, offset = ctx.saved_tensors
         gx, gs, go = K.bn_act_bwd(gy, x4, mean, rstd, scale, offset, ctx.act, ctx.alpha, ctx.groups)
         if len(ctx.in_shape) == 2:
@@ -1454,7 +1483,7 @@ class GateFn(Function):
     @staticmethod
     def backward(ctx, gy):
         if torch.is_grad_enabled():
-            _first_order_only('gate')
+            _first_order_only('gate', _NO_BN_ACT)
         (x,) = ctx.saved_tensors
         return K.gate_bwd(gy, x).reshape(x.shape)
 
@@ -1469,6 +1498,7 @@ class ChannelSplitFn(Function):
         return K.copy4d(ev, K.empty_cl(*ev.shape, device=x.device)), K.copy4d(od, K.empty_cl(*od.shape, device=x.device))
 
     @staticmethod
+    @_once
     def backward(ctx, ge, go):
         full = K.empty_cl(*ctx.shape, device=ge.device)
         K.copy4d(ge, full[:, ::2])
@@ -1519,6 +1549,7 @@ class EluFn(Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
         return K.elu_bwd(gy.contiguous() if not K.is_dense(gy) else gy, y)
@@ -1549,6 +1580,7 @@ class ScoreBNFn(Function):
         return y, e
 
     @staticmethod
+    @_once
     def backward(ctx, gy, ge):
         x4, mean, rstd, scale, offset, e = ctx.saved_tensors
         if gy is not None and gy.dim() == 2:
@@ -1601,6 +1633,16 @@ def batch_norm_blend(x, scale, offset, moving_mean, moving_var, shortcut=None, a
 # scale / offset.  The critic is differentiated TWICE through it (gradient penalty), so the operator is a composition
 # of five kernel-backed maps whose backwards are again members of the set (mul, rsqrt, per-sample sum / broadcast,
 # per-channel affine + the existing axpby / channel sum): every derivative order is a composition of the same kernels.
+def _in_layout_of(g, ref):
+    """g with ref's strides through differentiable ops only: inside a backward a kernel wrapper's repack (K.match_layout) would hand on a
+    tensor without grad_fn, and the second differentiation would lose what arrives through g without a word."""
+    if g.stride() == ref.stride():
+        return g
+    if g.dim() == 4 and ref.permute(0, 2, 3, 1).is_contiguous():
+        return g if g.permute(0, 2, 3, 1).is_contiguous() else to_channels_last(g)
+    return g.contiguous()
+
+
 class MulFn(Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -1610,6 +1652,7 @@ class MulFn(Function):
     @staticmethod
     def backward(ctx, g):
         a, b = ctx.saved_tensors
+        g = _in_layout_of(g, a)                     # (a broadcast gradient - ChannelSumFn's adjoint - is not dense)
         return (MulFn.apply(g, b) if ctx.needs_input_grad[0] else None), (MulFn.apply(g, a) if ctx.needs_input_grad[1] else None)
 
 
@@ -1664,7 +1707,7 @@ class ChannelAffineFn(Function):
     @staticmethod
     def backward(ctx, g):
         x, s = ctx.saved_tensors
-        g = K.match_layout(g, x) if g.dim() == 4 else g.contiguous()
+        g = _in_layout_of(g, x)
         gx = ChannelAffineFn.apply(g, s, None) if ctx.needs_input_grad[0] else None
         gs = _channel_sum(MulFn.apply(g, x)) if ctx.needs_input_grad[1] else None
         go = _channel_sum(g) if (ctx.has_o and ctx.needs_input_grad[2]) else None
@@ -1898,6 +1941,7 @@ class GradPenaltyFn(Function):
         return gp, slopes
 
     @staticmethod
+    @_once
     def backward(ctx, gout, _):
         g, slopes = ctx.saved_tensors
         return K.gp_bwd(g, slopes, gout, ctx.lam), None, None
@@ -1912,6 +1956,7 @@ class ConsistencyFn(Function):
         return ct
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         d, d_, f, f_, ct_i = ctx.saved_tensors
         gd, gd_, gf, gf_ = K.ct_bwd(d, d_, f, f_, ct_i, gout, ctx.lam2, ctx.M)
@@ -1927,6 +1972,7 @@ class SoftmaxCEFn(Function):
         return loss, ncorrect
 
     @staticmethod
+    @_once
     def backward(ctx, gout, _):
         probs, labels = ctx.saved_tensors
         return K.softmax_ce_bwd(probs, labels, gout), None
@@ -1941,6 +1987,7 @@ class MeanDiffFn(Function):
         return K.mean_diff_fwd(x, na, nb, sa, sb)
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         return K.mean_diff_bwd(gout, *ctx.cfg), None, None, None, None
 
@@ -1966,6 +2013,7 @@ class CriticHeadsFn(Function):
         return out[0], out[1], out[2], out[3], out[4]
 
     @staticmethod
+    @_once
     def backward(ctx, g0, g1, g2, g3, _g4=None):
         B, lam2, M, scale = ctx.cfg
         if ctx.has_a:
@@ -2010,7 +2058,7 @@ class CriticTailHeadsFn(Function):
         return out[0], out[1], out[2], out[3], out[4], d, acc
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, g0, g1, g2, g3, _g4=None, _gd=None, _gacc=None):
         B, lam2, M, scale, mask_scale = ctx.cfg
         if ctx.has_a:
@@ -2045,7 +2093,7 @@ class CriticTailHeadsProjFn(Function):
         return out[0], out[1], out[2], out[3], out[4], d, acc
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, g0, g1, g2, g3, _g4=None, _gd=None, _gacc=None):
         B, lam2, M, mask_scale = ctx.cfg
         y, w_out, emb, d, f, ct_i = ctx.saved_tensors
@@ -2092,7 +2140,7 @@ class GenTailHeadsFn(Function):
         return out.reshape(()), d
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, g0, _gd=None):
         ac_scale, mask_scale = ctx.cfg
         if ctx.has_a:
@@ -2117,7 +2165,7 @@ class GenTailHeadsProjFn(Function):
         return out.reshape(()), d
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, g0, _gd=None):
         y, w_out, emb = ctx.saved_tensors
         gy = K.gen_heads_bwd_proj(y, ctx.labels, g0.reshape(1).contiguous(), ctx.mask_scale, w_out, emb)
@@ -2149,7 +2197,7 @@ class GpHeadGradFn(Function):
         return K.gp_head_grad(y, w_out, mask_scale)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, gg):
         y, w_out = ctx.saved_tensors
         if not gg.permute(0, 2, 3, 1).is_contiguous():
@@ -2169,7 +2217,7 @@ class GpHeadGradProjFn(Function):
         return K.gp_head_grad_proj(y, w_out, mask_scale, emb, labels)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once
     def backward(ctx, gg):
         y, w_out, emb = ctx.saved_tensors
         if not gg.permute(0, 2, 3, 1).is_contiguous():
@@ -2221,6 +2269,7 @@ class GanLossFn(Function):
         return K.gan_loss_fwd(d, B, kind)
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         (d,) = ctx.saved_tensors
         return K.gan_loss_bwd(d, gout, *ctx.cfg).view(d.shape), None, None
@@ -2242,6 +2291,7 @@ class WeightNormFn(Function):
         return w
 
     @staticmethod
+    @_once
     def backward(ctx, gw):
         theta, s, rnorm = ctx.saved_tensors
         gtheta, gs = K.wn_bwd(gw, theta, s, rnorm, want_gs=ctx.needs_input_grad[1])
@@ -2270,6 +2320,7 @@ class DenseNoiseFn(Function):
         return h, a
 
     @staticmethod
+    @_once
     def backward(ctx, gh, ga):
         y, b = ctx.saved_tensors
         if gh is None and ga is None:
@@ -2305,6 +2356,7 @@ class SSLHeadFn(Function):
         return out4, ct_i
 
     @staticmethod
+    @_once
     def backward(ctx, gout, _):
         logits, labels = ctx.saved_tensors
         return K.ssl_head_bwd(logits, labels, gout, *ctx.cfg), None, None, None, None
@@ -2325,6 +2377,7 @@ class FeatMatchFn(Function):
         return loss
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         (diff,) = ctx.saved_tensors
         return K.featmatch_bwd(diff, gout, ctx.B), None
@@ -2345,6 +2398,7 @@ class BatchNorm2dFn(Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, gy):
         xhat, offset, rstd = ctx.saved_tensors
         gx, go = K.bn2d_bwd(gy, xhat, offset, rstd, ctx.act, want_goffset=offset is not None and ctx.needs_input_grad[1])
@@ -2367,6 +2421,7 @@ class WeightNormMidFn(Function):
         return w
 
     @staticmethod
+    @_once
     def backward(ctx, gw):
         theta, s, rnorm = ctx.saved_tensors
         gtheta, gs = K.wn_mid_bwd(gw, theta, s, rnorm, want_gs=ctx.needs_input_grad[1])
@@ -2395,6 +2450,7 @@ class FeatConsFn(Function):
         return out2
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         (f,) = ctx.saved_tensors
         return K.featcons_bwd(f, gout, ctx.B), None, None
@@ -2415,6 +2471,7 @@ class FeatMatchL1Fn(Function):
         return loss
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         (diff,) = ctx.saved_tensors
         return K.featmatch_l1_bwd(diff, gout, ctx.B), None
@@ -2440,6 +2497,7 @@ class TEHeadFn(Function):
         return out8
 
     @staticmethod
+    @_once
     def backward(ctx, gout):
         logits, feat, labels, idx = ctx.saved_tensors
         gl, gf = K.te_head_bwd(logits, feat, labels, idx, ctx.tables[0], ctx.tables[1], gout, *ctx.cfg)

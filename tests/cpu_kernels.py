@@ -5,6 +5,12 @@ the autograd wiring (double backward for the gradient penalty), the tflib regist
 orchestration, the flat optimizer, the DDP bucket logic - so tests monkeypatch the functions of
 `ctgan_amd.kernels` with these torch-CPU equivalents (fixture `cpu_kernels` in conftest.py).
 Nothing under ctgan_amd/ imports this file; the `-m gpu` suite never uses it.
+
+About the double-backward wiring: these stand-ins are differentiable torch expressions, a kernel's result is a constant to autograd (it is
+written into a fresh torch.empty through ctypes).  A Function.backward that calls a wrapper directly therefore keeps, on the stand-ins, a
+graph that it does not have on the device, and a second-order check run on them as they are can pass where the device drops terms.  The
+claim above holds only under the opaque shim of tests/test_autograd_orders_standins.py (autograd_orders_cases.make_opaque), which runs
+every installed stand-in under torch.no_grad(); that module declares and checks the derivative order of every Function.
 """
 import torch
 import torch.nn.functional as TF
