@@ -211,6 +211,11 @@ SIGNATURES = {
     'ctgan_gen_heads_bwd_proj': (c_int, [_p, _p, _p, c_int32, c_int32, c_int32, c_float, _p, _p, c_int32, _p, _p]),
     'ctgan_gp_head_grad_proj': (c_int, [_p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p]),
     'ctgan_gp_head_wgrad_proj': (c_int, [_p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, _p, _p, _p, c_int, _p]),
+    # hinge objective: one entry pair, projection table and class head optional (NULL)
+    'ctgan_tail_hinge_heads_fwd': (c_int, [_p, c_int32, c_int32, c_int32, _p, _p, _p, c_int32, _p, _p, c_int32, _p, c_float, _p, _p, _p, _p, _p, _p,
+                                           _p, _p]),
+    'ctgan_tail_hinge_heads_bwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _p, _p, c_int32, _p, _p, _p,
+                                           _p, _p, _p, _p, _p]),
     'ctgan_accuracy2': (c_int, [_p, _p, c_int32, c_int32, _p, _p]),
     # the optimizer updates: avg (may be NULL, then rate 0), avg_rate, scaler (may be NULL) ahead of the stream
     'ctgan_adam_step': (c_int, [_p, _p, _p, _p, c_int64, _p, c_float, c_float, c_float, c_float, _p, c_float, _p, _p]),
@@ -235,6 +240,7 @@ SIGNATURES = {
     'ctgan_rng_labels': (c_int, [_p, c_int64, c_int32, c_uint64, c_uint64, _p, _p]),
     'ctgan_rng_advance': (c_int, [_p, c_uint64, _p]),
     'ctgan_critic_prep': (c_int, [_p, _p, c_int32, c_int32, c_uint64, c_uint64, c_uint64, _p, c_float, c_float, c_float, _p, _p, _p]),
+    'ctgan_real_fake_prep': (c_int, [_p, _p, c_int32, c_int32, c_uint64, c_uint64, _p, c_float, c_float, c_float, _p, _p]),
     'ctgan_rows_cat_dropout': (c_int, [_p, c_int64, c_int64, c_int64, c_float, c_uint64, c_uint64, _p, _p, _p]),
     'ctgan_rows_cat_bwd': (c_int, [_p, c_int64, c_int64, c_int64, _p, _p]),
     'ctgan_rows_cat_bwd2': (c_int, [_p, c_int64, c_int64, c_int64, c_int64, _p, _p]),

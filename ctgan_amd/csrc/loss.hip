@@ -181,6 +181,8 @@ __device__ __forceinline__ float gan_term(int kind, bool real_row, float x) {
     case CTGAN_LOSS_BCE_D: return bce_logits(x, real_row ? 1.f : 0.f);
     case CTGAN_LOSS_BCE_G: return bce_logits(x, 1.f);
     case CTGAN_LOSS_LS_D: { const float r = real_row ? x - 1.f : x; return r * r; }
+    case CTGAN_LOSS_HINGE_D: { const float t = real_row ? 1.f - x : 1.f + x; return t >= 0.f ? t : 0.f; }     // ties count as on
+    case CTGAN_LOSS_HINGE_G: return -x;
     default: { const float r = x - 1.f; return r * r; }
     }
 }
@@ -189,10 +191,16 @@ __device__ __forceinline__ float gan_dterm(int kind, bool real_row, float x) {
     case CTGAN_LOSS_BCE_D: return real_row ? -sigmoidf_stable(-x) : sigmoidf_stable(x);      // sigmoid(x) - z; sigmoid(x) - 1 = -sigmoid(-x)
     case CTGAN_LOSS_BCE_G: return -sigmoidf_stable(-x);
     case CTGAN_LOSS_LS_D: return 2.f * (real_row ? x - 1.f : x);
+    case CTGAN_LOSS_HINGE_D: return real_row ? (1.f - x >= 0.f ? -1.f : 0.f) : (1.f + x >= 0.f ? 1.f : 0.f);
+    case CTGAN_LOSS_HINGE_G: return -1.f;
     default: return 2.f * (x - 1.f);
     }
 }
-__device__ __forceinline__ bool gan_kind_is_critic(int kind) { return kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D; }
+__device__ __forceinline__ bool gan_kind_is_critic(int kind) {
+    return kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D || kind == CTGAN_LOSS_HINGE_D;
+}
+// the 1/2 in front of the two means of the 'dcgan' / 'lsgan' critic costs; the hinge cost is their plain sum
+__device__ __forceinline__ float gan_kind_halves(int kind) { return (kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D) ? 2.f : 1.f; }
 
 __global__ __launch_bounds__(256) void gan_loss_fwd_kernel(const float* __restrict__ d, int B, int kind, float* __restrict__ out) {
     __shared__ float sh[4];
@@ -203,13 +211,16 @@ __global__ __launch_bounds__(256) void gan_loss_fwd_kernel(const float* __restri
         for (int i = threadIdx.x; i < B; i += 256) b += gan_term(kind, false, d[B + i]);
     a = block_sum(a, sh);
     b = block_sum(b, sh);
-    if (threadIdx.x == 0) out[0] = critic ? (b / (float)B + a / (float)B) / 2.f : a / (float)B;
+    if (threadIdx.x == 0) {
+        if (kind == CTGAN_LOSS_HINGE_D) out[0] = a / (float)B + b / (float)B;
+        else out[0] = critic ? (b / (float)B + a / (float)B) / 2.f : a / (float)B;
+    }
 }
 __global__ void gan_loss_bwd_kernel(const float* __restrict__ d, const float* __restrict__ gout, int B, int kind, float* __restrict__ gd) {
     const bool critic = gan_kind_is_critic(kind);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (critic ? 2 * B : B)) return;
-    const float w = critic ? 2.f * (float)B : (float)B;
+    const float w = critic ? gan_kind_halves(kind) * (float)B : (float)B;
     gd[i] = gout[0] * (gan_dterm(kind, !critic || i < B, d[i]) / w);
 }
 
@@ -651,6 +662,154 @@ __global__ __launch_bounds__(256) void tail_heads_bwd_kernel(const float* __rest
     if (lane == 0) {
         if (idx < nf) gw_out[idx] = acc;
         else if (idx < n_w) { const int q = idx - nf, k = q / nf, j = q - k * nf; gw_ac[(long long)j * ncls + k] = acc; }
+        else if (idx == n_w) gb_out[0] = acc;
+        else gb_ac[idx - n_w - 1] = acc;
+    }
+}
+
+// ---- the hinge objective's output stage (ctgan_tail_hinge_heads_fwd/bwd; NOT in the reference): the row workgroup and the one-workgroup
+// finish above without the consistency and penalty parts.  y [2B][hw][nf], rows [0,B) real, [B,2B) fake: one workgroup per row; a real row
+// with the class head also writes probs[r,:] and ce_i[r].  PROJ: the row's weight is w_out + emb[labels[r % B]] (never with the class head).
+template <bool PROJ>
+__global__ __launch_bounds__(256) void tail_hinge_rows_kernel(const float* __restrict__ y, int hw, int nf, const float* __restrict__ w_out,
+                                                              const float* __restrict__ b_out, const float* __restrict__ w_ac,
+                                                              const float* __restrict__ b_ac, int ncls, int B, const int32_t* __restrict__ labels,
+                                                              float* __restrict__ f, float* __restrict__ d, float* __restrict__ a,
+                                                              float* __restrict__ probs, float* __restrict__ ce_i, ProjArgs<PROJ> pa) {
+    __shared__ __attribute__((aligned(16))) float part[1024];
+    __shared__ float fs0[1024];
+    __shared__ float dsh[1];
+    const int r = blockIdx.x;
+    const long long row_elems = (long long)hw * nf;
+    ProjRow<PROJ> pr;
+    if constexpr (PROJ) pr.er = pa.emb + (long long)labels[r % B] * nf;
+    head_row<PROJ>(y + r * row_elems, hw, nf, 0, w_out, b_out, w_ac, b_ac, ncls, part, fs0, f + (long long)r * nf, d + r,
+                   w_ac ? a + (long long)r * ncls : nullptr, dsh, pr);
+    if (w_ac && r < B && threadIdx.x == 0) {
+        const float* z = a + (long long)r * ncls;                                // written above by this workgroup
+        float mx = z[0];
+        for (int k = 1; k < ncls; ++k) mx = fmaxf(mx, z[k]);
+        float se = 0.f;
+        for (int k = 0; k < ncls; ++k) se += expf(z[k] - mx);
+        const float lse = logf(se);
+        for (int k = 0; k < ncls; ++k) probs[(long long)r * ncls + k] = expf(z[k] - mx - lse);
+        ce_i[r] = (mx + lse) - z[labels[r]];
+    }
+}
+// the batch means: out[5] = {hinge + scale * acgan, hinge, hinge_real, hinge_fake, acgan}; with the class head (ce_i, a non-NULL) also the
+// accuracies of the step's own rows (accuracy2_kernel's arithmetic on a [2B,ncls]).  A hinge is t >= 0 ? t : 0.
+__global__ __launch_bounds__(256) void hinge_heads_final_kernel(const float* __restrict__ d, const float* __restrict__ ce_i,
+                                                                const float* __restrict__ a, const int32_t* __restrict__ labels, int B, int ncls,
+                                                                float scale, float* __restrict__ out, float* __restrict__ acc) {
+    __shared__ float sh[4];
+    if (a) {
+        float cr = 0.f, cf = 0.f;
+        for (int i = threadIdx.x; i < 2 * B; i += 256) {
+            const float* z = a + (long long)i * ncls;
+            float mx = z[0]; int am = 0;
+            for (int k = 1; k < ncls; ++k) if (z[k] > mx) { mx = z[k]; am = k; }
+            const float hit = (am == labels[i < B ? i : i - B]) ? 1.f : 0.f;
+            if (i < B) cr += hit; else cf += hit;
+        }
+        cr = block_sum(cr, sh); cf = block_sum(cf, sh);
+        if (threadIdx.x == 0) { acc[0] = cr / (float)B; acc[1] = cf / (float)B; }
+    }
+    float sr = 0.f, sf = 0.f, sl = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const float tr = 1.f - d[i], tf = 1.f + d[B + i];
+        sr += tr >= 0.f ? tr : 0.f;
+        sf += tf >= 0.f ? tf : 0.f;
+        if (ce_i) sl += ce_i[i];
+    }
+    sr = block_sum(sr, sh); sf = block_sum(sf, sh); sl = block_sum(sl, sh);
+    if (threadIdx.x == 0) {
+        const float hr = sr / (float)B, hf = sf / (float)B, ac = ce_i ? sl / (float)B : 0.f;
+        out[0] = (hr + hf) + scale * ac; out[1] = hr + hf; out[2] = hr; out[3] = hf; out[4] = ac;
+    }
+}
+// d hinge / d d_row before gout: -[1 - d >= 0] / B on a real row, +[1 + d >= 0] / B on a fake row (a tie counts as on)
+__device__ __forceinline__ float hinge_gd(const float* d, int row, int B, float g) {
+    if (row < B) return (1.f - d[row] >= 0.f) ? -g : 0.f;
+    return (1.f + d[row] >= 0.f) ? g : 0.f;
+}
+// Backward of {rows kernel + hinge heads + relu/dropout mask of the last conv} in one launch (tail_heads_bwd_kernel's layout):
+//   workgroups [0, 2B): gy[row,hw,j] = y > 0 ? (gd * (w_out[j] [+ emb[label][j]]) + sum_k ga[k] * w_ac[j,k]) / hw * mask_scale : 0
+//   workgroups [2B, ..): one wave per output - gw_out[j], gw_ac[j,k], gb_out, gb_ac[k], g_emb[c][j] - lanes over the rows in ascending
+//   order, wave_sum, a plain store: the same bits on every run; a class that no row carries gets exact zeros.
+template <bool PROJ>
+__global__ __launch_bounds__(256) void tail_hinge_bwd_kernel(const float* __restrict__ y, const float* __restrict__ d, const float* __restrict__ f,
+                                                             const float* __restrict__ probs, const int32_t* __restrict__ labels,
+                                                             const float* __restrict__ gout, int B, int hw, int nf, int ncls, float scale,
+                                                             float mask_scale, const float* __restrict__ w_out, const float* __restrict__ w_ac,
+                                                             float* __restrict__ gy, float* __restrict__ gw_out, float* __restrict__ gb_out,
+                                                             float* __restrict__ gw_ac, float* __restrict__ gb_ac, ProjArgs<PROJ> pa) {
+    __shared__ float t[1024];                            // [nf]
+    const int tid = threadIdx.x;
+    const float g = gout[0] / (float)B, ca = gout[0] * scale / (float)B;
+    if ((int)blockIdx.x < 2 * B) {
+        const int row = blockIdx.x;
+        const float gd = hinge_gd(d, row, B, g);
+        const float* er = nullptr;
+        if constexpr (PROJ) er = pa.emb + (long long)labels[row % B] * nf;
+        for (int j = tid; j < nf; j += 256) {
+            float v;
+            if constexpr (PROJ) v = gd * (w_out[j] + er[j]);
+            else v = gd * w_out[j];
+            if (w_ac && row < B) {
+                const int lab = labels[row];
+                for (int k = 0; k < ncls; ++k)
+                    v += ca * (probs[(long long)row * ncls + k] - (lab == k ? 1.f : 0.f)) * w_ac[(long long)j * ncls + k];
+            }
+            t[j] = v * (1.f / (float)hw);
+        }
+        __syncthreads();
+        const long long base = (long long)row * hw * nf;
+        const int n4 = (hw * nf) >> 2;                   // nf % 4 == 0
+        for (int q = tid; q < n4; q += 256) {
+            const int j = (q * 4) % nf;
+            const float4 yv = *reinterpret_cast<const float4*>(y + base + (long long)q * 4);
+            float4 o;
+            o.x = yv.x > 0.f ? t[j] * mask_scale : 0.f;     o.y = yv.y > 0.f ? t[j + 1] * mask_scale : 0.f;
+            o.z = yv.z > 0.f ? t[j + 2] * mask_scale : 0.f; o.w = yv.w > 0.f ? t[j + 3] * mask_scale : 0.f;
+            *reinterpret_cast<float4*>(gy + base + (long long)q * 4) = o;
+        }
+        return;
+    }
+    const int nac = w_ac ? ncls : 0;
+    const int n_w = nf * (1 + nac), n_all = n_w + 1 + nac;
+    const int lane = tid & 63;
+    const long long idx = ((long long)blockIdx.x - 2 * B) * 4 + (tid >> 6);      // one wave per output, lanes over rows (fixed order)
+    if constexpr (PROJ) {
+        if (idx >= n_all) {                              // g_emb[cls][j]: gw_out[j]'s sum over the rows of class cls
+            const long long q = idx - n_all;
+            if (q >= (long long)pa.n_labels * nf) return;
+            const int cls = (int)(q / nf), j = (int)(q - (long long)cls * nf);
+            float acc = 0.f;
+            for (int r = lane; r < 2 * B; r += 64)
+                if (labels[r % B] == cls) acc += f[(long long)r * nf + j] * hinge_gd(d, r, B, g);
+            acc = wave_sum(acc);
+            if (lane == 0) pa.g_emb[q] = acc;
+            return;
+        }
+    }
+    if (idx >= n_all) return;
+    float acc = 0.f;
+    if (idx < nf) {
+        for (int r = lane; r < 2 * B; r += 64) acc += f[(long long)r * nf + idx] * hinge_gd(d, r, B, g);
+    } else if (idx < n_w) {
+        const int q = (int)idx - nf, k = q / nf, j = q - k * nf;
+        for (int r = lane; r < B; r += 64)
+            acc += f[(long long)r * nf + j] * (ca * (probs[(long long)r * ncls + k] - (labels[r] == k ? 1.f : 0.f)));
+    } else if (idx == n_w) {
+        for (int r = lane; r < 2 * B; r += 64) acc += hinge_gd(d, r, B, g);
+    } else {
+        const int k = (int)idx - n_w - 1;
+        for (int r = lane; r < B; r += 64) acc += ca * (probs[(long long)r * ncls + k] - (labels[r] == k ? 1.f : 0.f));
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        if (idx < nf) gw_out[idx] = acc;
+        else if (idx < n_w) { const int q = (int)idx - nf, k = q / nf, j = q - k * nf; gw_ac[(long long)j * ncls + k] = acc; }
         else if (idx == n_w) gb_out[0] = acc;
         else gb_ac[idx - n_w - 1] = acc;
     }
@@ -1140,6 +1299,51 @@ int ctgan_gp_finish(float* ga, const float* gs, const int64_t* gs_strides, int32
                        (long long)gs_strides[2], (long long)gs_strides[3], c, h, w, scale, slopes);
     return ctgan_check_launch("gp_finish");
 }
+// ---- hinge objective (ctgan_hip.h): one entry pair, the projection table and the class head as optional (exclusive) operands
+int ctgan_tail_hinge_heads_fwd(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
+                               int32_t n_labels, const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float acgan_scale,
+                               float* f, float* d, float* a, float* probs, float* ce_i, float* acc, float* out, ctgan_stream_t s) {
+    if (!y || !f || !d || !w_out || !out || B <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 || (emb && w_ac) ||
+        (emb && (!labels || n_labels <= 0)) || (w_ac && (!a || !labels || !probs || !ce_i || !acc || ncls <= 0)) ||
+        (reinterpret_cast<uintptr_t>(y) & 15) || 2LL * B > 0x7fffffffLL)
+        return ctgan_fail(CTGAN_E_BADARG, "tail_hinge_heads_fwd: bad argument");
+    hipStream_t st = static_cast<hipStream_t>(s);
+    if (emb)
+        hipLaunchKernelGGL(tail_hinge_rows_kernel<true>, dim3(2 * B), dim3(256), 0, st, y, hw, nf, w_out, b_out, (const float*)nullptr,
+                           (const float*)nullptr, 0, B, labels, f, d, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                           ProjArgs<true>{emb, n_labels, nullptr});
+    else
+        hipLaunchKernelGGL(tail_hinge_rows_kernel<false>, dim3(2 * B), dim3(256), 0, st, y, hw, nf, w_out, b_out, w_ac, b_ac, ncls, B, labels, f, d,
+                           w_ac ? a : (float*)nullptr, probs, ce_i, ProjArgs<false>{});
+    int rc = ctgan_check_launch("tail_hinge_rows");
+    if (rc) return rc;
+    hipLaunchKernelGGL(hinge_heads_final_kernel, dim3(1), dim3(256), 0, st, d, w_ac ? ce_i : (const float*)nullptr,
+                       w_ac ? a : (const float*)nullptr, labels, B, ncls, w_ac ? acgan_scale : 0.f, out, acc);
+    return ctgan_check_launch("hinge_heads_final");
+}
+int ctgan_tail_hinge_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* gout,
+                               int32_t B, int32_t hw, int32_t nf, int32_t ncls, float acgan_scale, float mask_scale, const float* w_out,
+                               const float* emb, int32_t n_labels, const float* w_ac, float* gy, float* gw_out, float* gb_out, float* g_emb,
+                               float* gw_ac, float* gb_ac, ctgan_stream_t s) {
+    if (!y || !d || !f || !gout || !w_out || !gy || !gw_out || !gb_out || B <= 0 || hw <= 0 || nf <= 0 || (nf & 3) || nf > 1024 ||
+        (emb && w_ac) || (emb && (!labels || !g_emb || n_labels <= 0)) || (w_ac && (!probs || !labels || !gw_ac || !gb_ac || ncls <= 0)))
+        return ctgan_fail(CTGAN_E_BADARG, "tail_hinge_heads_bwd: bad argument");
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gy)) & 15) return ctgan_fail(CTGAN_E_BADARG, "tail_hinge_heads_bwd: unaligned");
+    const int nac = w_ac ? ncls : 0;
+    const long long n_waves = (long long)nf * (1 + nac) + 1 + nac + (emb ? (long long)n_labels * nf : 0);      // one wave per output
+    if (2LL * B + (n_waves + 3) / 4 > 0x7fffffffLL || (long long)hw * nf > 0x7fffffffLL)
+        return ctgan_fail(CTGAN_E_BADARG, "tail_hinge_heads_bwd: too large");
+    const unsigned grid = (unsigned)(2LL * B + (n_waves + 3) / 4);
+    hipStream_t st = static_cast<hipStream_t>(s);
+    if (emb)
+        hipLaunchKernelGGL(tail_hinge_bwd_kernel<true>, dim3(grid), dim3(256), 0, st, y, d, f, (const float*)nullptr, labels, gout, B, hw, nf, 0, 0.f,
+                           mask_scale, w_out, (const float*)nullptr, gy, gw_out, gb_out, (float*)nullptr, (float*)nullptr,
+                           ProjArgs<true>{emb, n_labels, g_emb});
+    else
+        hipLaunchKernelGGL(tail_hinge_bwd_kernel<false>, dim3(grid), dim3(256), 0, st, y, d, f, probs, labels, gout, B, hw, nf, ncls,
+                           w_ac ? acgan_scale : 0.f, mask_scale, w_out, w_ac, gy, gw_out, gb_out, gw_ac, gb_ac, ProjArgs<false>{});
+    return ctgan_check_launch("tail_hinge_heads_bwd");
+}
 int ctgan_accuracy2(const float* logits, const int32_t* labels, int32_t B, int32_t ncls, float* acc, ctgan_stream_t s) {
     if (!logits || !labels || !acc || B <= 0 || ncls <= 0) return ctgan_fail(CTGAN_E_BADARG, "accuracy2: bad argument");
     hipLaunchKernelGGL(accuracy2_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(s), logits, labels, B, ncls, acc);
@@ -1152,14 +1356,14 @@ int ctgan_mean_diff_fwd(const float* x, int32_t na, int32_t nb, float sa, float 
     return ctgan_check_launch("mean_diff_fwd");
 }
 int ctgan_gan_loss_fwd(const float* d, int32_t B, int32_t kind, float* out, ctgan_stream_t s) {
-    if (!d || !out || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_LS_G) return ctgan_fail(CTGAN_E_BADARG, "gan_loss_fwd: bad argument");
+    if (!d || !out || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_HINGE_G) return ctgan_fail(CTGAN_E_BADARG, "gan_loss_fwd: bad argument");
     hipLaunchKernelGGL(gan_loss_fwd_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(s), d, B, kind, out);
     return ctgan_check_launch("gan_loss_fwd");
 }
 int ctgan_gan_loss_bwd(const float* d, const float* gout, int32_t B, int32_t kind, float* gd, ctgan_stream_t s) {
-    if (!d || !gout || !gd || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_LS_G)
+    if (!d || !gout || !gd || B <= 0 || kind < CTGAN_LOSS_BCE_D || kind > CTGAN_LOSS_HINGE_G)
         return ctgan_fail(CTGAN_E_BADARG, "gan_loss_bwd: bad argument");
-    const int n = (kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D) ? 2 * B : B;
+    const int n = (kind == CTGAN_LOSS_BCE_D || kind == CTGAN_LOSS_LS_D || kind == CTGAN_LOSS_HINGE_D) ? 2 * B : B;
     hipLaunchKernelGGL(gan_loss_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(s), d, gout, B, kind, gd);
     return ctgan_check_launch("gan_loss_bwd");
 }

@@ -455,6 +455,27 @@ __global__ void critic_prep_kernel(const int32_t* __restrict__ xi, const float* 
     *reinterpret_cast<float4*>(rf + n4 * 4 + i) = fv;
     *reinterpret_cast<float4*>(interp + i) = o;
 }
+// ---- critic_prep_kernel without the interpolation (the hinge objective's critic step needs no x_hat): rf = [real ; fake] in one launch,
+// real as above - the draws of rng_uniform_kernel on [b,d] at (seed, sid, step).  d % 4 == 0.
+__global__ void real_fake_prep_kernel(const int32_t* __restrict__ xi, const float* __restrict__ fake, long long n4, uint64_t seed, uint32_t sid,
+                                      const uint64_t* __restrict__ ctr, float lo, float hi, float denom, float* __restrict__ rf) {
+    const uint64_t step = ctr ? ctr[0] : 0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
+        const long long i = q * 4;
+        uint32_t c[4];
+        draw4(seed, sid, step, (uint32_t)q, c);
+        const int4 xv = *reinterpret_cast<const int4*>(xi + i);
+        const float4 fv = *reinterpret_cast<const float4*>(fake + i);
+        float4 r;
+        r.x = 2.f * (((float)xv.x / denom) - .5f); r.x += lo + (hi - lo) * u01(c[0]);
+        r.y = 2.f * (((float)xv.y / denom) - .5f); r.y += lo + (hi - lo) * u01(c[1]);
+        r.z = 2.f * (((float)xv.z / denom) - .5f); r.z += lo + (hi - lo) * u01(c[2]);
+        r.w = 2.f * (((float)xv.w / denom) - .5f); r.w += lo + (hi - lo) * u01(c[3]);
+        *reinterpret_cast<float4*>(rf + i) = r;
+        *reinterpret_cast<float4*>(rf + n4 * 4 + i) = fv;
+    }
+}
 
 // ---- [x ; x[0:n_extra]] with tf.nn.dropout on the result, one launch (the input of the critic tail for the two dropout passes,
 // pass 2 on the real half only, :226-227,288-291): dst row r < n_src reads src row r, row n_src + r' reads src row r'.
@@ -802,6 +823,16 @@ int ctgan_critic_prep(const int32_t* x_int, const float* fake, int32_t b, int32_
     hipLaunchKernelGGL(critic_prep_kernel, dim3(ctgan_blocks(n4, 256, 1 << 20)), dim3(256), 0, static_cast<hipStream_t>(s), x_int, fake, n4,
                        d, seed, (uint32_t)sid_deq, (uint32_t)sid_alpha, ctr, lo, hi, denom, rf, interp);
     return ctgan_check_launch("critic_prep");
+}
+int ctgan_real_fake_prep(const int32_t* x_int, const float* fake, int32_t b, int32_t d, uint64_t seed, uint64_t stream_id, const uint64_t* ctr,
+                         float lo, float hi, float denom, float* rf, ctgan_stream_t s) {
+    if (!x_int || !fake || !rf || b <= 0 || d <= 0 || (d & 3) || (long long)b * d >= (1LL << 34) ||
+        ((reinterpret_cast<uintptr_t>(x_int) | reinterpret_cast<uintptr_t>(fake) | reinterpret_cast<uintptr_t>(rf)) & 15))
+        return ctgan_fail(CTGAN_E_BADARG, "real_fake_prep: bad argument");
+    const long long n4 = (long long)b * d / 4;
+    hipLaunchKernelGGL(real_fake_prep_kernel, dim3(ctgan_blocks(n4, 256, 1 << 20)), dim3(256), 0, static_cast<hipStream_t>(s), x_int, fake, n4, seed,
+                       (uint32_t)stream_id, ctr, lo, hi, denom, rf);
+    return ctgan_check_launch("real_fake_prep");
 }
 int ctgan_rows_cat_dropout(const float* src, int64_t n_src, int64_t n_extra, int64_t row_elems, float keep, uint64_t seed,
                            uint64_t stream_id, const uint64_t* ctr, float* dst, ctgan_stream_t s) {

@@ -41,7 +41,8 @@ BATCH_FAKES = _os.environ.get('CTGAN_DCGAN_BATCH_FAKES', '1') != '0'
 class GanMode(NamedTuple):
     """One MODE branch of a script: its objective, optimizer and loop literals (TF/CT_gan_mnist.py:122-206,238-249;
     TF/CT_gan_64x64.py:490-579,634-646)."""
-    loss: str                    # 'ct' (WGAN + consistency term + gradient penalty), 'wgan', 'bce' (MODE 'dcgan'), 'ls' (MODE 'lsgan')
+    loss: str                    # 'ct' (WGAN + consistency term + gradient penalty), 'wgan', 'bce' (MODE 'dcgan'), 'ls' (MODE 'lsgan');
+                                 # 'hinge' (DCGANTrainer(objective='hinge'): in no MODES table, the scripts have no such branch)
     optimizer: str               # 'adam' | 'rmsprop' (the same for critic and generator)
     lr: float = None             # None: the module's CT learning rate (cfg.LR, or its lr(iteration))
     betas: tuple = None          # Adam (beta1, beta2); None: the module's ADAM_BETAS
@@ -50,6 +51,7 @@ class GanMode(NamedTuple):
 
 
 CT_MODE = GanMode('ct', 'adam')
+HINGE_MODE = GanMode('hinge', 'adam')       # objective='hinge': the CT default's learning rate, ADAM_BETAS and cfg.CRITIC_ITERS
 
 
 def validate_mode(module_name, modes, mode):
@@ -77,7 +79,7 @@ def mode_of(module):
 
 class DCGANTrainer:
     def __init__(self, module, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, loss_scale=None,
-                 spectral_norm=False):
+                 spectral_norm=False, objective=None):
         """`module` = ctgan_amd.gan_cifar or ctgan_amd.gan_mnist (provides cfg, Generator, Discriminator,
         real_prep, feat_shapes).  g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights,
         moved inside its update launch (optim.FlatAdam / FlatRMSProp avg_rate), whatever the mode's optimizer.  It is the RATE, 1 - decay:
@@ -94,7 +96,16 @@ class DCGANTrainer:
         the reference; Miyato et al. 2018): the critic reads every conv filter and Linear weight divided by its spectral norm,
         one power iteration per critic update (optim.SpectralNorm: `spectral`); the registry, the optimizer and the checkpoints keep the
         raw weights, `d_params` and a step's out['grads'] are the normalised weights and the gradients with respect to them (the raw
-        weights' are in d_opt.grad).  ValueError under MODE 'wgan', whose weight clip answers the same question.  False: nothing differs."""
+        weights' are in d_opt.grad).  ValueError under MODE 'wgan', whose weight clip answers the same question.  False: nothing differs.
+        objective (NOT in the reference; Lim & Ye 2017, Miyato et al. 2018): None - the module's MODE; 'hinge' - the critic
+        minimises mean max(0, 1 - D(x)) + mean max(0, 1 + D(G(z))), the generator -mean D(G(z)): `mode` becomes GanMode('hinge', 'adam'),
+        i.e. the module's CT learning rate, its ADAM_BETAS and cfg.CRITIC_ITERS, one dropout pass over [real ; fake], no penalty.  Valid
+        only while the module's MODE is its CT default (the unnormalised critic with dropout and one statistic group): ValueError under
+        'wgan', 'dcgan' or 'lsgan', and for any other value.  The step runs on the autograd path (no hand schedule for this family).
+        None (default): nothing differs."""
+        if objective not in (None, 'hinge'):
+            raise ValueError("objective: None or 'hinge' (got %r)" % (objective,))
+        self.objective = objective
         self.mod = module
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape_of(module) if self.aug_policy else None
@@ -104,6 +115,10 @@ class DCGANTrainer:
         self.d_named = lib.named_params_with_name('Discriminator', trainable_only=True)
         self.g_named = lib.named_params_with_name('Generator', trainable_only=True)
         self.mode = mode_of(module)
+        if objective == 'hinge':
+            if self.mode.loss != 'ct':
+                raise ValueError("objective='hinge' replaces the CT objective only: not under MODE %r" % (module.cfg.MODE,))
+            self.mode = HINGE_MODE
         self.disc_iters = self.mode.critic_iters or module.cfg.CRITIC_ITERS     # critic steps per iteration
         if spectral_norm and self.mode.clip:
             raise ValueError('spectral_norm: not with the weight clip of MODE %r (two answers to one question: use one)' % (module.cfg.MODE,))
@@ -213,11 +228,13 @@ class DCGANTrainer:
     def _critic(self, x, u, groups):
         """The critic on rows made of `groups` reference calls (each its own BatchNorm statistics) - the non-CT objectives."""
         m = self.mod
+        if self.mode.loss == 'hinge':       # the CT default's critic: no batch norm, one statistic group (gan_cifar's takes no `groups`)
+            return m.Discriminator(x, u=u) if u is not None else m.Discriminator(x, rng=self.rng)
         return m.Discriminator(x, u=u, groups=groups) if u is not None else m.Discriminator(x, rng=self.rng, groups=groups)
 
     def _d_losses_plain(self, real_in, rnd, fake):
-        """Critic cost of the 'wgan' / 'dcgan' / 'lsgan' objectives over D(real) (masks u_real) and D(fake) (masks u_fake) - one batch of
-        2B rows, two statistic groups per generator tower."""
+        """Critic cost of the 'wgan' / 'dcgan' / 'lsgan' objectives (and of objective='hinge') over D(real) (masks u_real) and D(fake) (masks
+        u_fake) - one batch of 2B rows, two statistic groups per generator tower."""
         m, B = self.mod, self.mod.cfg.BATCH_SIZE
         with torch.no_grad():
             if fake is None:
@@ -408,7 +425,7 @@ def sample_grid(module, noise, trainer=None, averaged=False):
 
 def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100, dev_every=100,
           checkpoint_every=1000, score_every=None, classifier=None, resume=None, log=print, g_average=0.0, augment=None, loss_scale=None,
-          spectral_norm=False):
+          spectral_norm=False, objective=None):
     """The loop body the DCGAN-family scripts share (TF/CT_gan_cifar.py:190-236, TF/CT_gan_mnist.py:232-270, TF/CT_gan_64x64.py:628-669):
     `next_batch()` -> one real batch on the device; `dev_batches()` -> an iterable over the held-out batches (None: no dev pass).  Series
     (train_log.Series, log.jsonl in `out_dir`): `train disc cost` and `time` per iteration; every `dev_every` iterations `dev disc cost`
@@ -420,7 +437,8 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     grids and the scores stay un-augmented.  `loss_scale` (NOT in the reference; DCGANTrainer): None, a fixed scale, or 'dynamic' / an
     optim.LossScaler - then the series `loss_scale` and `skipped_steps` are added at every flush.  `spectral_norm` (NOT in the reference;
     DCGANTrainer): the critic's weights are spectrally normalised - then the series `sn_sigma_max` and `sn_sigma_min` are added at every
-    flush.  Returns the trainer."""
+    flush.  `objective` (NOT in the reference; DCGANTrainer): None or 'hinge' - the hinge critic and generator costs in place of the CT
+    objective; the series keep their names.  Returns the trainer."""
     import os
     import time
 
@@ -431,7 +449,8 @@ def train(module, next_batch, dev_batches=None, iters=None, out_dir='.', seed=20
     cfg = module.cfg
     iters = cfg.ITERS if iters is None else iters
     build_params(module)
-    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment, loss_scale=loss_scale, spectral_norm=spectral_norm)
+    trainer = DCGANTrainer(module, seed=seed, g_average=g_average, augment=augment, loss_scale=loss_scale, spectral_norm=spectral_norm,
+                           objective=objective)
     start = checkpoint.load(resume, trainer) if resume else 0
     first = next_batch()
     eng = GraphedDCGANTrainer(trainer, tuple(first.shape), first.dtype, use_graphs=use_graphs)

@@ -168,6 +168,8 @@ class Evaluator:
         labels = _cat([lab for _, lab in group])
         assert real_int.shape[0] == n and labels.shape[0] == n, 'every dev batch has BATCH_SIZE rows'
         fuse_heads = R._heads_fusable(rnds, rng)
+        if getattr(self.t, 'objective', None) == 'hinge':
+            return self._pass_resnet_hinge(real_int, labels, rnds, rng, G, fuse_heads)
         with torch.no_grad():
             z = _cat([torch.cat(r['z'], 0) for r in rnds]) if rnds is not None else None
             fake = R.Generator(n, labels, noise=z, groups=2 * G, rng=rng)
@@ -216,6 +218,37 @@ class Evaluator:
             return F.critic_heads(d_all, f_all, a_all if use_ac else None, labels, n, cfg.LAMBDA_2, cfg.Factor_M,
                                   cfg.ACGAN_SCALE if use_ac else 0.0, gp)[0]
 
+    def _pass_resnet_hinge(self, real_int, labels, rnds, rng, G, fuse_heads):
+        """The hinge critic cost (Trainer(objective='hinge'); NOT in the reference) over G batches at once: mean max(0, 1 - D(x)) + mean
+        max(0, 1 + D(G(z))) + ACGAN_SCALE ACGAN, one dropout pass over [real ; fake] - the call sites of Trainer.d_losses_hinge."""
+        R, cfg = self.mod, self.mod.cfg
+        n = real_int.shape[0]
+        use_ac = cfg.CONDITIONAL and cfg.ACGAN
+        P = lib.param
+        with torch.no_grad():
+            z = _cat([torch.cat(r['z'], 0) for r in rnds]) if rnds is not None else None
+            fake = R.Generator(n, labels, noise=z, groups=2 * G, rng=rng)
+            rf = R.real_fake_inputs(real_int, fake, rng, _cat([r['dequant'] for r in rnds]) if rnds is not None else None)
+            lab2 = torch.cat([labels, labels], 0)
+            if fuse_heads:
+                y = R.DiscriminatorTailBody(R.DiscriminatorTrunk(rf), 0.8, 0.5, 0.5, rng=rng, mask_done=True)
+                if not y.permute(0, 2, 3, 1).is_contiguous():
+                    y = F.to_channels_last(y)
+                return K.tail_hinge_heads_fwd(y, n, P('Discriminator.Output.W'), P('Discriminator.Output.b'), labels=labels,
+                                              emb=R.projection_table() if cfg.PROJECTION else None,
+                                              w_ac=P('Discriminator.ACGANOutput.W') if use_ac else None,
+                                              b_ac=P('Discriminator.ACGANOutput.b') if use_ac else None,
+                                              scale=cfg.ACGAN_SCALE if use_ac else 0.0)[0][0]
+            u = None
+            if rnds is not None:       # rows: real of all batches, fake of all batches
+                u = [torch.cat([a, b], 0) for a, b in zip(_cat_masks(rnds, 'u_pass1', slice(0, cfg.BATCH_SIZE)),
+                                                          _cat_masks(rnds, 'u_pass1', slice(cfg.BATCH_SIZE, 2 * cfg.BATCH_SIZE)))]
+            d, _, a = R.Discriminator(rf, lab2, 0.8, 0.5, 0.5, u=u, rng=rng)
+            cost = F.gan_loss(d, n, 'hinge', 'd')
+            if use_ac:
+                cost = cost + cfg.ACGAN_SCALE * F.softmax_cross_entropy(a[:n], labels)[0]
+            return cost
+
     def _gen(self, n, z, groups, rng):
         g = self.t.towers * groups
         if g > 1:
@@ -235,12 +268,13 @@ class Evaluator:
             real = m.real_prep(real_in)
             if t.mode.loss != 'ct':
                 x = torch.cat([real, fake], 0)
-                groups = 2 * t.towers * G
+                # (objective='hinge' keeps the CT default's critic: no batch norm, no `groups`)
+                kw = {} if t.mode.loss == 'hinge' else {'groups': 2 * t.towers * G}
                 if rnds is not None:
                     u = [torch.cat([a, c], 0) for a, c in zip(_cat_masks(rnds, 'u_real'), _cat_masks(rnds, 'u_fake'))]
-                    d, _ = m.Discriminator(x, u=u, groups=groups)
+                    d, _ = m.Discriminator(x, u=u, **kw)
                 else:
-                    d, _ = m.Discriminator(x, rng=rng, groups=groups)
+                    d, _ = m.Discriminator(x, rng=rng, **kw)
                 if t.mode.loss == 'wgan':
                     return F.mean_diff(d, n, n, -1.0, 1.0)
                 return F.gan_loss(d, n, t.mode.loss, 'd')

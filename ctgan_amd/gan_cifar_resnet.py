@@ -389,6 +389,17 @@ def _cat_rows(a, b):
     return torch.cat([a, b], dim=0)
 
 
+def real_fake_inputs(real_int, fake, rng, deq=None):
+    """rf [2n,d] = [dequantised real ; fake], the input of a hinge critic pass (Trainer.hinge_prep, evaluate.Evaluator._pass_resnet_hinge):
+    ONE Philox call site - the fused launch (kernels.real_fake_prep), or rng.uniform + real_prep + cat where it does not apply.  deq: the
+    injected dequantisation draw [n,d] (then `rng` draws nothing)."""
+    if PREP_FUSION and deq is None and cfg.OUTPUT_DIM % 4 == 0 and real_int.is_contiguous() and fake.is_contiguous():
+        return K.real_fake_prep(real_int, fake, rng.seed, rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
+    if deq is None:
+        deq = rng.uniform(real_int.shape[0], cfg.OUTPUT_DIM, lo=0.0, hi=1. / 128)
+    return _cat_rows(K.real_prep(real_int, deq, 256.0), fake)
+
+
 # A/B switch: the tail's dropouts (and the final ReLU) inside the neighbouring conv kernels (see DiscriminatorTail)
 DROP_FUSION = _os.environ.get('CTGAN_DROP_FUSION', '1') != '0'
 # A/B switch: the generator's upsampled 1x1 shortcut is read at low resolution by the epilogue of the block's last conv
@@ -495,7 +506,7 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
 class Trainer:
     """Owns the optimizers, the random streams and the D/G step (the session of the reference)."""
 
-    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, spectral_norm=False):
+    def __init__(self, seed=2024, rank=0, world_size=1, allreduce=None, g_average=0.0, augment=None, spectral_norm=False, objective=None):
         """g_average > 0 (NOT in the reference): keep an exponential moving average of the GENERATOR's weights, moved inside its update
         launch (optim.FlatAdam avg_rate).  It is the RATE, 1 - decay: g_average=1e-4 is a decay of 0.9999.  `averaged()` samples from it.
         The critic is never averaged.  0 (default): nothing differs from a trainer built without the argument.
@@ -508,7 +519,18 @@ class Trainer:
         projection table too - divided by its spectral norm, estimated by one power iteration per critic update (optim.SpectralNorm:
         `spectral`).  The registry, the optimizer and the checkpoints keep the raw weights; lib.param gives the normalised ones through
         the alias table, `d_params` are those, and a step's out['grads'] are gradients with respect to them (the raw weights' are in
-        d_opt.grad).  False (default): nothing differs from a trainer built without the argument."""
+        d_opt.grad).  False (default): nothing differs from a trainer built without the argument.
+        objective (NOT in the reference; Lim & Ye 2017, Miyato et al. 2018): None - the script's CT objective; 'hinge' - the
+        critic minimises mean max(0, 1 - D(x)) + mean max(0, 1 + D(G(z))) [+ ACGAN_SCALE * CE(class head of the real rows)]: ONE forward and
+        one backward chain over [real ; fake], no x_hat, no second dropout pass, no gradient penalty (d_losses_hinge, hinge_schedule.py).  The
+        critic network stays the script's (keep probabilities 0.8 / 0.5 / 0.5, one pass); the generator step, N_CRITIC, the learning-rate decay
+        and the optimizers stay.  A step's `out` then has cost, wgan (= the hinge sum without the class term), hinge_real, hinge_fake, acgan,
+        acc_real, acc_fake (None without the class head), fake, real, d_real, d_fake - and no ct, gp, slopes, gp_grads.  acc_real / acc_fake
+        are taken on the step's own, dropped-out rows (there is no clean third pass): they are NOT the CT step's clean-pass accuracies.  Any
+        other value raises ValueError.  None (default): nothing differs from a trainer built without the argument."""
+        if objective not in (None, 'hinge'):
+            raise ValueError("objective: None or 'hinge' (got %r)" % (objective,))
+        self.objective = objective
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape()
         self.dev = lib._dev()
@@ -676,6 +698,46 @@ class Trainer:
                    real=real, d_real=d_all[:B], d_fake=d_all[B:2 * B], gp_grads=grads)
         return out
 
+    def hinge_prep(self, real_int, fake, rnd=None):
+        """The hinge critic step's input rf [2B,d] = [real ; fake] (no x_hat): the dequantisation draw is the step's first call site, as in
+        the CT step (out['real'] is the same tensor at the same seed and step); with the augmentation on, [T(real) ; T(fake)]."""
+        B, rng = cfg.BATCH_SIZE, self.rng
+        if self.aug_policy:
+            deq = rnd['dequant'] if rnd is not None else rng.uniform(B, cfg.OUTPUT_DIM, lo=0.0, hi=1. / 128)
+            rf = torch.empty(2 * B, cfg.OUTPUT_DIM, dtype=torch.float32, device=real_int.device)
+            K.diffaug(K.real_prep(real_int, deq, 256.0), self.aug_shape, self.aug_policy, rng.aug_spec(AUG_REAL), out=rf[:B])
+            K.diffaug(fake.contiguous(), self.aug_shape, self.aug_policy, rng.aug_spec(AUG_FAKE), out=rf[B:])
+            return rf
+        return real_fake_inputs(real_int, fake, rng, rnd['dequant'] if rnd is not None else None)
+
+    def d_losses_hinge(self, real_int, labels, rnd=None, fake=None):
+        """Critic loss graph of objective='hinge' (NOT in the reference): L_D = mean max(0, 1 - D(x)) + mean max(0, 1 + D(G(z)))
+        [+ ACGAN_SCALE * CE(class head of the real rows)] over ONE dropout pass on [real ; fake].  `rnd` injects the draws: the keys `z`,
+        `dequant` and `u_pass1` of oracle/steps.make_rnd_resnet_d.  Call sites: the dequantisation, then the three dropouts in network order."""
+        B = cfg.BATCH_SIZE
+        rng = self.rng
+        with torch.no_grad():
+            if fake is None:
+                z = torch.cat(rnd['z'], 0) if rnd is not None else None
+                fake = Generator(B, labels, noise=z, groups=2, rng=rng)
+            rf = self.hinge_prep(real_int, fake, rnd)
+        use_ac = cfg.CONDITIONAL and cfg.ACGAN
+        d, _, a = Discriminator(rf, _cat_rows(labels, labels), 0.8, 0.5, 0.5, u=rnd['u_pass1'] if rnd is not None else None, rng=rng)
+        hinge = F.gan_loss(d, B, 'hinge', 'd')
+        cost, acgan, acc = hinge, None, (None, None)
+        if use_ac:
+            acgan, _ = F.softmax_cross_entropy(a[:B], labels)
+            cost = hinge + cfg.ACGAN_SCALE * acgan
+            with torch.no_grad():       # on the step's own, dropped-out rows: not the CT step's clean-pass accuracies
+                acc = K.accuracy2(a.detach().contiguous(), labels, B)
+        with torch.no_grad():           # the two reported halves of `hinge`
+            dd = d.detach()
+            tr, tf = 1.0 - dd[:B], 1.0 + dd[B:]
+            hinge_real = torch.where(tr >= 0, tr, torch.zeros_like(tr)).mean()
+            hinge_fake = torch.where(tf >= 0, tf, torch.zeros_like(tf)).mean()
+        return {'cost': cost, 'wgan': hinge, 'hinge_real': hinge_real, 'hinge_fake': hinge_fake, 'acgan': acgan, 'acc_real': acc[0],
+                'acc_fake': acc[1], 'fake': fake, 'real': rf[:B], 'd_real': d[:B], 'd_fake': d[B:2 * B]}
+
     def early_reduce(self, gpart):
         """`early` hook of critic_schedule.critic_step: the finished gradients of blocks 1-2 -> the prefix of the flat bucket -> their
         all-reduce, asynchronous on the side stream (ddp.FlatAllReduce).  Returns the number of parameters handed over."""
@@ -693,6 +755,18 @@ class Trainer:
         if fake is None and rnd is None:
             with torch.no_grad():      # (the draw d_losses would make first: same Philox call sites either way)
                 fake = Generator(cfg.BATCH_SIZE, labels, groups=2, rng=self.rng)
+        if self.objective == 'hinge':
+            # one forward, one backward chain over [real ; fake] (hinge_schedule.py); `early` is ignored: nothing is finished early in a
+            # plain backward.  The autograd path wherever that schedule does not apply, as below.
+            from . import hinge_schedule as HS
+            if HS.usable(_this_module(), rnd, self.rng, real_int, fake):
+                with torch.no_grad(), F.deferred_wgrads():
+                    prep = self.hinge_prep(real_int, fake) if self.aug_policy else None
+                    return HS.critic_step(self, _this_module(), real_int, labels, fake, prep=prep)
+            out = self.d_losses_hinge(real_int, labels, rnd, fake=fake)
+            with F.deferred_wgrads():
+                grads = torch.autograd.grad(out['cost'], self.d_params, grad_outputs=self.cost_seed(out['cost']), allow_unused=True)
+            return out, grads
         if CS.usable(_this_module(), rnd, self.rng, real_int, fake):
             with torch.no_grad(), F.deferred_wgrads():
                 prep = self.augmented_prep(real_int, fake) if self.aug_policy else None
@@ -852,7 +926,7 @@ class Trainer:
 
 def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_graphs=True, sample_every=100,
           checkpoint_every=1000, resume=None, log=print, dev_every=100, score_every=None, classifier=None, g_average=0.0, augment=None,
-          spectral_norm=False):
+          spectral_norm=False, objective=None):
     """The module-level training loop of the reference (TF/CT_gan_cifar_resnet.py:350-434): CIFAR-10 generator factories, `time` /
     `cost` / `wgan` / `acgan` / `acc_real` / `acc_fake` series (train_log.Series), fixed-noise sample grids every
     `sample_every` iterations (:341-348, :429), checkpoints every `checkpoint_every` (build-only), the held-out critic cost `dev_cost`
@@ -864,7 +938,9 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     reference; Trainer): a Differentiable Augmentation policy such as 'color,translation,cutout' for the critic's inputs in both steps;
     the dev cost, the sample grids and the scores stay un-augmented.  `spectral_norm` (NOT in the reference; Trainer): the critic's weights
     are spectrally normalised; the series `sn_sigma_max` / `sn_sigma_min` - the largest and smallest estimated spectral norm of its
-    layers - are added whenever the series are flushed."""
+    layers - are added whenever the series are flushed.  `objective` (NOT in the reference; Trainer): None or 'hinge' - the hinge critic
+    step; the series keep their names (`wgan` is then the hinge sum, `acc_real` / `acc_fake` the dropped-out rows' accuracies, `dev_cost`
+    the hinge cost over the dev batches)."""
     import os
     import time
 
@@ -874,7 +950,7 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
     from .train_log import Series
     iters = cfg.ITERS if iters is None else iters
     build_params()
-    trainer = Trainer(seed=seed, g_average=g_average, augment=augment, spectral_norm=spectral_norm)
+    trainer = Trainer(seed=seed, g_average=g_average, augment=augment, spectral_norm=spectral_norm, objective=objective)
     start = checkpoint.load(resume, trainer) if resume else 0
     eng = GraphedTrainer(trainer, use_graphs=use_graphs)
     ev = evaluate.Evaluator(trainer)

@@ -1890,14 +1890,15 @@ def mean_diff_bwd(gout, na, nb, sa, sb):
 
 
 # loss heads of the 'dcgan' / 'lsgan' objectives (csrc/loss.hip; kinds as in ctgan_hip.h)
-GAN_LOSS_KINDS = {('bce', 'd'): 0, ('bce', 'g'): 1, ('ls', 'd'): 2, ('ls', 'g'): 3}
+# ('hinge', .) (NOT in the reference): mean hinge(1 - D(real)) + mean hinge(1 + D(fake)), no 1/2 in front / -mean(D(fake))
+GAN_LOSS_KINDS = {('bce', 'd'): 0, ('bce', 'g'): 1, ('ls', 'd'): 2, ('ls', 'g'): 3, ('hinge', 'd'): 4, ('hinge', 'g'): 5}
 
 
 def gan_loss_fwd(d, B, kind):
-    """Cost of `kind` (0..3, GAN_LOSS_KINDS) over d = [D(real) ; D(fake)] (critic kinds, 2B rows) or D(fake) (generator kinds, B rows)."""
+    """Cost of `kind` (0..5, GAN_LOSS_KINDS) over d = [D(real) ; D(fake)] (critic kinds, 2B rows) or D(fake) (generator kinds, B rows)."""
     _need_dev(d)
     d = d.contiguous()
-    assert d.dtype == torch.float32 and d.numel() == (2 * B if kind in (0, 2) else B)
+    assert d.dtype == torch.float32 and d.numel() == (2 * B if kind in (0, 2, 4) else B)
     out = torch.empty((), dtype=torch.float32, device=d.device)
     check(lib.ctgan_gan_loss_fwd(_ptr(d), B, kind, _ptr(out), _stream()), 'gan_loss_fwd')
     return out
@@ -1906,7 +1907,7 @@ def gan_loss_fwd(d, B, kind):
 def gan_loss_bwd(d, gout, B, kind):
     _need_dev(d, gout)
     d = d.contiguous()
-    assert d.numel() == (2 * B if kind in (0, 2) else B)
+    assert d.numel() == (2 * B if kind in (0, 2, 4) else B)
     gd = torch.empty(d.numel(), dtype=torch.float32, device=d.device)
     check(lib.ctgan_gan_loss_bwd(_ptr(d), _ptr(gout.contiguous()), B, kind, _ptr(gd), _stream()), 'gan_loss_bwd')
     return gd
@@ -2216,6 +2217,63 @@ def tail_heads_bwd(y, d, f, probs, labels, ct_i, gout, B, lam2, M, scale, mask_s
     return gy, gw_out, gb_out, gw_ac, gb_ac
 
 
+def tail_hinge_heads_fwd(y, B, w_out, b_out, labels=None, emb=None, w_ac=None, b_ac=None, scale=0.0):
+    """The hinge objective's output stage over the 2B rows [real ; fake] of a critic step, two launches (NOT in the reference).
+    -> (out[5] = {hinge + scale * acgan, hinge, hinge_real, hinge_fake, acgan}, f [2B,nf], d [2B], a [2B,ncls] or None, probs [B,ncls] or
+    None, acc [2] or None).  emb [n_labels,nf] (projection table: a row's weight is w_out + emb[labels[r % B]]) and the class head
+    (w_ac [nf,ncls], b_ac) are optional and exclusive; acc = the accuracies of the step's own, dropped-out rows."""
+    _need_dev(y, w_out, b_out, labels, emb, w_ac, b_ac)
+    n, hw, nf = _cl_rows(y)
+    assert n == 2 * B and w_out.is_contiguous() and w_out.numel() == nf
+    dev = y.device
+    n_labels = _proj_args(emb, labels, nf, B) if emb is not None else 0
+    ncls = 0
+    a = probs = ce_i = acc = None
+    if w_ac is not None:
+        assert w_ac.is_contiguous() and w_ac.shape[0] == nf and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B
+        ncls = w_ac.shape[1]
+        a = torch.empty(n, ncls, dtype=torch.float32, device=dev)
+        probs = torch.empty(B, ncls, dtype=torch.float32, device=dev)
+        ce_i = torch.empty(B, dtype=torch.float32, device=dev)
+        acc = torch.empty(2, dtype=torch.float32, device=dev)
+    f = torch.empty(n, nf, dtype=torch.float32, device=dev)
+    d = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    check(lib.ctgan_tail_hinge_heads_fwd(_ptr(y), B, hw, nf, _ptr(w_out), _ptr(b_out), _ptr(emb), n_labels, _ptr(w_ac), _ptr(b_ac), ncls,
+                                         _ptr(labels), scale, _ptr(f), _ptr(d), _ptr(a), _ptr(probs), _ptr(ce_i), _ptr(acc), _ptr(out), _stream()),
+          'tail_hinge_heads_fwd')
+    return out, f, d, a, probs, acc
+
+
+def tail_hinge_heads_bwd(y, d, f, probs, labels, gout, B, scale, mask_scale, w_out, emb=None, w_ac=None, out=None):
+    """-> (gy like y: gradient w.r.t. the last block's pre-activation; gw_out, gb_out, g_emb or None, gw_ac or None, gb_ac or None) - one launch.
+    out: buffer for gy (y's shape, dense channels-last - e.g. the leading rows of a larger batch).  gout: the device scalar seed."""
+    _need_dev(y, d, f, probs, labels, gout, w_out, emb, w_ac, out)
+    n, hw, nf = _cl_rows(y)
+    assert n == 2 * B and gout.is_contiguous() and gout.numel() == 1
+    assert w_out.is_contiguous() and w_out.numel() == nf and d.is_contiguous() and d.numel() == n and f.is_contiguous() and tuple(f.shape) == (n, nf)
+    n_labels = _proj_args(emb, labels, nf, B) if emb is not None else 0
+    if out is not None:
+        assert tuple(out.shape) == tuple(y.shape) and _cl_rows(out) == (n, hw, nf)
+        gy = out
+    else:
+        gy = empty_cl(n, nf, y.shape[2], y.shape[3], y.device)
+    gw_out = torch.empty_like(w_out); gb_out = torch.empty(1, dtype=torch.float32, device=y.device)
+    g_emb = torch.empty_like(emb) if emb is not None else None
+    ncls = 0
+    gw_ac = gb_ac = None
+    if w_ac is not None:
+        assert w_ac.is_contiguous() and w_ac.shape[0] == nf and probs.is_contiguous() and tuple(probs.shape) == (B, w_ac.shape[1])
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B
+        ncls = w_ac.shape[1]
+        gw_ac = torch.empty_like(w_ac)
+        gb_ac = torch.empty(ncls, dtype=torch.float32, device=y.device)
+    check(lib.ctgan_tail_hinge_heads_bwd(_ptr(y), _ptr(d), _ptr(f), _ptr(probs), _ptr(labels), _ptr(gout), B, hw, nf, ncls, scale, mask_scale,
+                                         _ptr(w_out), _ptr(emb), n_labels, _ptr(w_ac), _ptr(gy), _ptr(gw_out), _ptr(gb_out), _ptr(g_emb),
+                                         _ptr(gw_ac), _ptr(gb_ac), _stream()), 'tail_hinge_heads_bwd')
+    return gy, gw_out, gb_out, g_emb, gw_ac, gb_ac
+
+
 def gen_heads_fwd(y, w_out, b_out, w_ac, b_ac, labels, ac_scale):
     """-> (cost [1] = -mean(d) + ac_scale * CE(a, labels), probs [n,ncls] or None, d [n]) from the last critic block's output."""
     _need_dev(y, w_out, b_out, w_ac, b_ac, labels)
@@ -2441,6 +2499,18 @@ def critic_prep(x_int, fake, seed, sid_deq, sid_alpha, ctr, lo, hi, denom):
     check(lib.ctgan_critic_prep(_ptr(x_int), _ptr(fake), B, d, seed, sid_deq, sid_alpha, _ptr(ctr), lo, hi, denom, _ptr(rf), _ptr(interp),
                                 _stream()), 'critic_prep')
     return rf, interp, both
+
+
+def real_fake_prep(x_int, fake, seed, sid_deq, ctr, lo, hi, denom):
+    """-> rf [2B,d] = [real ; fake] in one launch - critic_prep without the interpolation (the hinge objective's critic step): real = the
+    dequantised x_int, the draws those of rng_uniform on [B,d] (stream sid_deq)."""
+    _need_dev(x_int, fake)
+    B, d = x_int.shape
+    assert x_int.dtype == torch.int32 and x_int.is_contiguous() and fake.is_contiguous() and tuple(fake.shape) == (B, d)
+    assert fake.dtype == torch.float32 and ctr.is_cuda and ctr.dtype == torch.int64
+    rf = torch.empty(2 * B, d, dtype=torch.float32, device=x_int.device)
+    check(lib.ctgan_real_fake_prep(_ptr(x_int), _ptr(fake), B, d, seed, sid_deq, _ptr(ctr), lo, hi, denom, _ptr(rf), _stream()), 'real_fake_prep')
+    return rf
 
 
 def rows_cat_dropout(x, n_extra, keep, seed, stream_id, ctr):

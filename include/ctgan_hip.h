@@ -541,7 +541,10 @@ int ctgan_mean_diff_bwd(const float* gout, int32_t na, int32_t nb, float sa, flo
  * kind CTGAN_LOSS_BCE_G / CTGAN_LOSS_LS_G: d [B] = D(fake);  BCE_G = mean_i bce(d_i, 1),  LS_G = mean_i (d_i - 1)^2.
  * fwd: out[0] = the cost (one workgroup, fixed-order reduction).  bwd: gd = gout[0] * d cost / d d (for BCE (sigmoid(x) - z) / n,
  * finite for any finite logit).                                                                                                   */
-enum { CTGAN_LOSS_BCE_D = 0, CTGAN_LOSS_BCE_G = 1, CTGAN_LOSS_LS_D = 2, CTGAN_LOSS_LS_G = 3 };
+/* Hinge objective (Lim & Ye 2017; Miyato et al. 2018; NOT in the reference), hinge(t) = t >= 0 ? t : 0, so its derivative at t == 0 is 1:
+ * kind CTGAN_LOSS_HINGE_D: d [2B] as above;  HINGE_D = mean_i hinge(1 - d_real_i) + mean_i hinge(1 + d_fake_i)  (no 1/2 in front)
+ * kind CTGAN_LOSS_HINGE_G: d [B] = D(fake);  HINGE_G = -mean_i d_i.                                                               */
+enum { CTGAN_LOSS_BCE_D = 0, CTGAN_LOSS_BCE_G = 1, CTGAN_LOSS_LS_D = 2, CTGAN_LOSS_LS_G = 3, CTGAN_LOSS_HINGE_D = 4, CTGAN_LOSS_HINGE_G = 5 };
 int ctgan_gan_loss_fwd(const float* d, int32_t B, int32_t kind, float* out, ctgan_stream_t stream);
 int ctgan_gan_loss_bwd(const float* d, const float* gout, int32_t B, int32_t kind, float* gd, ctgan_stream_t stream);
 
@@ -638,6 +641,26 @@ int ctgan_tail_heads_bwd_proj(const float* y, const float* d, const float* f, co
                               const float* y_gp, int32_t n_gp, float* gz_gp, ctgan_stream_t stream);
 int ctgan_gen_heads_fwd_proj(const float* y, int32_t n, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
                              int32_t n_labels, const int32_t* labels, float* f, float* d, float* out, ctgan_stream_t stream);
+/* ---- Hinge objective (NOT in the reference): the ResNet critic's fused output stage for L_D = mean_i hinge(1 - D(x_i)) + mean_i hinge(1 +
+ * D(G(z_i))) [+ acgan_scale * CE(class head of the real rows)], hinge(t) = t >= 0 ? t : 0 - the row workgroup and the one-workgroup finish of
+ * ctgan_tail_critic_heads_fwd / ctgan_tail_heads_bwd without the consistency and penalty parts.  ONE entry pair: the projection table
+ * emb [n_labels,nf] (a row's weight is w_out + emb[labels[r % B]]) and the class head w_ac [nf,ncls], b_ac are optional operands, NULL = absent;
+ * both non-NULL: CTGAN_E_BADARG.  y [2B][hw][nf] dense channels-last = relu(dropout(z)), rows [0,B) real, [B,2B) fake; labels [B] (needed with
+ * either operand; a label outside the table is the caller's error, as for the _proj entries).  nf % 4 == 0, nf <= 1024, y / gy 16-byte aligned.
+ *   fwd (two launches): f [2B,nf] = mean_hw y, d [2B], a [2B,ncls]; probs [B,ncls] and ce_i [B] on the real rows; acc[2] as ctgan_accuracy2 on a
+ *     (the step's own, dropped-out rows); out[5] = {hinge + acgan_scale * acgan, hinge, hinge_real, hinge_fake, acgan}.  Without the class head
+ *     a, probs, ce_i, acc are not touched and acgan = 0.
+ *   bwd (one launch), gout = device scalar: gd_r = -gout [1 - d_r >= 0] / B (real rows), +gout [1 + d_r >= 0] / B (fake rows);
+ *     ga = gout acgan_scale (probs - onehot) / B on the real rows; gy = (y > 0) (gd_r (w_out + emb[label]) + W_ac ga_r) / hw * mask_scale;
+ *     gw_out [nf] = sum_r f_r gd_r, gb_out [1] = sum_r gd_r, gw_ac [nf,ncls], gb_ac [ncls], g_emb [n_labels,nf] (every element written; a class
+ *     no row carries gets exact zeros).  Every sum: one wave, lanes over the rows in ascending order, no atomics - the same bits on every run. */
+int ctgan_tail_hinge_heads_fwd(const float* y, int32_t B, int32_t hw, int32_t nf, const float* w_out, const float* b_out, const float* emb,
+                               int32_t n_labels, const float* w_ac, const float* b_ac, int32_t ncls, const int32_t* labels, float acgan_scale,
+                               float* f, float* d, float* a, float* probs, float* ce_i, float* acc, float* out, ctgan_stream_t stream);
+int ctgan_tail_hinge_heads_bwd(const float* y, const float* d, const float* f, const float* probs, const int32_t* labels, const float* gout,
+                               int32_t B, int32_t hw, int32_t nf, int32_t ncls, float acgan_scale, float mask_scale, const float* w_out,
+                               const float* emb, int32_t n_labels, const float* w_ac, float* gy, float* gw_out, float* gb_out, float* g_emb,
+                               float* gw_ac, float* gb_ac, ctgan_stream_t stream);
 int ctgan_gen_heads_bwd_proj(const float* y, const int32_t* labels, const float* gout, int32_t n, int32_t hw, int32_t nf, float mask_scale,
                              const float* w_out, const float* emb, int32_t n_labels, float* gy, ctgan_stream_t stream);
 int ctgan_gp_head_grad_proj(const float* y, const float* w_out, const float* emb, const int32_t* labels, int32_t n_labels, int32_t n,
@@ -755,6 +778,10 @@ int ctgan_rng_advance(uint64_t* ctr, uint64_t by, ctgan_stream_t stream);
 int ctgan_critic_prep(const int32_t* x_int, const float* fake, int32_t b, int32_t d, uint64_t seed, uint64_t sid_deq,
                       uint64_t sid_alpha, const uint64_t* ctr, float lo, float hi, float denom, float* rf, float* interp,
                       ctgan_stream_t stream);
+/* ctgan_critic_prep without the interpolation (the hinge objective's critic step has no x_hat): rf [2b,d] = [2*(x_int/denom - .5) + U[lo,hi) ;
+ * fake] in one launch, the draws those of ctgan_rng_uniform on [b,d] at (seed, stream_id, ctr).  d % 4 == 0, 16-byte aligned pointers.       */
+int ctgan_real_fake_prep(const int32_t* x_int, const float* fake, int32_t b, int32_t d, uint64_t seed, uint64_t stream_id,
+                         const uint64_t* ctr, float lo, float hi, float denom, float* rf, ctgan_stream_t stream);
 /* dst [n_src + n_extra rows] = tf.nn.dropout([src ; src[0:n_extra]], keep) in one launch (input of the critic tail for the
  * two dropout passes, pass 2 on the real half only, :226-227); draws as ctgan_dropout_rng on the concatenated tensor;
  * keep = 1: plain concat.  rows_cat_bwd: the concat's adjoint gsrc[r] = g[r] + g[n_src + r] (r < n_extra).                */
