@@ -304,6 +304,12 @@ SIGNATURES = {
     'ctgan_spectral_scratch_bytes': (c_size_t, [POINTER(c_int64)]),
     'ctgan_spectral_normalize': (c_int, [_p, _p, c_int64, _p, c_int32, c_int64, _p, _p, _p, _p, c_int32, _p, _p]),
     'ctgan_spectral_grad': (c_int, [_p, _p, _p, c_int32, c_int64, _p, _p, _p, _p, _p, _p, _p]),
+    # self-attention core and its gated residual (csrc/attention.hip)
+    'ctgan_attention_fwd': (c_int, [_p, _p, _p, _p, _p, c_int64, c_int32, c_int32, c_int32, _p]),
+    'ctgan_attention_bwd': (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, c_int64, c_int32, c_int32, c_int32, _p]),
+    'ctgan_attn_residual_parts': (c_int, []),
+    'ctgan_attn_residual_fwd': (c_int, [_p, _p, _p, _p, c_int64, _p]),
+    'ctgan_attn_residual_bwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int64, _p]),
 }
 
 

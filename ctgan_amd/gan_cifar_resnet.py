@@ -21,6 +21,7 @@ import torch
 
 from . import functional as F
 from . import kernels as K
+from . import attention as _attention
 from . import tflib as lib
 from .optim import FlatAdam, SpectralNorm
 from .optim import averaged as averaged_weights
@@ -53,6 +54,8 @@ class Config:
     ACGAN_SCALE_G = 0.1
     GP_LAMBDA = 10.0          # the literal 10.0 of :286
     PROJECTION = False        # NOT in the reference: projection head D(x, y) = f . (w_out + E[y]) + b_out (projection_table)
+    ATTENTION_G = False       # NOT in the reference: a self-attention block (attention.SelfAttention) at the generator's 16x16 stage
+    ATTENTION_D = False       # ... and at the critic's 16x16 stage: first order only, so objective='hinge' only (Trainer)
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -77,6 +80,10 @@ def configure(**kw):
     if new.PROJECTION and not (new.CONDITIONAL and not new.ACGAN):
         raise ValueError('PROJECTION=True needs CONDITIONAL=True and ACGAN=False (got CONDITIONAL=%r, ACGAN=%r): the projection head is '
                          'the label path of a conditional critic without the classifier loss' % (new.CONDITIONAL, new.ACGAN))
+    for switch, width in (('ATTENTION_G', 'DIM_G'), ('ATTENTION_D', 'DIM_D')):
+        if getattr(new, switch) and getattr(new, width) % 32:
+            raise ValueError('%s=True needs %s to be a multiple of 32 (got %r): the block projects to %s // 8 and %s // 2 channels, and the '
+                             'attention kernel takes multiples of 4 and of 16' % (switch, width, getattr(new, width), width, width))
     cfg = new
     if cfg.CONDITIONAL and (not cfg.ACGAN) and (not cfg.NORMALIZATION_D) and (not cfg.PROJECTION):
         print("WARNING! Conditional model without normalization in D might be effectively unconditional!")      # :58-59
@@ -218,6 +225,8 @@ def Generator(n_samples, labels, noise=None, groups=1, rng=None):
     out = F.to_channels_last(out.reshape(-1, G, 4, 4))
     out = ResidualBlock('Generator.1', G, G, 3, out, resample='up', labels=labels, groups=groups)
     out = ResidualBlock('Generator.2', G, G, 3, out, resample='up', labels=labels, groups=groups)
+    if cfg.ATTENTION_G:       # 16x16: 256 positions
+        out = _attention.SelfAttention('Generator.Attention', G, out)
     out = ResidualBlock('Generator.3', G, G, 3, out, resample='up', labels=labels, groups=groups)
     fused = _fused_output_stage(out, G, groups)
     if fused is not None:
@@ -286,6 +295,8 @@ def DiscriminatorTrunk(inputs, labels=None):
     D = cfg.DIM_D
     out = inputs.reshape(-1, 3, 32, 32)
     out = OptimizedResBlockDisc1(out)
+    if cfg.ATTENTION_D:       # 16x16: 256 positions
+        out = _attention.SelfAttention('Discriminator.Attention', D, out)
     return ResidualBlock('Discriminator.2', D, D, 3, out, resample='down', labels=labels)
 
 
@@ -530,6 +541,10 @@ class Trainer:
         other value raises ValueError.  None (default): nothing differs from a trainer built without the argument."""
         if objective not in (None, 'hinge'):
             raise ValueError("objective: None or 'hinge' (got %r)" % (objective,))
+        if cfg.ATTENTION_D and objective != 'hinge':
+            raise ValueError("ATTENTION_D=True needs objective='hinge' (got %r): the gradient penalty of the CT objective differentiates the "
+                             'critic twice, and the attention operator is first order only (attention.AttentionFn has no second derivative)'
+                             % (objective,))
         self.objective = objective
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape()

@@ -27,8 +27,9 @@ from .kernels import ConvGeom
 
 def usable(R, rnd, rng, real_int, fake):
     """Is the hand-scheduled hinge step the same computation as Trainer.d_losses_hinge + autograd here?  The conditions of
-    critic_schedule.usable: the fully fused default path, in-kernel Philox draws, a piecewise-linear critic on the few-channel kernels."""
-    return CS.usable(R, rnd, rng, real_int, fake)
+    critic_schedule.usable: the fully fused default path, in-kernel Philox draws, a piecewise-linear critic on the few-channel kernels -
+    and no attention block in the critic (cfg.ATTENTION_D: its launches are not in this schedule, the autograd path serves the step)."""
+    return not getattr(R.cfg, 'ATTENTION_D', False) and CS.usable(R, rnd, rng, real_int, fake)
 
 
 def critic_step(tr, R, real_int, labels, fake, prep=None):

@@ -3209,3 +3209,67 @@ def segment_sums(vals, off, out=None):
     out = _knn_out(out, s, torch.float64, 'segment_sums', vals.device)
     check(lib.ctgan_segment_sums(_ptr(vals), _ptr(off), s, _ptr(out), _stream()), 'segment_sums')
     return out
+
+
+# ---- self-attention core and its gated residual (csrc/attention.hip; NOT in the reference) --------------------------------------------
+ATTN_RESIDUAL_PARTS = lib.ctgan_attn_residual_parts()
+
+
+def _attn_rows(t, what):
+    assert t.dim() == 3 and t.is_contiguous() and t.dtype == torch.float32, 'attention: dense fp32 [n, N, d] rows expected for %s' % what
+    return t.shape
+
+
+def attention_fwd(q, k, v, want_lse=True):
+    """q, k [n, N, dk], v [n, N, dv] dense rows -> (out [n, N, dv], lse [n, N] or None): out_i = sum_j softmax_j(q_i . k_j) v_j per image,
+    no 1 / sqrt(dk) scale, lse the row log-sum-exp the backward needs (want_lse=False under no_grad: it is not written).  One launch; the
+    [N, N] scores never reach memory; exact-fp32 MFMA whatever MMA_DTYPE is.  N % 16 == 0, dk % 4 == 0 in [4, 64], dv % 16 == 0 in
+    [16, 128]: anything else is a ValueError naming the operand."""
+    _need_dev(q, k, v)
+    n, N, dk = _attn_rows(q, 'q')
+    assert tuple(_attn_rows(k, 'k')) == (n, N, dk), 'attention: k is not q-shaped'
+    assert tuple(_attn_rows(v, 'v'))[:2] == (n, N), 'attention: v has other rows than q'
+    dv = v.shape[2]
+    out = torch.empty(n, N, dv, dtype=torch.float32, device=q.device)
+    lse = torch.empty(n, N, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.ctgan_attention_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), n, N, dk, dv, _stream()), 'attention_fwd')
+    return out, lse
+
+
+def attention_bwd(q, k, v, out, lse, gout):
+    """-> (gq, gk, gv) of attention_fwd from its operands, its two results and gout [n, N, dv]: two launches, P recomputed from lse, each
+    gradient owned by one launch (no atomics, the same bits on every run)."""
+    _need_dev(q, k, v, out, lse, gout)
+    n, N, dk = _attn_rows(q, 'q')
+    dv = v.shape[2]
+    assert tuple(_attn_rows(k, 'k')) == (n, N, dk) and tuple(_attn_rows(v, 'v')) == (n, N, dv)
+    assert tuple(_attn_rows(out, 'out')) == (n, N, dv) and tuple(_attn_rows(gout, 'gout')) == (n, N, dv)
+    assert lse.is_contiguous() and tuple(lse.shape) == (n, N)
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty_like(lse)
+    check(lib.ctgan_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv), _ptr(delta),
+                                  n, N, dk, dv, _stream()), 'attention_bwd')
+    return gq, gk, gv
+
+
+def attn_residual_fwd(x, o, gamma):
+    """x + gamma * o with the one-element gate `gamma` read on the device (a replayed graph sees the optimizer's updates); o has x's layout."""
+    _need_dev(x, o, gamma)
+    assert gamma.numel() == 1 and is_dense(x)
+    o = match_layout(o, x)
+    y = empty_like_dense(x)
+    check(lib.ctgan_attn_residual_fwd(_ptr(x), _ptr(o), _ptr(gamma), _ptr(y), x.numel(), _stream()), 'attn_residual_fwd')
+    return y
+
+
+def attn_residual_bwd(gy, o, gamma):
+    """-> (go = gamma * gy in o's layout, ggamma [1] = sum gy o in one fixed order: the same bits on every run); the gradient of x is gy."""
+    _need_dev(gy, o, gamma)
+    assert gamma.numel() == 1 and is_dense(o)
+    gy = match_layout(gy, o)
+    go = empty_like_dense(o)
+    ggamma = torch.empty(1, dtype=torch.float32, device=o.device)
+    part = torch.empty(ATTN_RESIDUAL_PARTS, dtype=torch.float64, device=o.device)
+    check(lib.ctgan_attn_residual_bwd(_ptr(gy), _ptr(o), _ptr(gamma), _ptr(go), _ptr(ggamma), _ptr(part), o.numel(), _stream()),
+          'attn_residual_bwd')
+    return go, ggamma

@@ -1080,6 +1080,28 @@ int ctgan_spectral_normalize(const float* theta, float* theta_bar, int64_t total
 int ctgan_spectral_grad(float* gbar, const float* theta_bar, const int64_t* table, int32_t njobs, int64_t nslices, const float* u,
                         const float* v, const float* sigma, float* scratch, const float* scaler, float* hold, ctgan_stream_t stream);
 
+/* ---- self-attention core and its gated residual (csrc/attention.hip; NOT in the reference) ----------------------------------
+ * Dense rows: q, k [n, N, dk], v, out, gout [n, N, dv], lse, delta [n, N], all fp32; q, k, v, out, gout 16-byte aligned.
+ * ctgan_attention_fwd: out[b, i, :] = sum_j softmax_j(q[b, i] . k[b, j]) v[b, j, :] (no 1 / sqrt(dk) scale; the row maximum is
+ *   subtracted before exp), lse[b, i] = log sum_j exp(q[b, i] . k[b, j]); lse may be NULL (no backward will follow).  One launch.
+ * ctgan_attention_bwd: P = exp(S - lse), delta_i = gout_i . out_i, dS = P o (gout v^T - delta); gq = dS k, gk = dS^T q,
+ *   gv = P^T gout.  Two launches: one over query blocks owns gq (and writes delta, the [n, N] scratch of the second), one over key
+ *   blocks owns gk and gv.
+ * The [N, N] scores exist in registers and LDS only; products on the exact-fp32 MFMA; no atomics, the same bits on every run, an
+ * image's rows independent of the rest of the launch.  N a multiple of 16 (at least 16), dk a multiple of 4 in [4, 64], dv a
+ * multiple of 16 in [16, 128]: anything else CTGAN_E_BADARG naming the operand.
+ * ctgan_attn_residual_fwd: y = x + gamma[0] o over n elements (gamma is read on the device).
+ * ctgan_attn_residual_bwd: go = gamma[0] gy, ggamma[0] = sum gy o in one fixed order (fp64 partial sums in `part`, 8-byte aligned,
+ *   ctgan_attn_residual_parts() doubles, then a plain store); the gradient of x is gy itself.  Two launches.                    */
+int ctgan_attention_fwd(const float* q, const float* k, const float* v, float* out, float* lse, int64_t n, int32_t N, int32_t dk, int32_t dv,
+                        ctgan_stream_t stream);
+int ctgan_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* gout, float* gq,
+                        float* gk, float* gv, float* delta, int64_t n, int32_t N, int32_t dk, int32_t dv, ctgan_stream_t stream);
+int ctgan_attn_residual_parts(void);
+int ctgan_attn_residual_fwd(const float* x, const float* o, const float* gamma, float* y, int64_t n, ctgan_stream_t stream);
+int ctgan_attn_residual_bwd(const float* gy, const float* o, const float* gamma, float* go, float* ggamma, double* part, int64_t n,
+                            ctgan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
