@@ -310,6 +310,8 @@ SIGNATURES = {
     'ctgan_attn_residual_parts': (c_int, []),
     'ctgan_attn_residual_fwd': (c_int, [_p, _p, _p, _p, c_int64, _p]),
     'ctgan_attn_residual_bwd': (c_int, [_p, _p, _p, _p, _p, _p, c_int64, _p]),
+    'ctgan_attention_bwd2': (c_int, [_p] * 15 + [c_int64, c_int32, c_int32, c_int32, _p]),
+    'ctgan_attn_residual_bwd2': (c_int, [_p] * 9 + [c_int64, _p]),
 }
 
 

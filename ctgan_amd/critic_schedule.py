@@ -38,12 +38,13 @@ MERGED_BWD = _os.environ.get('CTGAN_MERGED_BWD', '1') != '0'
 def usable(R, rnd, rng, real_int, fake):
     """Is the hand-scheduled step the same computation as Trainer.d_losses + autograd here?  Only the fully fused default path
     (every switch it builds on at its default), in-kernel Philox draws, a piecewise-linear critic whose first layers run on the
-    direct few-channel kernels."""
+    direct few-channel kernels, no attention block in it (cfg.ATTENTION_D: the schedule below writes out a fixed graph without one)."""
     cfg = R.cfg
     D = cfg.DIM_D
     return bool(MERGED_BWD and rnd is None and rng is not None and fake is not None and R.PREP_FUSION and R.TRUNK_SHARE and R.TAIL_SHARE
                 and R.HEADS_FOLD and R.FUSE_RELU and R.DROP_FUSION and R.HEAD_FUSION and F.FORK_FUSION and F.RESAMPLE_FUSION
                 and F.MASK_IN_DGRAD_EPILOGUE and F.PREMASK_FUSION and F.DEFER_WGRADS and not cfg.NORMALIZATION_D
+                and not getattr(cfg, 'ATTENTION_D', False)           # (the schedule writes out a fixed graph that has no attention block)
                 and R._heads_fusable(rnd, rng) and D % 32 == 0 and cfg.OUTPUT_DIM == 3072
                 and K.fewch_handles(ConvGeom(3, 32, 32, D, 3, 3, 1)) and K.fewch_handles(ConvGeom(3, 16, 16, D, 1, 1, 1))
                 and real_int.is_contiguous() and fake.is_contiguous())

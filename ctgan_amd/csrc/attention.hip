@@ -301,6 +301,288 @@ __global__ __launch_bounds__(TPB) void attention_bwd_kv_kernel(const float* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ second derivative
+// The backward of the backward above: a, b, c are the cotangents of gq, gk, gv.  With T = a k^T + q b^T (the cotangent of dS), dP = gout v^T,
+//   tau_i = sum_j P T,   Pc = P c,   rho_i = sum_j P T dP - 2 tau_i delta_i + gout_i . (Pc)_i              (row statistics: a full key sweep)
+//   W = P o (T - tau),   Sbar = P o (T o dP - dP tau - T delta + gout c^T - rho),   dS = P o (dP - delta)
+//   d q = Sbar k + dS b,  d gout = W v + Pc          (grid = images x blocks of 64 queries: sweep 1 the statistics, sweep 2 the two outputs)
+//   d k = Sbar^T q + dS^T a,  d v = W^T gout         (grid = images x blocks of 64 keys, on the transposed tiles; reads tau, rho [n, N])
+// Every tile quantity is in the accumulator layout [row 4 lg + r of the wave][column li + 16 t of the staged block]; three of them (Sbar, dS,
+// W) cross a wave-private LDS tile each into the A-operand layout.  The staged operands are read both ways (zero columns up to the
+// accumulator's width).  Keys past N have P = 0 by index, so every product with them vanishes; rows past N are clamped and not stored.
+template <int DKT, int DVT>
+__global__ __launch_bounds__(TPB) void attention_bwd2_q_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                               const float* __restrict__ gout, const float* __restrict__ a,
+                                                               const float* __restrict__ b_, const float* __restrict__ c_,
+                                                               float* __restrict__ dq, float* __restrict__ dgout, float* __restrict__ tau_out,
+                                                               float* __restrict__ rho_out, int N, int dk, int dv) {
+    extern __shared__ __align__(16) float smem[];
+    ATT_IDS
+    constexpr int KW = 16 * DKT, LDK = KW + 4, VW = 16 * DVT, LDV = VW + 4;
+    float* sK = smem;
+    float* sB = sK + TN * LDK;
+    float* sV = sB + TN * LDK;
+    float* sC = sV + TN * LDV;
+    float* sX = sC + TN * LDV + wave * 3 * PTILE;         // P (sweep 1), Sbar (sweep 2)
+    float* sY = sX + PTILE;                               // dS
+    float* sZ = sY + PTILE;                               // W
+    const float* qp = q + (base + arow) * dk + lg;
+    const float* ap = a + (base + arow) * dk + lg;
+    const float* gp = gout + (base + arow) * dv + lg;
+    float ls[4], dl[4], tau[4], rho[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int rc = min(r0 + 16 * wave + 4 * lg + r, N - 1);
+        ls[r] = lse[base + rc];
+        dl[r] = delta[base + rc];
+        tau[r] = rho[r] = 0.f;
+    }
+    f32x4 pc[DVT];                                        // Pc, then d gout = Pc + W v
+#pragma unroll
+    for (int c = 0; c < DVT; ++c) pc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // ---- sweep 1: tau, rho, Pc
+    for (int j0 = 0; j0 < N; j0 += TN) {
+        __syncthreads();
+        const int valid = min(TN, N - j0);
+        stage(sK, LDK, KW, k + (base + j0) * dk, valid, dk);
+        stage(sB, LDK, KW, b_ + (base + j0) * dk, valid, dk);
+        stage(sV, LDV, VW, v + (base + j0) * dv, valid, dv);
+        stage(sC, LDV, VW, c_ + (base + j0) * dv, valid, dv);
+        __syncthreads();
+        f32x4 s[4], tt[4], dp[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s[t] = tt[t] = dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kk = 0; kk < dk; kk += 4) {
+            const float qa = qp[kk], aa = ap[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float kb = sK[(li + 16 * t) * LDK + lg + kk];
+                s[t] = MFMA4(qa, kb, s[t]);
+                tt[t] = MFMA4(aa, kb, tt[t]);
+                tt[t] = MFMA4(qa, sB[(li + 16 * t) * LDK + lg + kk], tt[t]);
+            }
+        }
+        for (int kk = 0; kk < dv; kk += 4) {
+            const float ga = gp[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) dp[t] = MFMA4(ga, sV[(li + 16 * t) * LDV + lg + kk], dp[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool in = j0 + li + 16 * t < N;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = in ? expf(s[t][r] - ls[r]) : 0.f;
+                const float pt = p * tt[t][r];
+                tau[r] += pt;
+                rho[r] += pt * dp[t][r];
+                sX[(4 * lg + r) * LDP + li + 16 * t] = p;
+            }
+        }
+        __syncthreads();
+        for (int kk = 0; kk < TN; kk += 4) {
+            const float ax = sX[li * LDP + lg + kk];
+#pragma unroll
+            for (int c = 0; c < DVT; ++c)
+                if (16 * c < dv) pc[c] = MFMA4(ax, sC[(lg + kk) * LDV + li + 16 * c], pc[c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = r0 + 16 * wave + 4 * lg + r, rc = min(row, N - 1);
+        float gpc = 0.f;
+#pragma unroll
+        for (int c = 0; c < DVT; ++c)
+            if (16 * c < dv) gpc += gout[(base + rc) * dv + li + 16 * c] * pc[c][r];
+        tau[r] = row_sum(tau[r]);
+        rho[r] = row_sum(rho[r]) - 2.f * tau[r] * dl[r] + row_sum(gpc);
+        if (li == 0 && row < N) {
+            tau_out[base + row] = tau[r];
+            rho_out[base + row] = rho[r];
+        }
+    }
+    f32x4 g[DKT];
+#pragma unroll
+    for (int c = 0; c < DKT; ++c) g[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // ---- sweep 2: d q, d gout
+    for (int j0 = 0; j0 < N; j0 += TN) {
+        __syncthreads();
+        const int valid = min(TN, N - j0);
+        stage(sK, LDK, KW, k + (base + j0) * dk, valid, dk);
+        stage(sB, LDK, KW, b_ + (base + j0) * dk, valid, dk);
+        stage(sV, LDV, VW, v + (base + j0) * dv, valid, dv);
+        stage(sC, LDV, VW, c_ + (base + j0) * dv, valid, dv);
+        __syncthreads();
+        f32x4 s[4], tt[4], dp[4], gc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s[t] = tt[t] = dp[t] = gc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kk = 0; kk < dk; kk += 4) {
+            const float qa = qp[kk], aa = ap[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float kb = sK[(li + 16 * t) * LDK + lg + kk];
+                s[t] = MFMA4(qa, kb, s[t]);
+                tt[t] = MFMA4(aa, kb, tt[t]);
+                tt[t] = MFMA4(qa, sB[(li + 16 * t) * LDK + lg + kk], tt[t]);
+            }
+        }
+        for (int kk = 0; kk < dv; kk += 4) {
+            const float ga = gp[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                dp[t] = MFMA4(ga, sV[(li + 16 * t) * LDV + lg + kk], dp[t]);
+                gc[t] = MFMA4(ga, sC[(li + 16 * t) * LDV + lg + kk], gc[t]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool in = j0 + li + 16 * t < N;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = in ? expf(s[t][r] - ls[r]) : 0.f;
+                const float T = tt[t][r], d = dp[t][r];
+                const float pbar = T * d - d * tau[r] - T * dl[r] + gc[t][r];
+                const int at = (4 * lg + r) * LDP + li + 16 * t;
+                sX[at] = p * (pbar - rho[r]);
+                sY[at] = p * (d - dl[r]);
+                sZ[at] = p * (T - tau[r]);
+            }
+        }
+        __syncthreads();
+        for (int kk = 0; kk < TN; kk += 4) {
+            const float ax = sX[li * LDP + lg + kk], ay = sY[li * LDP + lg + kk], az = sZ[li * LDP + lg + kk];
+#pragma unroll
+            for (int c = 0; c < DKT; ++c) {
+                g[c] = MFMA4(ax, sK[(lg + kk) * LDK + li + 16 * c], g[c]);
+                g[c] = MFMA4(ay, sB[(lg + kk) * LDK + li + 16 * c], g[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < DVT; ++c)
+                if (16 * c < dv) pc[c] = MFMA4(az, sV[(lg + kk) * LDV + li + 16 * c], pc[c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = r0 + 16 * wave + 4 * lg + r;
+        if (row >= N) continue;
+#pragma unroll
+        for (int c = 0; c < DKT; ++c)
+            if (li + 16 * c < dk) dq[(base + row) * dk + li + 16 * c] = g[c][r];
+#pragma unroll
+        for (int c = 0; c < DVT; ++c)
+            if (li + 16 * c < dv) dgout[(base + row) * dv + li + 16 * c] = pc[c][r];
+    }
+}
+
+template <int DKT, int DVT>
+__global__ __launch_bounds__(TPB) void attention_bwd2_kv_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                                const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                const float* __restrict__ tau, const float* __restrict__ rho,
+                                                                const float* __restrict__ gout, const float* __restrict__ a,
+                                                                const float* __restrict__ b_, const float* __restrict__ c_,
+                                                                float* __restrict__ dkey, float* __restrict__ dval, int N, int dk, int dv) {
+    extern __shared__ __align__(16) float smem[];
+    ATT_IDS
+    constexpr int QW = 16 * DKT, LDQ = QW + 4, GW = 16 * DVT, LDG = GW + 4;
+    float* sQ = smem;
+    float* sA = sQ + TN * LDQ;
+    float* sG = sA + TN * LDQ;
+    float* sL = sG + TN * LDG;
+    float* sD = sL + TN;
+    float* sT = sD + TN;
+    float* sR = sT + TN;
+    float* sX = sR + TN + wave * 3 * PTILE;               // Sbar^T
+    float* sY = sX + PTILE;                               // dS^T
+    float* sZ = sY + PTILE;                               // W^T
+    const float* kp = k + (base + arow) * dk + lg;        // this workgroup's rows are keys
+    const float* bp = b_ + (base + arow) * dk + lg;
+    const float* vp = v + (base + arow) * dv + lg;
+    const float* cp = c_ + (base + arow) * dv + lg;
+    f32x4 ak[DKT], av[DVT];
+#pragma unroll
+    for (int c = 0; c < DKT; ++c) ak[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < DVT; ++c) av[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int i0 = 0; i0 < N; i0 += TN) {
+        __syncthreads();
+        const int valid = min(TN, N - i0);
+        stage(sQ, LDQ, QW, q + (base + i0) * dk, valid, dk);
+        stage(sA, LDQ, QW, a + (base + i0) * dk, valid, dk);
+        stage(sG, LDG, GW, gout + (base + i0) * dv, valid, dv);
+        if (threadIdx.x < TN) {
+            const bool in = (int)threadIdx.x < valid;
+            sL[threadIdx.x] = in ? lse[base + i0 + threadIdx.x] : 0.f;
+            sD[threadIdx.x] = in ? delta[base + i0 + threadIdx.x] : 0.f;
+            sT[threadIdx.x] = in ? tau[base + i0 + threadIdx.x] : 0.f;
+            sR[threadIdx.x] = in ? rho[base + i0 + threadIdx.x] : 0.f;
+        }
+        __syncthreads();
+        f32x4 s[4], tt[4], dp[4], gc[4];                  // [key 4 lg + r of the wave][query li + 16 t of the block]
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s[t] = tt[t] = dp[t] = gc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kk = 0; kk < dk; kk += 4) {
+            const float ka = kp[kk], ba = bp[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float qb = sQ[(li + 16 * t) * LDQ + lg + kk];
+                s[t] = MFMA4(ka, qb, s[t]);
+                tt[t] = MFMA4(ka, sA[(li + 16 * t) * LDQ + lg + kk], tt[t]);
+                tt[t] = MFMA4(ba, qb, tt[t]);
+            }
+        }
+        for (int kk = 0; kk < dv; kk += 4) {
+            const float va = vp[kk], ca = cp[kk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float gb = sG[(li + 16 * t) * LDG + lg + kk];
+                dp[t] = MFMA4(va, gb, dp[t]);
+                gc[t] = MFMA4(ca, gb, gc[t]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool in = i0 + li + 16 * t < N;
+            const float L = sL[li + 16 * t], D = sD[li + 16 * t], Tau = sT[li + 16 * t], Rho = sR[li + 16 * t];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = in ? expf(s[t][r] - L) : 0.f;
+                const float T = tt[t][r], d = dp[t][r];
+                const float pbar = T * d - d * Tau - T * D + gc[t][r];
+                const int at = (4 * lg + r) * LDP + li + 16 * t;
+                sX[at] = p * (pbar - Rho);
+                sY[at] = p * (d - D);
+                sZ[at] = p * (T - Tau);
+            }
+        }
+        __syncthreads();
+        for (int kk = 0; kk < TN; kk += 4) {
+            const float ax = sX[li * LDP + lg + kk], ay = sY[li * LDP + lg + kk], az = sZ[li * LDP + lg + kk];
+#pragma unroll
+            for (int c = 0; c < DKT; ++c) {
+                ak[c] = MFMA4(ax, sQ[(lg + kk) * LDQ + li + 16 * c], ak[c]);
+                ak[c] = MFMA4(ay, sA[(lg + kk) * LDQ + li + 16 * c], ak[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < DVT; ++c) av[c] = MFMA4(az, sG[(lg + kk) * LDG + li + 16 * c], av[c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = r0 + 16 * wave + 4 * lg + r;
+        if (row >= N) continue;
+#pragma unroll
+        for (int c = 0; c < DKT; ++c)
+            if (li + 16 * c < dk) dkey[(base + row) * dk + li + 16 * c] = ak[c][r];
+#pragma unroll
+        for (int c = 0; c < DVT; ++c)
+            if (li + 16 * c < dv) dval[(base + row) * dv + li + 16 * c] = av[c][r];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ gated residual
 __global__ __launch_bounds__(TPB) void attn_residual_fwd_kernel(const float* __restrict__ x, const float* __restrict__ o,
                                                                 const float* __restrict__ gamma, float* __restrict__ y, long long n) {
@@ -320,6 +602,35 @@ __global__ __launch_bounds__(TPB) void attn_residual_bwd_kernel(const float* __r
         const float d = gy[i];
         go[i] = g * d;
         acc += (double)d * (double)o[i];
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = TPB / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// The backward of the backward above, cgo / cgg the cotangents of go / ggamma: dgy = gamma cgo + cgg o, dO = cgg gy,
+// part[block] = the block's share of d gamma = sum cgo gy (the order of attn_residual_bwd_kernel).  cgg may be NULL (zero: dO is not written).
+__global__ __launch_bounds__(TPB) void attn_residual_bwd2_kernel(const float* __restrict__ cgo, const float* __restrict__ gy,
+                                                                 const float* __restrict__ o, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ cgg, float* __restrict__ dgy, float* __restrict__ dO,
+                                                                 double* __restrict__ part, long long n) {
+    __shared__ double red[TPB];
+    const float g = gamma[0];
+    const float s = cgg ? cgg[0] : 0.f;
+    double acc = 0.;
+    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)RES_PARTS * TPB) {
+        const float x = cgo[i], d = gy[i];
+        if (cgg) {
+            dgy[i] = g * x + s * o[i];
+            dO[i] = s * d;
+        } else {
+            dgy[i] = g * x;
+        }
+        acc += (double)x * (double)d;
     }
     red[threadIdx.x] = acc;
     __syncthreads();
@@ -408,6 +719,41 @@ int launch_bwd_kv_dv(int dvt, const float* q, const float* k, const float* v, co
     return launch_bwd_kv<DKT, 8>(q, k, v, lse, delta, gout, gk, gv, grid, N, dk, dv, st);
 }
 
+// the operands of ctgan_attention_bwd2 behind one name each (nine inputs, two [n, N] scratch rows, four outputs)
+struct Bwd2Args {
+    const float *q, *k, *v, *lse, *delta, *gout, *a, *b, *c;
+    float *dq, *dkey, *dval, *dgout, *tau, *rho;
+};
+
+inline size_t bwd2_q_lds(int dkt, int dvt) {
+    return sizeof(float) * (2 * (size_t)TN * (16 * dkt + 4) + 2 * (size_t)TN * (16 * dvt + 4) + 12 * PTILE);
+}
+inline size_t bwd2_kv_lds(int dkt, int dvt) {
+    return sizeof(float) * (2 * (size_t)TN * (16 * dkt + 4) + (size_t)TN * (16 * dvt + 4) + 4 * TN + 12 * PTILE);
+}
+
+template <int DKT, int DVT>
+int launch_bwd2(const Bwd2Args& p, unsigned grid, int N, int dk, int dv, hipStream_t st) {
+    static size_t granted_q = 0, granted_kv = 0;
+    const size_t lds_q = bwd2_q_lds(DKT, DVT), lds_kv = bwd2_kv_lds(DKT, DVT);
+    if (int rc = grant_lds(attention_bwd2_q_kernel<DKT, DVT>, lds_q, &granted_q, "attention_bwd2 (dq, dgout)")) return rc;
+    if (int rc = grant_lds(attention_bwd2_kv_kernel<DKT, DVT>, lds_kv, &granted_kv, "attention_bwd2 (dk, dv)")) return rc;
+    hipLaunchKernelGGL((attention_bwd2_q_kernel<DKT, DVT>), dim3(grid), dim3(TPB), lds_q, st, p.q, p.k, p.v, p.lse, p.delta, p.gout, p.a, p.b, p.c,
+                       p.dq, p.dgout, p.tau, p.rho, N, dk, dv);
+    if (int rc = ctgan_check_launch("attention_bwd2 (dq, dgout)")) return rc;
+    hipLaunchKernelGGL((attention_bwd2_kv_kernel<DKT, DVT>), dim3(grid), dim3(TPB), lds_kv, st, p.q, p.k, p.v, p.lse, p.delta, p.tau, p.rho, p.gout,
+                       p.a, p.b, p.c, p.dkey, p.dval, N, dk, dv);
+    return ctgan_check_launch("attention_bwd2 (dk, dv)");
+}
+
+template <int DKT>
+int launch_bwd2_dv(int dvt, const Bwd2Args& p, unsigned grid, int N, int dk, int dv, hipStream_t st) {
+    if (dvt <= 1) return launch_bwd2<DKT, 1>(p, grid, N, dk, dv, st);
+    if (dvt <= 2) return launch_bwd2<DKT, 2>(p, grid, N, dk, dv, st);
+    if (dvt <= 4) return launch_bwd2<DKT, 4>(p, grid, N, dk, dv, st);
+    return launch_bwd2<DKT, 8>(p, grid, N, dk, dv, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -445,6 +791,22 @@ int ctgan_attention_bwd(const float* q, const float* k, const float* v, const fl
     return launch_bwd_kv_dv<4>(dvt, q, k, v, lse, delta, gout, gk, gv, grid, N, dk, dv, S(stream));
 }
 
+int ctgan_attention_bwd2(const float* q, const float* k, const float* v, const float* lse, const float* delta, const float* gout, const float* a,
+                         const float* b, const float* c, float* dq, float* dkey, float* dval, float* dgout, float* tau, float* rho, int64_t n,
+                         int32_t N, int32_t dk, int32_t dv, ctgan_stream_t stream) {
+    if (int rc = check_shape("attention_bwd2", n, N, dk, dv)) return rc;
+    if (!q || !k || !v || !lse || !delta || !gout || !a || !b || !c || !dq || !dkey || !dval || !dgout || !tau || !rho)
+        return ctgan_fail(CTGAN_E_BADARG, "attention_bwd2: a null pointer (q, k, v, lse, delta, gout, a, b, c, dq, dk, dv, dgout, tau, rho)");
+    if (misaligned16(q) || misaligned16(k) || misaligned16(v) || misaligned16(gout) || misaligned16(a) || misaligned16(b) || misaligned16(c))
+        return ctgan_fail(CTGAN_E_BADARG, "attention_bwd2: q, k, v, gout, a, b, c not 16-byte aligned");
+    const unsigned grid = (unsigned)(n * ((N + TM - 1) / TM));
+    const int dkt = (dk + 15) / 16, dvt = dv / 16;
+    const Bwd2Args p = {q, k, v, lse, delta, gout, a, b, c, dq, dkey, dval, dgout, tau, rho};
+    if (dkt <= 1) return launch_bwd2_dv<1>(dvt, p, grid, N, dk, dv, S(stream));
+    if (dkt <= 2) return launch_bwd2_dv<2>(dvt, p, grid, N, dk, dv, S(stream));
+    return launch_bwd2_dv<4>(dvt, p, grid, N, dk, dv, S(stream));
+}
+
 int ctgan_attn_residual_parts(void) { return RES_PARTS; }
 
 int ctgan_attn_residual_fwd(const float* x, const float* o, const float* gamma, float* y, int64_t n, ctgan_stream_t stream) {
@@ -463,6 +825,18 @@ int ctgan_attn_residual_bwd(const float* gy, const float* o, const float* gamma,
     if (int rc = ctgan_check_launch("attn_residual_bwd")) return rc;
     hipLaunchKernelGGL(attn_residual_finish_kernel, dim3(1), dim3(RES_PARTS), 0, S(stream), part, ggamma);
     return ctgan_check_launch("attn_residual_bwd (finish)");
+}
+
+int ctgan_attn_residual_bwd2(const float* cgo, const float* gy, const float* o, const float* gamma, const float* cgg, float* dgy, float* d_o,
+                             float* dgamma, double* part, int64_t n, ctgan_stream_t stream) {
+    if (n < 1) return ctgan_fail(CTGAN_E_BADARG, "attn_residual_bwd2: n = %lld elements", (long long)n);
+    if (!cgo || !gy || !o || !gamma || !dgy || !dgamma || !part || (cgg && !d_o))
+        return ctgan_fail(CTGAN_E_BADARG, "attn_residual_bwd2: a null pointer (cgo, gy, o, gamma, dgy, dgamma, part; d_o with cgg; only cgg may be NULL)");
+    if (reinterpret_cast<uintptr_t>(part) & 7) return ctgan_fail(CTGAN_E_BADARG, "attn_residual_bwd2: part not 8-byte aligned");
+    hipLaunchKernelGGL(attn_residual_bwd2_kernel, dim3(RES_PARTS), dim3(TPB), 0, S(stream), cgo, gy, o, gamma, cgg, dgy, d_o, part, (long long)n);
+    if (int rc = ctgan_check_launch("attn_residual_bwd2")) return rc;
+    hipLaunchKernelGGL(attn_residual_finish_kernel, dim3(1), dim3(RES_PARTS), 0, S(stream), part, dgamma);
+    return ctgan_check_launch("attn_residual_bwd2 (finish)");
 }
 
 }  // extern "C"

@@ -55,7 +55,9 @@ class Config:
     GP_LAMBDA = 10.0          # the literal 10.0 of :286
     PROJECTION = False        # NOT in the reference: projection head D(x, y) = f . (w_out + E[y]) + b_out (projection_table)
     ATTENTION_G = False       # NOT in the reference: a self-attention block (attention.SelfAttention) at the generator's 16x16 stage
-    ATTENTION_D = False       # ... and at the critic's 16x16 stage: first order only, so objective='hinge' only (Trainer)
+    ATTENTION_D = False       # ... and at the critic's 16x16 stage: first order only, so objective='hinge' only (Trainer) unless ...
+    ATTENTION_SECOND_ORDER = False    # ... the critic's block on the twice-differentiable operators (attention.attention2): the
+                                      # CT objective's gradient penalty may stand behind it.  Needs ATTENTION_D; the generator's block is untouched
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -84,6 +86,9 @@ def configure(**kw):
         if getattr(new, switch) and getattr(new, width) % 32:
             raise ValueError('%s=True needs %s to be a multiple of 32 (got %r): the block projects to %s // 8 and %s // 2 channels, and the '
                              'attention kernel takes multiples of 4 and of 16' % (switch, width, getattr(new, width), width, width))
+    if new.ATTENTION_SECOND_ORDER and not new.ATTENTION_D:
+        raise ValueError('ATTENTION_SECOND_ORDER=True needs ATTENTION_D=True: it selects the twice-differentiable operators of the '
+                         "critic's attention block, and there is no such block without ATTENTION_D")
     cfg = new
     if cfg.CONDITIONAL and (not cfg.ACGAN) and (not cfg.NORMALIZATION_D) and (not cfg.PROJECTION):
         print("WARNING! Conditional model without normalization in D might be effectively unconditional!")      # :58-59
@@ -296,7 +301,7 @@ def DiscriminatorTrunk(inputs, labels=None):
     out = inputs.reshape(-1, 3, 32, 32)
     out = OptimizedResBlockDisc1(out)
     if cfg.ATTENTION_D:       # 16x16: 256 positions
-        out = _attention.SelfAttention('Discriminator.Attention', D, out)
+        out = _attention.SelfAttention('Discriminator.Attention', D, out, second_order=cfg.ATTENTION_SECOND_ORDER)
     return ResidualBlock('Discriminator.2', D, D, 3, out, resample='down', labels=labels)
 
 
@@ -443,7 +448,7 @@ BATCH_FAKES = _os.environ.get('CTGAN_BATCH_FAKES', '1') != '0'
 
 
 def _heads_fusable(rnd, rng):
-    return (HEAD_FUSION and rnd is None and _critic_piecewise_linear() and _tail_fusable(0.8, 0.5, 0.5, None, rng)
+    return (HEAD_FUSION and rnd is None and not cfg.NORMALIZATION_D and _tail_fusable(0.8, 0.5, 0.5, None, rng)
             and cfg.DIM_D % 4 == 0 and cfg.DIM_D <= 1024)
 
 
@@ -484,7 +489,7 @@ def gradient_penalty_branch(interp, labels, rng, rnd=None, trunk_tape=None, tail
     """GP = lambda * mean((||dD(x_hat)/dx_hat||_2 - 1)^2) with its own dropout masks (:277-286): critic forward on x_hat,
     data gradient back to x_hat under create_graph.  -> (gp, slopes, dD/dx_hat).  interp must require grad.
     defer_mean: gp is returned as a slot that the caller's F.critic_tail_heads(..., gp, slopes=slopes, gp_lambda=...) fills."""
-    fuse_heads = _heads_fusable(rnd, rng)
+    fuse_heads = _heads_fusable(rnd, rng) and _critic_piecewise_linear()
     with F.weight_grads(not _critic_piecewise_linear()):
         if fuse_heads:
             if trunk_tape is not None:       # the trunk's forward launches were shared with the dropout passes (F.tape_record)
@@ -541,10 +546,10 @@ class Trainer:
         other value raises ValueError.  None (default): nothing differs from a trainer built without the argument."""
         if objective not in (None, 'hinge'):
             raise ValueError("objective: None or 'hinge' (got %r)" % (objective,))
-        if cfg.ATTENTION_D and objective != 'hinge':
+        if cfg.ATTENTION_D and objective != 'hinge' and not cfg.ATTENTION_SECOND_ORDER:
             raise ValueError("ATTENTION_D=True needs objective='hinge' (got %r): the gradient penalty of the CT objective differentiates the "
-                             'critic twice, and the attention operator is first order only (attention.AttentionFn has no second derivative)'
-                             % (objective,))
+                             'critic twice, and the attention operator is first order only (attention.AttentionFn has no second derivative).  '
+                             'ATTENTION_SECOND_ORDER=True builds the block from the twice-differentiable operators instead' % (objective,))
         self.objective = objective
         self.aug_policy = K.diffaug_policy(augment)
         self.aug_shape = image_shape()
@@ -614,7 +619,7 @@ class Trainer:
                 else:
                     rf, interp, both = K.critic_prep(real_int, fake, rng.seed, rng._sid(), rng._sid(), rng.ctr, 0.0, 1. / 128, 256.0)
                 real = rf[:B]
-                if TRUNK_SHARE and not cfg.NORMALIZATION_D and _heads_fusable(rnd, rng):
+                if TRUNK_SHARE and _critic_piecewise_linear() and _heads_fusable(rnd, rng):
                     # blocks 1-2 once for [real ; fake ; x_hat]: the two passes below replay rows of it (F.tape_record)
                     with F.tape_record() as tape:
                         DiscriminatorTrunk(both)
@@ -634,7 +639,7 @@ class Trainer:
         # branches, so that the penalty's 64-row double backward overlaps the main pass's backward - was measured twice: -1 % in round 1,
         # -2.5 % in round 3 (16.47 vs 16.06 ms on one box): removed.)
         interp.requires_grad_(True)
-        fuse_heads = _heads_fusable(rnd, rng)
+        fuse_heads = _heads_fusable(rnd, rng) and _critic_piecewise_linear()
         use_ac = cfg.CONDITIONAL and cfg.ACGAN
         tail = None
         if TAIL_SHARE and tape is not None and fuse_heads:
@@ -1007,7 +1012,10 @@ def train(data_dir, n_examples=50000, iters=None, out_dir='.', seed=2024, use_gr
 
 
 def _critic_piecewise_linear():
-    return not cfg.NORMALIZATION_D
+    """Does the gradient penalty reach the weights through the backward ops alone (so that the penalty pass may skip its forward's weight
+    gradients, share the dropout passes' forward launches and start its backward at the fused heads)?  Not with a Layernorm in the critic,
+    and not with the attention block (softmax): those steps run on the autograd path of Trainer.d_losses."""
+    return not cfg.NORMALIZATION_D and not cfg.ATTENTION_D
 
 
 def _this_module():

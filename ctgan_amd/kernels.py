@@ -3239,6 +3239,12 @@ def attention_fwd(q, k, v, want_lse=True):
 def attention_bwd(q, k, v, out, lse, gout):
     """-> (gq, gk, gv) of attention_fwd from its operands, its two results and gout [n, N, dv]: two launches, P recomputed from lse, each
     gradient owned by one launch (no atomics, the same bits on every run)."""
+    return attention_bwd_delta(q, k, v, out, lse, gout)[:3]
+
+
+def attention_bwd_delta(q, k, v, out, lse, gout):
+    """attention_bwd, the same two launches -> (gq, gk, gv, delta [n, N]): delta_i = gout_i . out_i, the row scratch the first launch writes,
+    is an operand of the second derivative (attention_bwd2)."""
     _need_dev(q, k, v, out, lse, gout)
     n, N, dk = _attn_rows(q, 'q')
     dv = v.shape[2]
@@ -3249,7 +3255,25 @@ def attention_bwd(q, k, v, out, lse, gout):
     delta = torch.empty_like(lse)
     check(lib.ctgan_attention_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv), _ptr(delta),
                                   n, N, dk, dv, _stream()), 'attention_bwd')
-    return gq, gk, gv
+    return gq, gk, gv, delta
+
+
+def attention_bwd2(q, k, v, lse, delta, gout, a, b, c):
+    """The backward of attention_bwd: a, b, c the cotangents of gq, gk, gv (dense, shaped like them) -> (dq, dk, dv, dgout), the total
+    derivative through out, lse and delta as well.  Two launches - query blocks (a statistics sweep, then dq and dgout), key
+    blocks (dk, dv) - with two [n, N] scratch rows between them; no [N, N] tensor, no atomics, the same bits on every run, exact-fp32 MFMA.
+    The shape contract of attention_fwd."""
+    _need_dev(q, k, v, lse, delta, gout, a, b, c)
+    n, N, dk = _attn_rows(q, 'q')
+    dv = v.shape[2]
+    assert tuple(_attn_rows(k, 'k')) == (n, N, dk) and tuple(_attn_rows(v, 'v')) == (n, N, dv) and tuple(_attn_rows(gout, 'gout')) == (n, N, dv)
+    assert tuple(_attn_rows(a, 'a')) == (n, N, dk) and tuple(_attn_rows(b, 'b')) == (n, N, dk) and tuple(_attn_rows(c, 'c')) == (n, N, dv)
+    assert lse.is_contiguous() and tuple(lse.shape) == (n, N) and delta.is_contiguous() and tuple(delta.shape) == (n, N)
+    dq, dkey, dval, dgout = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(gout)
+    stats = torch.empty(2, n, N, dtype=torch.float32, device=q.device)
+    check(lib.ctgan_attention_bwd2(_ptr(q), _ptr(k), _ptr(v), _ptr(lse), _ptr(delta), _ptr(gout), _ptr(a), _ptr(b), _ptr(c), _ptr(dq), _ptr(dkey),
+                                   _ptr(dval), _ptr(dgout), _ptr(stats[0]), _ptr(stats[1]), n, N, dk, dv, _stream()), 'attention_bwd2')
+    return dq, dkey, dval, dgout
 
 
 def attn_residual_fwd(x, o, gamma):
@@ -3273,3 +3297,19 @@ def attn_residual_bwd(gy, o, gamma):
     check(lib.ctgan_attn_residual_bwd(_ptr(gy), _ptr(o), _ptr(gamma), _ptr(go), _ptr(ggamma), _ptr(part), o.numel(), _stream()),
           'attn_residual_bwd')
     return go, ggamma
+
+
+def attn_residual_bwd2(gy, o, gamma, cgo, cgg=None):
+    """The backward of attn_residual_bwd with cgo / cgg [1] the cotangents of go / ggamma -> (dgy = gamma cgo + cgg o, d_o = cgg gy, dgamma
+    [1] = sum cgo gy in the fixed order of attn_residual_bwd), all in o's layout.  gamma and cgg are read on the device.  cgg None: zero -
+    dgy = gamma cgo, d_o is None.  Two launches."""
+    _need_dev(gy, o, gamma, cgo, cgg)
+    assert gamma.numel() == 1 and is_dense(o) and (cgg is None or cgg.numel() == 1)
+    gy, cgo = match_layout(gy, o), match_layout(cgo, o)
+    dgy = empty_like_dense(o)
+    d_o = empty_like_dense(o) if cgg is not None else None
+    dgamma = torch.empty(1, dtype=torch.float32, device=o.device)
+    part = torch.empty(ATTN_RESIDUAL_PARTS, dtype=torch.float64, device=o.device)
+    check(lib.ctgan_attn_residual_bwd2(_ptr(cgo), _ptr(gy), _ptr(o), _ptr(gamma), _ptr(cgg), _ptr(dgy), _ptr(d_o), _ptr(dgamma), _ptr(part),
+                                       o.numel(), _stream()), 'attn_residual_bwd2')
+    return dgy, d_o, dgamma

@@ -1101,6 +1101,21 @@ int ctgan_attn_residual_parts(void);
 int ctgan_attn_residual_fwd(const float* x, const float* o, const float* gamma, float* y, int64_t n, ctgan_stream_t stream);
 int ctgan_attn_residual_bwd(const float* gy, const float* o, const float* gamma, float* go, float* ggamma, double* part, int64_t n,
                             ctgan_stream_t stream);
+/* The second derivative: the backward of ctgan_attention_bwd, with a, b, c the cotangents of gq, gk, gv (shaped like them,
+ * 16-byte aligned, never NULL: the host passes zeros for an absent one) and lse, delta the rows that ctgan_attention_bwd read / wrote.
+ *   T = a k^T + q b^T, dP = gout v^T, tau_i = sum_j P T, Pc = P c, rho_i = sum_j P T dP - 2 tau_i delta_i + gout_i . (Pc)_i,
+ *   W = P o (T - tau), Sbar = P o (T o dP - dP tau - T delta + gout c^T - rho), dS = P o (dP - delta);
+ *   dq = Sbar k + dS b, dgout = W v + Pc, dk = Sbar^T q + dS^T a, dv = W^T gout.
+ * Two launches: one over query blocks (a first key sweep for tau, rho, Pc, a second for dq and dgout; tau, rho go to the [n, N] scratch
+ * rows `tau`, `rho`), one over key blocks for dk and dv.  The same shape contract and the same properties as the first derivative.
+ * ctgan_attn_residual_bwd2: the backward of ctgan_attn_residual_bwd with cgo / cgg the cotangents of go / ggamma: dgy = gamma[0] cgo +
+ *   cgg[0] o, d_o = cgg[0] gy, dgamma[0] = sum cgo gy (the partial sums of ctgan_attn_residual_bwd).  gamma and cgg are read on the
+ *   device; cgg may be NULL (zero), then d_o may be NULL and is not written.  Two launches.                                       */
+int ctgan_attention_bwd2(const float* q, const float* k, const float* v, const float* lse, const float* delta, const float* gout, const float* a,
+                         const float* b, const float* c, float* dq, float* dk, float* dv, float* dgout, float* tau, float* rho, int64_t n,
+                         int32_t N, int32_t dk_width, int32_t dv_width, ctgan_stream_t stream);
+int ctgan_attn_residual_bwd2(const float* cgo, const float* gy, const float* o, const float* gamma, const float* cgg, float* dgy, float* d_o,
+                             float* dgamma, double* part, int64_t n, ctgan_stream_t stream);
 
 #ifdef __cplusplus
 }
